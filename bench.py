@@ -131,7 +131,16 @@ def parse():
     ap.add_argument("--detail", default=None,
                     help="file the FULL result (notes, stage tables, per-kernel counters) is written to; the printed line is a bounded "
                          "extract of it (umeregrobust_amd/benchline.py).  Default: gpurun_out/bench_detail.json under the repo")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned for the pairs of its LAST step as DIR/<name>.npy "
+                         "(float32 / float64, <= 64 MB in all; one leading axis over the pairs, pair_index.npy = their global indices): "
+                         "SE(3) hypotheses, matches, match distances, match probabilities, drawn sub-sample, and the UME matrices of a fixed "
+                         "seeded sample of keypoint rows (ume_rows.npy).  A step whose pairs do not fit is written as a fixed seeded sample "
+                         "of them.  The copies are taken on each pair's stream inside the last timed step; rank 0's pairs only")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def _synth_one(job):
@@ -161,6 +170,33 @@ def synth_many(seeds, kw, workers):
 def gate_counts(rre, rte):
     rre, rte = np.asarray(rre, np.float64), np.asarray(rte, np.float64)
     return [int(((rre <= r) & (rte <= t)).sum()) for r, t in GATES]
+
+
+DUMP_LIMIT_BYTES = 64_000_000   # --dump-outputs: all files together, .npy headers included
+DUMP_UME_ROWS = 256              # keypoint rows of the UME matrices written per pair (fixed seeded sample)
+
+
+def write_outputs(out_dir, kept, rows, pair_index):
+    """--dump-outputs.  kept: [{name: float32 / float64 device tensor or host array}] per pair of the last timed step, in submission
+    order; rows: the sampled keypoint rows of ume_src / ume_tgt; pair_index: the pairs' global indices.  -> out_dir/<name>.npy, each
+    stacked over the pairs.  If the step's pairs do not fit in DUMP_LIMIT_BYTES, a fixed seeded sample of them is written (sorted;
+    pair_index.npy says which)."""
+    n_pairs = len(kept)
+    per_pair = sum(int(v.nbytes) for v in kept[0].values())
+    fixed = (len(rows) + n_pairs) * 8 + 1024 * (len(kept[0]) + 2)          # pair_index, ume_rows, one header per file
+    k = max(1, min(n_pairs, (DUMP_LIMIT_BYTES - fixed) // max(per_pair, 1)))
+    sel = np.arange(n_pairs) if k == n_pairs else np.sort(np.random.RandomState(0).choice(n_pairs, k, replace=False))
+    arrays = {"pair_index": np.asarray(pair_index, np.float64)[sel], "ume_rows": np.asarray(rows, np.float64)}
+    for name in kept[0]:
+        arrays[name] = np.stack([kept[i][name].cpu().numpy() if hasattr(kept[i][name], "cpu") else kept[i][name] for i in sel])
+        assert arrays[name].dtype in (np.float32, np.float64), (name, arrays[name].dtype)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    total = sum(os.path.getsize(os.path.join(out_dir, name + ".npy")) for name in arrays)
+    assert total <= DUMP_LIMIT_BYTES or k == 1, total
+    return {"dir": out_dir, "pairs_written": int(k), "pairs_in_the_step": n_pairs, "bytes": int(total),
+            "arrays": {name: list(v.shape) for name, v in arrays.items()}}
 
 
 def main():
@@ -275,14 +311,33 @@ def main():
         h = pipe.submit(e.src_pts, e.tgt_pts, e.src_feat, e.tgt_feat, src_inds=e.src_inds, tgt_inds=e.tgt_inds,
                         timing=tm, pair=e.pair, rng=rngs[i % len(rngs)])
         h.entry = e
+        h.index = i
         if tm is timing:
             mom_bytes_log.extend(e.mom_bytes)
         return h
+
+    # --dump-outputs: the pairs i in [dump.lo, dump.hi) of the timed leg keep a copy of what pipe.finish returned them, taken on the pair's
+    # stream as it finishes (the graph's outputs and the slot's buffers belong to the slot's next pair); indices become float64
+    dump = SimpleNamespace(lo=0, hi=0, kept=[], index=[], rows=None, rows_dev=None)
+
+    def keep_outputs(i, out):
+        f32 = lambda x: x.to(torch.float32, copy=True)    # noqa: E731
+        kept = {"rtume_tform": f32(out.rtume_tform[0]), "match": out.match[0].to(torch.float64, copy=True), "match_d": f32(out.match_d[0]),
+                "ume_src": out.ume_src[0].index_select(0, dump.rows_dev).to(torch.float32),
+                "ume_tgt": out.ume_tgt[0].index_select(0, dump.rows_dev).to(torch.float32)}
+        if out.prob is not None:
+            kept["prob"] = f32(out.prob.reshape(-1))
+        if out.cond is not None:
+            kept["cond"] = np.asarray(out.cond, dtype=np.float64).copy()
+        dump.kept.append(kept)
+        dump.index.append(rank + world * i)
 
     def finish(h):
         out = leg.pipe.finish(h, order_caller=False)            # host RNG draw + SE(3) hypotheses (consumed on the pair's own stream below)
         with torch.cuda.stream(leg.pipe.stream_of(h)):          # a7 + recall gates, on the device
             ops.hypothesis_gates(out.rtume_tform[0], h.entry.gt, leg_counts(h.slot))
+            if dump.lo <= h.index < dump.hi:
+                keep_outputs(h.index, out)
 
     roofline_every = a.roofline_every if a.roofline_every else max(1, a.steps // 5)
     # positions of a sampled step: the first n_alone pairs run alone, pair k_situ is timed inside the pipeline.  Short steps (the K1 tests
@@ -324,11 +379,21 @@ def main():
     torch.cuda.synchronize()
     for c_ in counts:
         c_.zero_()
+    if a.dump_outputs:
+        n_kp_pool = int(pool[0].src_inds.numel())
+        dump.rows = np.sort(np.random.RandomState(0).choice(n_kp_pool, min(n_kp_pool, DUMP_UME_ROWS), replace=False))
+        dump.rows_dev = torch.from_numpy(dump.rows).to(dev)
+        dump.lo, dump.hi = (a.warmup + a.steps - 1) * P, (a.warmup + a.steps) * P
     fence()
     t0 = time.perf_counter()
     run(a.warmup * P, a.steps * P, True)
     fence()
     elapsed = time.perf_counter() - t0
+    dump.lo = dump.hi = 0
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = write_outputs(a.dump_outputs, dump.kept, dump.rows, dump.index)
+    dump.kept, dump.index = [], []
     counts = torch.stack(counts).sum(0).double()
     if collective:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -614,7 +679,7 @@ def main():
                                         "timed inside the pipeline, beside the kernels of the other pairs in flight", "host_draw_thread": bool(a.threaded_draw), "clouds_per_moment_launch": 2 if a.batch_clouds else 1,
                    "excluded_from_value": "the two keypoint draws of evaluate.py:199-200 (indices pre-drawn with the pair; they are "
                                           "inside `end_to_end`), the feature network, hypothesis selection and ICP (see `end_to_end`)"},
-        "library_source_hash": lib_hash, "counters_match_library_by_file": counters_match,
+        "library_source_hash": lib_hash, "counters_match_library_by_file": counters_match, "dump_outputs": dumped,
         "roofline": dominant,
         "rooflines": {"ume_moments_kernel": roof_mom, roof_dist["kernel"]: roof_dist},
         "hypothesis_quality": {"hypotheses": int(c[0]), "within_1.5deg_0.6m": round(c[1] / max(c[0], 1), 4),

@@ -968,12 +968,14 @@ def test_bench_two_ranks_equal_one_rank_over_the_same_pairs(gpu):
     assert abs(e1["mRRE_deg"] - e2["mRRE_deg"]) < 1e-4 and abs(e1["mRTE_m"] - e2["mRTE_m"]) < 1e-4
 
 
-def test_bench_eight_ranks_equal_one_rank_over_the_same_pairs(gpu):
-    """First contact with an 8-GPU node, rehearsed on one GPU: `torch.distributed.run --nproc-per-node 8 bench.py --gpus 8`, every
-    rank on device 0 (--force-device 0), collectives on gloo.  K1 shape, one step of one pair per rank: the eight ranks cover the
-    global pairs 0..7 of the named path and 0..7 of the end-to-end leg, and the summed integer counts must EQUAL a 1-rank run over
-    the same eight pairs.  Every rank is pinned to its own share of the host (hostpin) before numpy / torch exist.
-    The eight ranks are started the way the command is TYPED -- `python bench.py --gpus 8 ...`, no launcher: bench.py re-executes itself
+def test_bench_four_ranks_equal_one_rank_over_the_same_pairs(gpu):
+    """First contact with a multi-GPU node, rehearsed on one GPU: `torch.distributed.run --nproc-per-node 4 bench.py --gpus 4`, every
+    rank on device 0 (--force-device 0), collectives on gloo.  K1 shape, one step of one pair per rank: the four ranks cover the
+    global pairs 0..3 of the named path and 0..3 of the end-to-end leg, and the summed integer counts must EQUAL a 1-rank run over
+    the same four pairs.  Every rank is pinned to its own share of the host (hostpin) before numpy / torch exist.
+    Four ranks, not eight: with this test's own process they are five processes holding the one device, and a shared GPU node
+    admits at most six at once (the 8-rank sharding and host pinning are covered on the CPU: tests/test_host_logic.py).
+    The ranks are started the way the command is TYPED -- `python bench.py --gpus 4 ...`, no launcher: bench.py re-executes itself
     under torch.distributed.run (umeregrobust_amd/benchline.py); an inconsistent launch (WORLD_SIZE set to something else) still ends
     at once with a message (no rendezvous, no hang)."""
     import json
@@ -984,25 +986,60 @@ def test_bench_eight_ranks_equal_one_rank_over_the_same_pairs(gpu):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
     common = ["--config", "K1", "--warmup", "1", "--steps", "1", "--no-cpu-baseline", "--e2e-hard-pairs", "0", "--e2e-side-by-side", "0",
               "--pool", "8"]
-    bad = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "8"] + common, capture_output=True, text=True,
+    bad = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "4"] + common, capture_output=True, text=True,
                          timeout=300, env=dict(env, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"), cwd=repo)
-    assert bad.returncode != 0 and "--gpus 8 but WORLD_SIZE=2" in bad.stderr and "torch.distributed.run" in bad.stderr
-    env8 = {k: v for k, v in env.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
-    l8, j8, r8 = _run_bench([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "8", "--dist-backend", "gloo",
-                             "--force-device", "0", "--pairs-per-step", "1", "--e2e-pairs", "1"] + common, "eight", env8, repo, 1500)
-    assert "--nproc-per-node=8" in r8.stderr and l8["config"]["world"]["launched_by"].startswith("bench.py itself")
-    assert l8["n_gpus"] == 8 and l8["config"]["world"]["ranks"] == 8 and l8["config"]["world"]["backend"] == "gloo"
-    assert j8["n_gpus"] == 8 and j8["world"]["ranks"] == 8 and j8["world"]["backend"] == "gloo" and j8["scaling"] == "weak"
-    assert 1 <= j8["world"]["host_threads_per_rank"] <= 8 and j8["world"]["host_cpus_rank0"]
-    assert j8["config"]["sharding"].startswith("pairs[rank::8]")
-    _, j1, _ = _run_bench([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--pairs-per-step", "8", "--e2e-pairs", "8"] + common,
-                          "one8", env, repo, 900)
-    assert j1["hypothesis_quality"]["counts"] == j8["hypothesis_quality"]["counts"]      # 8 ranks x 1 pair == 1 rank x 8 pairs
-    e1, e8 = j1["end_to_end"], j8["end_to_end"]
-    assert e1["pairs"] == e8["pairs"] == 8
+    assert bad.returncode != 0 and "--gpus 4 but WORLD_SIZE=2" in bad.stderr and "torch.distributed.run" in bad.stderr
+    env4 = {k: v for k, v in env.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
+    l4, j4, r4 = _run_bench([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "4", "--dist-backend", "gloo",
+                             "--force-device", "0", "--pairs-per-step", "1", "--e2e-pairs", "1"] + common, "four", env4, repo, 1500)
+    assert "--nproc-per-node=4" in r4.stderr and l4["config"]["world"]["launched_by"].startswith("bench.py itself")
+    assert l4["n_gpus"] == 4 and l4["config"]["world"]["ranks"] == 4 and l4["config"]["world"]["backend"] == "gloo"
+    assert j4["n_gpus"] == 4 and j4["world"]["ranks"] == 4 and j4["world"]["backend"] == "gloo" and j4["scaling"] == "weak"
+    assert 1 <= j4["world"]["host_threads_per_rank"] <= 8 and j4["world"]["host_cpus_rank0"]
+    assert j4["config"]["sharding"].startswith("pairs[rank::4]")
+    _, j1, _ = _run_bench([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--pairs-per-step", "4", "--e2e-pairs", "4"] + common,
+                          "one4", env, repo, 900)
+    assert j1["hypothesis_quality"]["counts"] == j4["hypothesis_quality"]["counts"]      # 4 ranks x 1 pair == 1 rank x 4 pairs
+    e1, e4 = j1["end_to_end"], j4["end_to_end"]
+    assert e1["pairs"] == e4["pairs"] == 4
     for key in ("rr_1.5deg_0.6m", "rr_1.5deg_0.3m", "rr_1deg_0.1m"):
-        assert e1[key] == e8[key] and e1["selected_before_icp"][key] == e8["selected_before_icp"][key]
-    assert abs(e1["mRRE_deg"] - e8["mRRE_deg"]) < 1e-4 and abs(e1["mRTE_m"] - e8["mRTE_m"]) < 1e-4
+        assert e1[key] == e4[key] and e1["selected_before_icp"][key] == e4["selected_before_icp"][key]
+    assert abs(e1["mRRE_deg"] - e4["mRRE_deg"]) < 1e-4 and abs(e1["mRTE_m"] - e4["mRTE_m"]) < 1e-4
+
+
+def test_bench_dump_outputs_are_what_the_timed_path_returned(gpu, tmp_path):
+    """bench.py --dump-outputs: the files hold what the timed path returned for the pairs of its LAST step -- the same matches, draws,
+    SE(3) hypotheses and UME rows as register_pair on the same pool pair with the same RNG (pair g = pool[g % pool], RandomState(1234 + g)).
+    With 1 warm-up step and 3 timed steps of 3 pairs the last step is pairs 9..11; every step here is a roofline sample, so the dump
+    covers both the layered launches (pairs run alone / timed in situ) and the graph replay."""
+    import sys
+    from types import SimpleNamespace
+
+    from umeregrobust_amd import evaluate
+    from umeregrobust_amd.synth import CONFIGS, synth_pair
+    from umeregrobust_amd.utils.general_utils import benchmark_config_path, update_namespace_from_yaml
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    d = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--config", "K1", "--steps", "3", "--warmup", "1", "--pairs-per-step", "3",
+           "--pool", "4", "--no-cpu-baseline", "--no-e2e", "--resident-steps", "0", "--plan-check-pairs", "0", "--dump-outputs", str(d)]
+    line, full, _ = _run_bench(cmd, "dump", dict(os.environ), repo, 600)
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and full["dump_outputs"]["pairs_written"] == 3
+    dump = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    assert all(v.dtype in (np.float32, np.float64) for v in dump.values())
+    assert np.array_equal(dump["pair_index"], [9, 10, 11])
+    cfg = CONFIGS["K1"]
+    args = update_namespace_from_yaml(SimpleNamespace(), benchmark_config_path("kitti_test"))
+    args.ume_n_samples, args.filter_by_ume_dist_cond = cfg["M"], cfg["filter_by_ume_dist_cond"]
+    rows = dump["ume_rows"].astype(np.int64)
+    for j, g in enumerate(dump["pair_index"].astype(int)):
+        p = synth_pair(seed=g % 4, N=cfg["N"], n_kp=cfg["n_kp"], kind="test", voxel=cfg["voxel"])
+        t = lambda a: T_(a, gpu)[None]     # noqa: E731
+        r = evaluate.register_pair(t(p.src_pts), t(p.tgt_pts), t(p.src_feat), t(p.tgt_feat), args, rng=np.random.RandomState(1234 + g),
+                                   src_inds=p.src_inds, tgt_inds=p.tgt_inds)
+        assert np.array_equal(dump["match"][j], N_(r.match[0])) and np.array_equal(dump["cond"][j], np.asarray(r.cond))
+        assert np.abs(dump["rtume_tform"][j] - N_(r.rtume_tform[0])).max() <= 1e-6
+        assert np.abs(dump["ume_src"][j] - N_(r.ume_src[0])[rows]).max() <= 1e-6 and np.abs(dump["ume_tgt"][j] - N_(r.ume_tgt[0])[rows]).max() <= 1e-6
+        assert np.abs(dump["prob"][j] - N_(r.prob)).max() <= 1e-7 and np.abs(dump["match_d"][j] - N_(r.match_d[0])).max() <= 1e-6
 
 
 @pytest.mark.parametrize("case", ["kitti", "lattice_ties", "sparse_far", "tiny"])

@@ -387,6 +387,37 @@ def test_valu_issue_floor_prices_every_instruction_once():
         assert 0.3 * dur_s < floor_s < dur_s and cls["packed_f32"][0] > 0
 
 
+def test_bench_dump_outputs_fit_their_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: one float32 / float64 file per array, stacked over the last step's pairs; a step larger than the budget
+    is written as a fixed seeded sample of its pairs (the same sample every run, named by pair_index.npy); --steps < 1 is refused"""
+    import bench
+
+    def pair(g):          # one KT-shaped pair's outputs, tagged with its index
+        return {"rtume_tform": np.full((2500, 4, 4), g, np.float32), "match": np.full(10000, g, np.float64), "match_d": np.zeros(10000, np.float32),
+                "ume_src": np.zeros((256, 32, 4), np.float32), "ume_tgt": np.zeros((256, 32, 4), np.float32),
+                "prob": np.zeros(10000, np.float32), "cond": np.arange(2500, dtype=np.float64)}
+    rows = np.arange(0, 10000, 40)
+    size = lambda d: sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d))     # noqa: E731
+    r = bench.write_outputs(str(tmp_path / "a"), [pair(g) for g in range(64)], rows, list(range(64)))
+    assert r["pairs_written"] == 64 and size(tmp_path / "a") == r["bytes"] <= bench.DUMP_LIMIT_BYTES
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(n + ".npy" for n in list(pair(0)) + ["pair_index", "ume_rows"])
+    assert np.load(tmp_path / "a" / "rtume_tform.npy").shape == (64, 2500, 4, 4) and np.load(tmp_path / "a" / "match.npy").dtype == np.float64
+    picks = []
+    for tag in ("b", "c"):
+        r = bench.write_outputs(str(tmp_path / tag), [pair(g) for g in range(256)], rows, [1000 + g for g in range(256)])
+        assert 64 < r["pairs_written"] < 256 and size(tmp_path / tag) == r["bytes"] <= bench.DUMP_LIMIT_BYTES
+        idx = np.load(tmp_path / tag / "pair_index.npy")
+        assert np.all(np.diff(idx) > 0) and np.array_equal(np.load(tmp_path / tag / "match.npy")[:, 0], idx - 1000)
+        picks.append(idx)
+    assert np.array_equal(*picks)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.steps == 7 and a.dump_outputs == "d"
+
+
 def test_ragged_synthetic_pairs_contract():
     """synth_pair / synth_pair_hard with n_src != n_tgt (what the reference's collate produces: datasets/kitti/kitti_dataset.py:568-569
     dilutes the two clouds independently; evaluate.py:195-204 draws min(10000, N_src, N_tgt) keypoints from each): sizes, keypoint rule,
