@@ -44,7 +44,7 @@ def lib():
         build()
         _lib = ctypes.CDLL(_SO)
         for name in ("orc_ball_query_f32", "orc_ball_query_fma_f32", "orc_ume_moments_f32", "orc_orthobasis_f64",
-                     "orc_ume_cdist_f64", "orc_knn_points_f32", "orc_pc_corr_cost_f32"):
+                     "orc_ume_cdist_f64", "orc_ume_match_f64", "orc_knn_points_f32", "orc_pc_corr_cost_f32"):
             getattr(_lib, name).restype = ctypes.c_int
     return _lib
 
@@ -210,6 +210,28 @@ def ume_cdist_f64(ume1, ume2):
     return D
 
 
+UmeMatch64 = namedtuple("UmeMatch64", "argmin d2min d2sec d_at")
+
+
+def ume_match_f64(ume1, ume2, cols=None):
+    """Row reduction of ume_cdist_f64 without the [n1,n2] matrix (orc_ume_match_f64): per row the fp64 arg-min (first index of
+    the minimum), the smallest and second-smallest D^2 (an exact tie makes them equal) and D at `cols[i]` (the column a matcher
+    chose; None -> d_at is None).  The distances are those of ume_cdist_f64 bit for bit: D = sqrt(D^2).
+    ume1 [n1,32,4], ume2 [n2,32,4] -> UmeMatch64(argmin i64 [n1], d2min f64 [n1], d2sec f64 [n1], d_at f64 [n1] | None)."""
+    ume1 = _f32(ume1); ume2 = _f32(ume2)
+    n1, n2, d = ume1.shape[0], ume2.shape[0], ume1.shape[1]
+    am = np.empty((n1,), np.int64)
+    b1 = np.empty((n1,), np.float64)
+    b2 = np.empty((n1,), np.float64)
+    c = None if cols is None else np.ascontiguousarray(cols, dtype=np.int64).reshape(-1)
+    assert c is None or c.shape[0] == n1
+    d_at = None if c is None else np.empty((n1,), np.float64)
+    rc = lib().orc_ume_match_f64(_p(ume1), _p(ume2), ctypes.c_int64(n1), ctypes.c_int64(n2), ctypes.c_int(d), _p(c), _p(am),
+                                 _p(b1), _p(b2), _p(d_at))
+    assert rc == 0, rc
+    return UmeMatch64(am, b1, b2, d_at)
+
+
 def orthobasis_f64(ume):
     ume = _f32(ume)
     n, d = ume.shape[0], ume.shape[1]
@@ -271,6 +293,62 @@ def batch_estimate_transform_ume_old(G, H, with_dist=True):
         G_GT = G_orth @ np.swapaxes(G_orth, 1, 2)                # :342
         D = (f1(0.707) * np.linalg.norm(H_HT - G_GT, ord="fro", axis=(1, 2))).astype(np.float32)  # :344
     return T.astype(np.float32), D
+
+
+RtumeCond = namedtuple("RtumeCond", "s s3_s1 cos_mg_mh kappa_R kappa_t")
+
+
+def batch_estimate_transform_ume_f64(G, H, g_index=None, h_index=None):
+    """The statements of batch_estimate_transform_ume_old (utils/loc_utils.py:292-350, translation part; no D) in fp64 on the
+    fp32 inputs, with the optional row gathers of the HIP solve: hypothesis k pairs G[g_index[k]] with H[h_index[k]].
+    -> (T f64 [n,4,4], RtumeCond) where the conditioning figures of each hypothesis are
+      s          singular values of the 3x3 cross-moment left^T right (:325-326), descending [n,3];
+      s3_s1      s[2] / s[0];
+      cos_mg_mh  |mg.mh| / (|mg| |mh|), the denominator of wrc (:313, :320);
+      kappa_R    first-order amplification of a relative rounding error u into R: |dR| <~ u * kappa_R.  Two terms: the
+                 cross-moment's own rounding, |terms of A| / (s2 + det * s3) (polar factor sensitivity), and a solve through
+                 the normal matrix A^T A, s1^2 / (s2 (s2 + det * s3));
+      kappa_t    the same for t (in the units of t): the rounding of wrc (a quotient over mg.mh), of wlc, and wlc's share of dR.
+    Two correct fp64 evaluations of these statements differ by a small multiple of 2^-53 * kappa."""
+    G = np.asarray(G, np.float32).astype(np.float64)
+    H = np.asarray(H, np.float32).astype(np.float64)
+    if g_index is not None:
+        G = G[np.asarray(g_index, np.int64)]
+    if h_index is not None:
+        H = H[np.asarray(h_index, np.int64)]
+    assert G.shape == H.shape and G.shape[1:] == (32, 4)
+    n = G.shape[0]
+    mg, mh, g, h = G[:, :, :1], H[:, :, :1], G[:, :, 1:], H[:, :, 1:]        # :304-309
+    mg2 = (mg ** 2).sum(1, keepdims=True) + 1e-16                             # :312
+    mg_mh = (mg * mh).sum(1, keepdims=True)                                   # :313
+    wlc = (g * mg).sum(1, keepdims=True) / (mg2 + 1e-16)                      # :314, :319
+    wrc = (h * mg).sum(1, keepdims=True) / (mg_mh + 1e-16)                    # :315, :320
+    left, right = g - wlc * mg, h - wrc * mh                                  # :322-323
+    M = np.swapaxes(right, 1, 2) @ left                                       # :325
+    U, S, Vh = np.linalg.svd(np.swapaxes(M, 1, 2))                            # :326
+    det = np.sign(np.linalg.det(U @ Vh))
+    Q = np.tile(np.eye(3), (n, 1, 1))
+    Q[:, 2, 2] = det                                                          # :327-328
+    R = U @ Q @ Vh                                                            # :329
+    b2 = wrc - wlc @ R                                                        # :332
+    T = np.tile(np.eye(4), (n, 1, 1))
+    T[:, :3, :3] = np.swapaxes(R, 1, 2)                                       # :347-348
+    T[:, :3, 3] = b2[:, 0]                                                    # :349
+    # conditioning
+    nrm = lambda x: np.sqrt((x * x).sum(axis=(1, 2)))                         # noqa: E731
+    n_mg, n_mh, n_g, n_h = nrm(mg), nrm(mh), nrm(g), nrm(h)
+    n_wlc, n_wrc = nrm(wlc), nrm(wrc)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cos = np.abs(mg_mh[:, 0, 0]) / (n_mg * n_mh)
+        gap = S[:, 1] + det * S[:, 2]
+        a_terms = (n_g + n_wlc * n_mg) * (n_h + n_wrc * n_mh)
+        kappa_R = a_terms / gap + S[:, 0] ** 2 / (S[:, 1] * gap)
+        q_wrc = (n_h * n_mg + n_wrc * n_mg * n_mh) / np.abs(mg_mh[:, 0, 0])
+        q_wlc = (n_g * n_mg + n_wlc * n_mg ** 2) / mg2[:, 0, 0]
+        kappa_t = q_wrc + q_wlc + n_wlc * (1.0 + kappa_R)
+        s3_s1 = S[:, 2] / S[:, 0]
+    bad = lambda x: np.where(np.isfinite(x), x, np.inf)                       # noqa: E731
+    return T, RtumeCond(S, np.nan_to_num(s3_s1, nan=0.0), np.nan_to_num(cos, nan=0.0), bad(kappa_R), bad(kappa_t))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -444,8 +522,9 @@ def umeyama_no_scaling(p, q):
     return R, mq - R @ mp
 
 
-def icp_point_to_point(src, tgt, T_init, max_dist=0.2, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6):
-    """-> (T float64 [4,4], fitness, inlier_rmse, iterations)."""
+def icp_point_to_point(src, tgt, T_init, max_dist=0.2, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6, steps=None):
+    """-> (T float64 [4,4], fitness, inlier_rmse, iterations).
+    steps: optional list; receives (max |R_upd - I|, max |t_upd|) of every update applied, in order."""
     T = np.asarray(T_init, np.float64).copy()
     tgt64 = np.asarray(tgt, np.float32).astype(np.float64)
     idx, fit, rmse, q = icp_evaluate(src, tgt, T, max_dist)
@@ -456,6 +535,8 @@ def icp_point_to_point(src, tgt, T_init, max_dist=0.2, max_iteration=30, relativ
         if ok.any():
             R, t = umeyama_no_scaling(q[ok], tgt64[idx[ok]])
             upd[:3, :3], upd[:3, 3] = R, t
+        if steps is not None:
+            steps.append((float(np.abs(upd[:3, :3] - np.eye(3)).max()), float(np.abs(upd[:3, 3]).max())))
         T = upd @ T
         it += 1
         pf, pr = fit, rmse

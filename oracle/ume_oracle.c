@@ -291,6 +291,56 @@ ORC_API int orc_ume_cdist_f64(const float* ume1, const float* ume2, int64_t n1, 
 }
 
 /* --------------------------------------------------------------------------
+ * a3+a4 without the matrix: the fp64 truth of orc_ume_cdist_f64 reduced per row,
+ * so that a 10 000 x 10 000 match can be checked in O(n1 + n2) memory.
+ * Per row i, over all columns j of D2[i,j] = max(4 - |Q1_i^T Q2_j|_F^2, 0) (the
+ * same statements, in the same order, as orc_ume_cdist_f64 -- D = sqrt(D2) there):
+ *   argmin[i]  first j of the row minimum (= np.argmin of that row),
+ *   d2min[i]   the smallest D2, d2sec[i] the second smallest (a duplicate of the
+ *              minimum counts: an exact tie gives d2sec == d2min; +inf if n2 == 1),
+ *   d_at[i]    D[i, cols[i]] (optional; cols NULL -> d_at untouched).
+ * -------------------------------------------------------------------------- */
+ORC_API int orc_ume_match_f64(const float* ume1, const float* ume2, int64_t n1, int64_t n2, int d,
+                              const int64_t* cols, int64_t* argmin, double* d2min, double* d2sec, double* d_at)
+{
+    if (d > 64 || n1 < 0 || n2 < 1) return -1;
+    if (cols)
+        for (int64_t i = 0; i < n1; ++i)
+            if (cols[i] < 0 || cols[i] >= n2) return -3;
+    double* Q1 = (double*)malloc(sizeof(double) * (size_t)(n1 * d * 4 + 1));
+    double* Q2 = (double*)malloc(sizeof(double) * (size_t)(n2 * d * 4));
+    if (!Q1 || !Q2) { free(Q1); free(Q2); return -2; }
+    orc_orthobasis_f64(ume1, n1, d, Q1);
+    orc_orthobasis_f64(ume2, n2, d, Q2);
+#pragma omp parallel for schedule(dynamic, 8)
+    for (int64_t i = 0; i < n1; ++i) {
+        const double* a = Q1 + i * d * 4;
+        double b1 = INFINITY, b2 = INFINITY;
+        int64_t bj = 0;
+        for (int64_t j = 0; j < n2; ++j) {
+            const double* b = Q2 + j * d * 4;
+            double s = 0.0;
+            for (int p = 0; p < 4; ++p)
+                for (int q = 0; q < 4; ++q) {
+                    double c = 0.0;
+                    for (int r = 0; r < d; ++r) c += a[r * 4 + p] * b[r * 4 + q];
+                    s += c * c;
+                }
+            double v = 4.0 - s;
+            v = v > 0.0 ? v : 0.0;
+            if (v < b1) { b2 = b1; b1 = v; bj = j; }
+            else if (v < b2) b2 = v;
+            if (cols && j == cols[i] && d_at) d_at[i] = sqrt(v);
+        }
+        argmin[i] = bj;
+        d2min[i] = b1;
+        d2sec[i] = b2;
+    }
+    free(Q1); free(Q2);
+    return 0;
+}
+
+/* --------------------------------------------------------------------------
  * f1 support: pytorch3d.ops.knn_points (K nearest, squared distances, ascending;
  * ties -> lower index first -- upstream tie order is unspecified, parity unpinned)
  * as called at utils/loc_utils.py:580,623 and evaluate.py:272,274.

@@ -311,3 +311,63 @@ def test_contracted_ball_query_variant_against_numpy():
             assert np.array_equal(got.idx[0, i][:want.size], want) and (got.idx[0, i][want.size:] == -1).all()
         hit = got.idx[0] >= 0
         assert np.array_equal(got.dists[0][hit], np.take_along_axis(co if fma else un, np.where(hit, got.idx[0], 0), 1)[hit])
+
+
+def test_ume_match_f64_equals_the_matrix_reduced():
+    """oracle.ume_match_f64 (per-row arg-min / two smallest D^2 / D at a given column, no n1 x n2 matrix) against
+    ume_cdist_f64(...).argmin / sort on small inputs, exact ties included (duplicated targets, a zero UME, one target)."""
+    rng = np.random.RandomState(4)
+    u1 = rng.standard_normal((57, 32, 4)).astype(np.float32)
+    u2 = rng.standard_normal((90, 32, 4)).astype(np.float32)
+    u2[:20] = u1[:20] @ (np.eye(4) + 0.1 * rng.standard_normal((4, 4))).astype(np.float32)
+    u2[40:43] = u2[3]                      # exact ties: row 3's best target exists four times -> the lowest index, d2sec == d2min
+    u2[60] = u2[61] = u2[62] = u1[30]      # and three copies of row 30 itself (D = 0)
+    u1[50] = 0.0                           # zero UME: Q = I[:, :4]
+    for a, b in ((u1, u2), (u1[:7], u2[:1]), (u1[:1], u2)):
+        D = orc.ume_cdist_f64(a, b)
+        cols = rng.randint(0, b.shape[0], a.shape[0])
+        r = orc.ume_match_f64(a, b, cols=cols)
+        assert np.array_equal(r.argmin, D.argmin(axis=1))
+        s = np.sort(D ** 2, axis=1)
+        assert np.array_equal(np.sqrt(r.d2min), D.min(axis=1))                 # the same statements, bit for bit
+        assert np.allclose(r.d2min, s[:, 0], rtol=0, atol=1e-15)
+        if b.shape[0] > 1:
+            assert np.allclose(r.d2sec, s[:, 1], rtol=0, atol=1e-15)
+        else:
+            assert np.isinf(r.d2sec).all()
+        assert np.array_equal(r.d_at, D[np.arange(a.shape[0]), cols])
+        assert orc.ume_match_f64(a, b).d_at is None
+    r = orc.ume_match_f64(u1, u2)
+    assert r.argmin[3] == 3 and r.d2sec[3] == r.d2min[3]                         # (row 3 -> target 3, tied with 40..42)
+    assert r.argmin[30] == 60 and r.d2min[30] == 0.0 and r.d2sec[30] == 0.0
+
+
+def test_rtume_f64_against_its_fp32_sibling_and_its_conditioning_figures():
+    """oracle.batch_estimate_transform_ume_f64 (utils/loc_utils.py:292-350 in fp64, with the row gathers) on golden G4:
+    on the well-posed rows (0..31 physical twins, 62..69 reflections) it agrees with the fp32 restatement
+    (batch_estimate_transform_ume_old) to the bar that pins that one to the reference; the conditioning figures flag the
+    deliberately mismatched rows 32..61, and bound the fp32 sibling's deviation on every row (kappa * 2^-24)."""
+    g = load_golden("g4_rtume.npz")
+    T64, c = orc.batch_estimate_transform_ume_f64(g["G"], g["H"])
+    T32, _ = orc.batch_estimate_transform_ume_old(g["G"], g["H"], with_dist=False)
+    dR = np.abs(T32[:, :3, :3] - T64[:, :3, :3]).max(axis=(1, 2))
+    dt = np.abs(T32[:, :3, 3] - T64[:, :3, 3]).max(axis=1)
+    well = np.r_[0:32, 62:70]
+    assert dR[well].max() < 2e-6 and dt[well].max() < 1e-4
+    assert np.abs(T64[:32] - g["gt_tform"]).max() < 2e-4
+    assert np.allclose(np.linalg.det(T64[:, :3, :3]), 1.0, atol=1e-12) and np.all(T64[:, 3] == [0, 0, 0, 1])
+    # figures: a true match has mg ~ mh (cosine 1); the mismatched rows do not, and their cross-moments are worse conditioned
+    assert c.cos_mg_mh[well].min() > 0.999 and c.cos_mg_mh[32:62].max() < 0.5
+    assert np.median(c.kappa_R[32:62]) > np.median(c.kappa_R[well]) and c.kappa_R.argmax() in range(32, 62)
+    assert c.s.shape == (70, 3) and np.all(np.diff(c.s, axis=1) <= 0) and np.allclose(c.s3_s1, c.s[:, 2] / c.s[:, 0])
+    u32 = 2.0 ** -24
+    assert np.all(dR <= u32 * c.kappa_R) and np.all(dt <= u32 * c.kappa_t)
+    # gathers: hypothesis k = (G[gi[k]], H[hi[k]])
+    gi, hi = np.array([5, 0, 69, 33]), np.array([5, 0, 69, 34])
+    Tg, cg = orc.batch_estimate_transform_ume_f64(g["G"], g["H"], gi, hi)
+    Tx, _ = orc.batch_estimate_transform_ume_f64(g["G"][gi], g["H"][hi])
+    assert np.array_equal(Tg, Tx) and np.array_equal(Tg[:3], T64[[5, 0, 69]]) and cg.kappa_R.shape == (4,)
+    # a zero cross-moment (rank 0) is degenerate in every figure and still gives a finite transform
+    Z = np.zeros((1, 32, 4), np.float32)
+    Tz, cz = orc.batch_estimate_transform_ume_f64(Z, Z)
+    assert np.isfinite(Tz).all() and np.isinf(cz.kappa_R).all() and cz.cos_mg_mh[0] == 0.0

@@ -738,8 +738,10 @@ def evaluate_pairs(pairs, args, rng=np.random, refine=True, verbose=False, overl
     where the last four are the numbers the reference prints (:304-309).  overlap (default): consecutive pairs overlap on
     two HIP streams (same results, same RNG consumption; see the loop).  Datasets and the feature network are the
     caller's business (out of scope); everything between them and the printed metrics is here.
-    collect: a list that receives, per pair, dict(rtume_tform [M,4,4] (every hypothesis, a copy), cond, match) -- the intermediate
-    results a stage-by-stage comparison against a CPU checker needs (tests); costs one device copy per pair."""
+    collect: a list that receives, per pair, the intermediate results a stage-by-stage comparison against a CPU checker needs
+    (tests): dict(rtume_tform [M,4,4] (every hypothesis), cond (the drawn rows, host), match [1,n_kp], match_d [1,n_kp],
+    prob [n_kp] | None, ume_src / ume_tgt [1,n_kp,32,4], T_sel [4,4] (the selected hypothesis)).  The tensors are device
+    CLONES, made on the pair's stream only when `collect` is given; without it nothing is copied."""
     R_sel, t_sel, raw = [], [], []
     # Two pairs overlap on two HIP streams: while the correlation scores of pair i are computed (two thirds of a pair's GPU
     # time, and nothing on the host needs them before the read-back below), pair i + 1 goes through its keypoint draws,
@@ -793,8 +795,9 @@ def evaluate_pairs(pairs, args, rng=np.random, refine=True, verbose=False, overl
                                                           pair["tgt_feat"], out.rtume_tform, pair["gt_tform"], args, rng=rng,
                                                           prepared=getattr(out, "side", None), return_tform=True)       # :258-296
             if collect is not None:
-                collect.append(dict(rtume_tform=out.rtume_tform[0].clone(), cond=out.cond,
-                                    match=out.match.clone() if isinstance(out.match, torch.Tensor) else out.match))
+                cl = lambda t_: t_.clone() if isinstance(t_, torch.Tensor) else t_                                      # noqa: E731
+                collect.append(dict(rtume_tform=out.rtume_tform[0].clone(), cond=out.cond, match=cl(out.match), match_d=cl(out.match_d),
+                                    prob=cl(out.prob), ume_src=cl(out.ume_src), ume_tgt=cl(out.ume_tgt), T_sel=T_dev[0].clone()))
             job = None
             if refine and st is not None and src_raw.is_cuda and src_raw.dtype == torch.float32 and tgt_raw.dtype == torch.float32:
                 job = ops.IcpJob(src_raw, tgt_raw, T_dev[0].contiguous(), max_corr, max_it)                              # :63-96
