@@ -44,7 +44,8 @@ def lib():
         build()
         _lib = ctypes.CDLL(_SO)
         for name in ("orc_ball_query_f32", "orc_ball_query_fma_f32", "orc_ume_moments_f32", "orc_orthobasis_f64",
-                     "orc_ume_cdist_f64", "orc_ume_match_f64", "orc_knn_points_f32", "orc_pc_corr_cost_f32"):
+                     "orc_ume_cdist_f64", "orc_ume_match_f64", "orc_knn_points_f32", "orc_pc_corr_cost_f32",
+                     "orc_corr_images_f32", "orc_corr_judge_f32"):
             getattr(_lib, name).restype = ctypes.c_int
     return _lib
 
@@ -455,6 +456,39 @@ def pc_corr_cost_c(T, source_points, target_points, k, source_vals, target_vals,
                                     ctypes.c_float(sigma), _p(scores))
     assert rc == 0
     return scores
+
+
+CORR_FORM_REF, CORR_FORM_FMA = 0, 1       # the image q of a source point: orc_pc_corr_cost_f32's form / the HIP routes' form
+
+
+def corr_images(T, source_points, form=CORR_FORM_FMA):
+    """The fp32 images q [M,Ns,3] of every source point under every T [M,4,4] (orc_corr_images_f32): CORR_FORM_REF
+    q = ((T0 x + T1 y) + T2 z) + T3, CORR_FORM_FMA q = fmaf(T2, z, fmaf(T1, y, T0 x)) + T3."""
+    T = _f32(T); sp = _f32(source_points)
+    q = np.empty((T.shape[0], sp.shape[0], 3), np.float32)
+    rc = lib().orc_corr_images_f32(_p(T), ctypes.c_int64(T.shape[0]), _p(sp), ctypes.c_int64(sp.shape[0]), ctypes.c_int(form), _p(q))
+    assert rc == 0, rc
+    return q
+
+
+CorrJudge = namedtuple("CorrJudge", "idx d2 label score absum")
+
+
+def corr_judge(T, source_points, target_points, k, source_vals, target_vals, sigma, form=CORR_FORM_FMA, neighbours=False):
+    """pc_corr_cost judged per neighbour, for the hypotheses T [M,4,4] (orc_corr_judge_f32; brute force, Ns x Nt per hypothesis):
+    -> CorrJudge(idx [M,Ns,k] int64 | None, d2 [M,Ns,k] f32 | None (neighbours=True), label [M] f64 (sum of <vp, vq> over the
+    neighbour sets: exact for small integer features), score [M] f64 (the fp64 score on those sets), absum [M] f64 (sum of
+    w * sum_c |vp_c vq_c|)).  The neighbour sets are the K smallest (fp32 d2, index) of the fp32 image of the chosen form."""
+    T = _f32(T); sp = _f32(source_points); tp = _f32(target_points); vp = _f32(source_vals); vq = _f32(target_vals)
+    M, Ns = T.shape[0], sp.shape[0]
+    idx = np.empty((M, Ns, k), np.int64) if neighbours else None
+    d2 = np.empty((M, Ns, k), np.float32) if neighbours else None
+    label, score, absum = (np.empty(M, np.float64) for _ in range(3))
+    rc = lib().orc_corr_judge_f32(_p(T), ctypes.c_int64(M), _p(sp), ctypes.c_int64(Ns), _p(tp), ctypes.c_int64(tp.shape[0]), _p(vp),
+                                  _p(vq), ctypes.c_int(vp.shape[1]), ctypes.c_int(k), ctypes.c_double(sigma), ctypes.c_int(form),
+                                  _p(idx), _p(d2), _p(label), _p(score), _p(absum))
+    assert rc == 0, rc
+    return CorrJudge(idx, d2, label, score, absum)
 
 
 def feature_corr_hypothesis_test(source_pc, target_pc, source_feat, target_feat, T_kp, sigma=0.05, corr_num_nn=20,

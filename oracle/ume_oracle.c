@@ -372,6 +372,27 @@ ORC_API int orc_knn_points_f32(const float* p1, const float* p2, int64_t n1, int
     return 0;
 }
 
+/* The K smallest (d2, index) of the fp32 squared distances ((dx*dx) + (dy*dy)) + (dz*dz) from q to tp[0..Nt), ascending
+ * (ties -> lower index): the brute-force selection of orc_pc_corr_cost_f32 and orc_corr_judge_f32.  -> how many (min(K, Nt)). */
+static int knn_select_f32(const float* q, const float* tp, int64_t Nt, int K, float* bd, int64_t* bi)
+{
+    int cnt = 0;
+    for (int64_t j = 0; j < Nt; ++j) {
+        const float dx = q[0] - tp[3 * j];
+        const float dy = q[1] - tp[3 * j + 1];
+        const float dz = q[2] - tp[3 * j + 2];
+        float d2 = dx * dx;
+        d2 = d2 + dy * dy;
+        d2 = d2 + dz * dz;
+        if (cnt == K && !(d2 < bd[K - 1])) continue;
+        int p = cnt < K ? cnt : K - 1;
+        while (p > 0 && bd[p - 1] > d2) { bd[p] = bd[p - 1]; bi[p] = bi[p - 1]; --p; }
+        bd[p] = d2; bi[p] = j;
+        if (cnt < K) ++cnt;
+    }
+    return cnt;
+}
+
 /* --------------------------------------------------------------------------
  * f1: pc_corr_cost_pytorch3d -> pc_corr_pytorch3d -> pc_corr (reference utils/loc_utils.py:592-637, P=None,
  * use_norm=False) for M hypotheses in one call -- the same arithmetic as oracle.py's numpy restatement
@@ -404,20 +425,8 @@ ORC_API int orc_pc_corr_cost_f32(const float* T, int64_t M, const float* sp, int
             v = v + Th[4 * a + 2] * z;
             q[a] = v + Th[4 * a + 3];
         }
-        float bd[256]; int64_t bi[256]; int cnt = 0;
-        for (int64_t j = 0; j < Nt; ++j) {
-            const float dx = q[0] - tp[3 * j];
-            const float dy = q[1] - tp[3 * j + 1];
-            const float dz = q[2] - tp[3 * j + 2];
-            float d2 = dx * dx;
-            d2 = d2 + dy * dy;
-            d2 = d2 + dz * dz;
-            if (cnt == K && !(d2 < bd[K - 1])) continue;
-            int p = cnt < K ? cnt : K - 1;
-            while (p > 0 && bd[p - 1] > d2) { bd[p] = bd[p - 1]; bi[p] = bi[p - 1]; --p; }
-            bd[p] = d2; bi[p] = j;
-            if (cnt < K) ++cnt;
-        }
+        float bd[256]; int64_t bi[256];
+        const int cnt = knn_select_f32(q, tp, Nt, K, bd, bi);
         double s = 0.0;
         for (int k = 0; k < cnt; ++k) {
             const float dist = sqrtf(bd[k]);
@@ -437,5 +446,95 @@ ORC_API int orc_pc_corr_cost_f32(const float* T, int64_t M, const float* sp, int
         scores[h] = (float)(s / (double)Ns);
     }
     free(per_point);
+    return 0;
+}
+
+/* --------------------------------------------------------------------------
+ * f1, judged per neighbour: the images, neighbour sets and exact sums of pc_corr_cost for a chosen subset of hypotheses.
+ *
+ * form 0  the reference form of orc_pc_corr_cost_f32:  q = ((T0 x + T1 y) + T2 z) + T3, one rounding per operation;
+ * form 1  the form of every HIP route (corr_leftover.hip, corr_lattice.hip, corr_consensus.hip):
+ *             q = fmaf(T2, z, fmaf(T1, y, T0 * x)) + T3          (fmaf: correctly rounded, whatever the target supports)
+ * Then d2 = ((dx*dx) + (dy*dy)) + (dz*dz) in fp32 and the K smallest by (d2, index): ties -> lower index.  Both are defined
+ * fp32 functions, so the neighbour sets are bit-exact.
+ *
+ * orc_corr_images_f32:   q [M,Ns,3] of the chosen form.
+ * orc_corr_judge_f32:    per hypothesis h (brute force, Ns x Nt per hypothesis):
+ *   idx [M,Ns,K] i64, d2 [M,Ns,K] f32 (either may be NULL)  the neighbour sets, ascending by (d2, index);
+ *   label [M] f64   sum over (n,k) of <vp[n], vq[nn]> in fp64: the exact integer when the features are small integers;
+ *   score [M] f64   sum over (n,k) of w * <vp, vq> / Ns, w = 1 / (1 + d2 / sigma^2) from the fp32 d2, everything in fp64;
+ *   absum [M] f64   sum over (n,k) of w * sum_c |vp_c vq_c| (the magnitude that bounds fp32 rounding of the same sum).
+ * T [M,4,4] row-major fp32; sp [Ns,3]; tp [Nt,3]; vp [Ns,d]; vq [Nt,d].  K <= min(Nt, 256).
+ * -------------------------------------------------------------------------- */
+static inline void corr_image(const float* Th, const float* p, int form, float* q)
+{
+    for (int a = 0; a < 3; ++a) {
+        if (form == 1) {
+            q[a] = fmaf(Th[4 * a + 2], p[2], fmaf(Th[4 * a + 1], p[1], Th[4 * a] * p[0])) + Th[4 * a + 3];
+        } else {
+            float v = Th[4 * a] * p[0];
+            v = v + Th[4 * a + 1] * p[1];
+            v = v + Th[4 * a + 2] * p[2];
+            q[a] = v + Th[4 * a + 3];
+        }
+    }
+}
+
+ORC_API int orc_corr_images_f32(const float* T, int64_t M, const float* sp, int64_t Ns, int form, float* q)
+{
+    if (form != 0 && form != 1) return -1;
+#pragma omp parallel for schedule(static)
+    for (int64_t w = 0; w < M * Ns; ++w) corr_image(T + (w / Ns) * 16, sp + 3 * (w % Ns), form, q + 3 * w);
+    return 0;
+}
+
+ORC_API int orc_corr_judge_f32(const float* T, int64_t M, const float* sp, int64_t Ns, const float* tp, int64_t Nt,
+                               const float* vp, const float* vq, int d, int K, double sigma, int form,
+                               int64_t* idx, float* d2out, double* label, double* score, double* absum)
+{
+    if (K > Nt || K > 256 || K < 1 || (form != 0 && form != 1)) return -1;
+    double* acc = (double*)malloc(sizeof(double) * (size_t)(M * Ns) * 3);
+    if (!acc) return -2;
+    const double inv_s2 = 1.0 / (sigma * sigma);
+#pragma omp parallel for schedule(dynamic, 16)
+    for (int64_t w = 0; w < M * Ns; ++w) {
+        const int64_t h = w / Ns, n = w % Ns;
+        float q[3];
+        corr_image(T + h * 16, sp + 3 * n, form, q);
+        float bd[256]; int64_t bi[256];
+        const int cnt = knn_select_f32(q, tp, Nt, K, bd, bi);
+        double lab = 0.0, s = 0.0, a = 0.0;
+        for (int k = 0; k < cnt; ++k) {
+            const float* x = vp + n * d;
+            const float* y = vq + bi[k] * d;
+            double val = 0.0, mag = 0.0;
+            for (int c = 0; c < d; ++c) {
+                const double t = (double)x[c] * (double)y[c];          /* exact: a product of two floats */
+                val += t;
+                mag += fabs(t);
+            }
+            const double wgt = 1.0 / (1.0 + (double)bd[k] * inv_s2);
+            lab += val;
+            s += wgt * val;
+            a += wgt * mag;
+        }
+        for (int k = 0; k < K; ++k) {
+            if (idx) idx[w * K + k] = k < cnt ? bi[k] : -1;
+            if (d2out) d2out[w * K + k] = k < cnt ? bd[k] : NAN;
+        }
+        acc[3 * w] = lab; acc[3 * w + 1] = s; acc[3 * w + 2] = a;
+    }
+    for (int64_t h = 0; h < M; ++h) {
+        double lab = 0.0, s = 0.0, a = 0.0;
+        for (int64_t n = 0; n < Ns; ++n) {
+            lab += acc[3 * (h * Ns + n)];
+            s += acc[3 * (h * Ns + n) + 1];
+            a += acc[3 * (h * Ns + n) + 2];
+        }
+        if (label) label[h] = lab;
+        if (score) score[h] = s / (double)Ns;
+        if (absum) absum[h] = a;
+    }
+    free(acc);
     return 0;
 }

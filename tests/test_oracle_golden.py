@@ -371,3 +371,165 @@ def test_rtume_f64_against_its_fp32_sibling_and_its_conditioning_figures():
     Z = np.zeros((1, 32, 4), np.float32)
     Tz, cz = orc.batch_estimate_transform_ume_f64(Z, Z)
     assert np.isfinite(Tz).all() and np.isinf(cz.kappa_R).all() and cz.cos_mg_mh[0] == 0.0
+
+
+# ---- f1 judged per neighbour (orc_corr_images_f32 / orc_corr_judge_f32) -------------------------------------------------------
+def _round_f32(x):
+    """A Fraction rounded to the nearest fp32 (ties to even), as a Fraction: the exact-rational model of one IEEE fp32 operation."""
+    from fractions import Fraction
+    if x == 0:
+        return Fraction(0)
+    v = float(x)                                      # nearest double (correctly rounded by Fraction.__float__)
+    f = np.float32(v)                                 # may round twice: decide by hand around it
+    cands = [np.nextafter(f, np.float32(-np.inf)), f, np.nextafter(f, np.float32(np.inf))]
+    best = None
+    for c in cands:
+        if not np.isfinite(c):
+            continue
+        e = abs(Fraction(float(c)) - x)
+        if best is None or e < best[0] or (e == best[0] and (int(np.float32(c).view(np.uint32)) & 1) == 0):
+            best = (e, c)
+    return Fraction(float(best[1]))
+
+
+def _fmaf_exact(a, b, c):
+    from fractions import Fraction
+    return _round_f32(Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c)))
+
+
+def _image_exact(T, p, form):
+    from fractions import Fraction
+    F = lambda v: Fraction(float(v))
+    out = []
+    for a in range(3):
+        if form == orc.CORR_FORM_FMA:
+            v = _round_f32(F(T[a, 0]) * F(p[0]))
+            v = _round_f32(F(T[a, 1]) * F(p[1]) + v)
+            v = _round_f32(F(T[a, 2]) * F(p[2]) + v)
+        else:
+            v = _round_f32(F(T[a, 0]) * F(p[0]))
+            v = _round_f32(v + _round_f32(F(T[a, 1]) * F(p[1])))
+            v = _round_f32(v + _round_f32(F(T[a, 2]) * F(p[2])))
+        out.append(np.float32(float(_round_f32(v + F(T[a, 3])))))
+    return np.array(out, np.float32)
+
+
+def test_corr_images_fma_form_is_correctly_rounded():
+    """The FMA form (the HIP routes' q = fmaf(T2, z, fmaf(T1, y, T0 x)) + T3) equals an exact-rational emulation of fmaf on 4 096
+    triples, ~half of them built so that an fp64 emulation (a*b + c in double, then to fp32) rounds twice and misses: a = b = 1 + m 2^-12
+    (m odd) puts a*b exactly on an fp32 midpoint and a tiny c of either sign decides the side."""
+    rng = np.random.RandomState(3)
+    M, Ns = 64, 64
+    T = np.zeros((M, 4, 4), np.float32)
+    sp = np.ones((Ns, 3), np.float32)
+    m = (2 * rng.randint(1, 1 << 10, Ns) + 1).astype(np.float64)
+    half = Ns // 2
+    sp[:half, 1] = (1.0 + m[:half] * 2.0 ** -12).astype(np.float32)                          # b: midpoint family
+    sp[half:, 1] = (rng.standard_normal(Ns - half) * 10.0 ** rng.uniform(-3, 3, Ns - half)).astype(np.float32)
+    for h in range(M):
+        if h < M // 2:
+            T[h, 0, 1] = sp[h % half, 1] * np.float32(2.0 ** rng.randint(-3, 4))                # a: the same family, a power of two apart
+            T[h, 0, 0] = np.float32((-1) ** h * 2.0 ** -rng.randint(40, 60))                  # c: far below the midpoint bit
+        else:
+            T[h, 0, :2] = (rng.standard_normal(2) * 10.0 ** rng.uniform(-3, 3, 2)).astype(np.float32)
+    q = orc.corr_images(T, sp, orc.CORR_FORM_FMA)
+    n_double = 0
+    for h in range(M):
+        for n in range(Ns):
+            a, b, c = T[h, 0, 1], sp[n, 1], T[h, 0, 0]
+            want = np.float32(float(_fmaf_exact(a, b, c)))
+            assert q[h, n, 0] == want, (h, n, a, b, c, q[h, n, 0], want)
+            n_double += int(np.float32(float(a) * float(b) + float(c)) != want)
+    assert n_double >= 100, n_double                   # the fp64 emulation would have failed here
+    # the whole chain, all three rows, random transforms and points, both forms
+    T = rng.standard_normal((24, 4, 4)).astype(np.float32) * np.float32(3)
+    sp = (rng.standard_normal((40, 3)) * 50).astype(np.float32)
+    for form in (orc.CORR_FORM_REF, orc.CORR_FORM_FMA):
+        q = orc.corr_images(T, sp, form)
+        for h in range(T.shape[0]):
+            for n in range(sp.shape[0]):
+                assert np.array_equal(q[h, n], _image_exact(T[h], sp[n], form)), (form, h, n)
+
+
+def _numpy_neighbours(q, tp, K):
+    """K smallest (fp32 d2 = ((dx*dx) + (dy*dy)) + (dz*dz), index), ascending -- numpy, one rounding per operation."""
+    d = q[:, None, :] - tp[None, :, :]
+    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    order = np.lexsort((np.broadcast_to(np.arange(tp.shape[0]), d2.shape), d2), axis=-1)[:, :K]
+    return order, np.take_along_axis(d2, order, axis=1)
+
+
+def _int_features(rng, Ns, Nt, K, d=32):
+    L = (2 ** 24 - 1) // (K * Ns)
+    vp = np.zeros((Ns, d), np.float32)
+    vp[np.arange(Ns), np.arange(Ns) % d] = rng.choice([-1.0, 1.0], Ns)
+    vq = rng.randint(-L, L + 1, (Nt, d)).astype(np.float32)
+    return vp, vq, L
+
+
+def test_corr_judge_neighbour_sets_labels_and_scores():
+    """orc_corr_judge_f32 in both forms: neighbour sets equal a numpy brute force on the same form's images; the reference form's sets
+    are orc_pc_corr_cost_f32's (with unit weights and integer features both scores are exact: equal to the label / Ns); the labels equal
+    a numpy recomputation from the returned sets; the fp64 score and absum equal a numpy fp64 restatement on real features."""
+    rng = np.random.RandomState(8)
+    Ns, Nt, K, M = 300, 700, 20, 12
+    tp = (rng.uniform(-10, 10, (Nt, 3)) * [1, 1, 0.2]).astype(np.float32)
+    sp = (tp[rng.randint(0, Nt, Ns)] + rng.standard_normal((Ns, 3)) * 0.3).astype(np.float32)
+    T = np.tile(np.eye(4, dtype=np.float32), (M, 1, 1))
+    for h in range(1, M):
+        th = rng.uniform(-0.3, 0.3)
+        T[h, :2, :2] = [[np.cos(th), -np.sin(th)], [np.sin(th), np.cos(th)]]
+        T[h, :3, 3] = rng.standard_normal(3) * rng.choice([0.1, 3.0])
+    vp, vq, L = _int_features(rng, Ns, Nt, K)
+    assert L == (2 ** 24 - 1) // (K * Ns)
+    sets = {}
+    for form in (orc.CORR_FORM_REF, orc.CORR_FORM_FMA):
+        j = orc.corr_judge(T, sp, tp, K, vp, vq, 2.0 ** 22, form=form, neighbours=True)
+        q = orc.corr_images(T, sp, form)
+        for h in range(M):
+            idx, d2 = _numpy_neighbours(q[h], tp, K)
+            assert np.array_equal(j.idx[h], idx) and np.array_equal(j.d2[h], d2), (form, h)
+            lab = (vp[:, None, :] * vq[idx]).sum(-1, dtype=np.float64).sum()
+            assert j.label[h] == lab == np.rint(lab), (form, h)
+        sets[form] = j
+    # the two forms differ on some images (by an ulp), and can differ on the sets
+    assert not np.array_equal(orc.corr_images(T, sp, 0), orc.corr_images(T, sp, 1))
+    ref = orc.pc_corr_cost_c(T, sp, tp, K, vp, vq, 2.0 ** 22)
+    assert np.array_equal(ref, (sets[orc.CORR_FORM_REF].label / Ns).astype(np.float32))
+    assert np.all(np.abs(sets[orc.CORR_FORM_REF].score * Ns - sets[orc.CORR_FORM_REF].label) <= 1e-9 * sets[orc.CORR_FORM_REF].absum)
+    # real features and sigma: the fp64 score / absum on the same sets
+    vp = rng.standard_normal((Ns, 32)).astype(np.float32); vq = rng.standard_normal((Nt, 32)).astype(np.float32)
+    sigma = 0.7
+    j = orc.corr_judge(T, sp, tp, K, vp, vq, sigma, neighbours=True)
+    assert np.array_equal(j.idx, sets[orc.CORR_FORM_FMA].idx)
+    for h in range(M):
+        w = 1.0 / (1.0 + j.d2[h].astype(np.float64) / sigma ** 2)
+        t = vp.astype(np.float64)[:, None, :] * vq.astype(np.float64)[j.idx[h]]
+        assert abs(j.score[h] - (w * t.sum(-1)).sum() / Ns) <= 1e-12 * np.abs(w * t.sum(-1)).sum() / Ns
+        assert abs(j.absum[h] - (w * np.abs(t).sum(-1)).sum()) <= 1e-12 * j.absum[h]
+    ref = orc.pc_corr_cost(T[:, :3, :3], T[:, :3, 3], sp, tp, K, vp, vq, sigma)
+    assert np.all(np.abs(ref - j.score) <= 1e-5 * j.absum / Ns)
+
+
+def test_corr_judge_lattice_ties_go_to_the_lower_index():
+    """A target on an integer lattice (shuffled, with duplicated points) and queries on lattice points, cell centres and edge midpoints:
+    distance ties by the dozen at the K-th place.  The sets equal the numpy (d2, index) order: every tie goes to the lower index."""
+    rng = np.random.RandomState(4)
+    g = np.stack(np.meshgrid(np.arange(8), np.arange(8), np.arange(3), indexing="ij"), -1).reshape(-1, 3).astype(np.float32)
+    tp = np.concatenate([g, g[rng.randint(0, len(g), 40)]])[rng.permutation(len(g) + 40)]
+    sp = np.concatenate([g[rng.randint(0, len(g), 60)], g[rng.randint(0, len(g), 60)] + 0.5,
+                         g[rng.randint(0, len(g), 60)] + [0.5, 0, 0]]).astype(np.float32)
+    T = np.tile(np.eye(4, dtype=np.float32), (2, 1, 1))
+    T[1, :3, 3] = [1.0, -2.0, 0.0]
+    vp, vq, _ = _int_features(rng, sp.shape[0], tp.shape[0], 20)
+    n_ties = 0
+    for K in (1, 6, 20):
+        j = orc.corr_judge(T, sp, tp, K, vp, vq, 2.0 ** 22, neighbours=True)
+        for h in range(2):
+            q = orc.corr_images(T[h:h + 1], sp)[0]
+            idx, d2 = _numpy_neighbours(q, tp, K)
+            assert np.array_equal(j.idx[h], idx) and np.array_equal(j.d2[h], d2), (K, h)
+            d = q[:, None, :] - tp[None]
+            full = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+            n_ties += int((full == d2[:, -1:]).sum(1).__gt__((d2 == d2[:, -1:]).sum(1)).sum())
+    assert n_ties > 100, n_ties                        # K-boundary ties were there to break
