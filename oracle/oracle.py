@@ -45,7 +45,7 @@ def lib():
         _lib = ctypes.CDLL(_SO)
         for name in ("orc_ball_query_f32", "orc_ball_query_fma_f32", "orc_ume_moments_f32", "orc_orthobasis_f64",
                      "orc_ume_cdist_f64", "orc_ume_match_f64", "orc_knn_points_f32", "orc_pc_corr_cost_f32",
-                     "orc_corr_images_f32", "orc_corr_judge_f32"):
+                     "orc_corr_images_f32", "orc_corr_judge_f32", "orc_match_split_f64"):
             getattr(_lib, name).restype = ctypes.c_int
     return _lib
 
@@ -231,6 +231,89 @@ def ume_match_f64(ume1, ume2, cols=None):
                                  _p(b1), _p(b2), _p(d_at))
     assert rc == 0, rc
     return UmeMatch64(am, b1, b2, d_at)
+
+
+# Split-f16 basis layouts (umeregrobust_amd/csrc/qlayout.h, hoff_rows / hoff_cols): every basis entry q is stored as two
+# halfs, hi = f16(q) (plane 0) and lo = f16(q - hi) (plane 1), rounded from the fp64 Householder Q inside the library's
+# orthobasis kernel -- so they cannot be rebuilt from its fp32 output and are decoded from the buffer it wrote.
+QLAYOUT_ROWS_F16X2, QLAYOUT_COLS_F16X2 = 3, 4
+
+
+def split_f16_halfs(n, layout):
+    """Number of halfs of a split-f16 basis buffer of n keypoints (umereg_qbasis_bytes / 2): ROWS pads n to 128, COLS to 32."""
+    pad = {QLAYOUT_ROWS_F16X2: 128, QLAYOUT_COLS_F16X2: 32}[layout]
+    return (n + pad - 1) // pad * pad * 256
+
+
+def split_f16_offsets(n, layout):
+    """Half offsets of entry (keypoint, channel k, basis column, plane): int64 [n,32,4,2], restated from hoff_rows / hoff_cols."""
+    i = np.arange(n, dtype=np.int64)[:, None, None, None]
+    k = np.arange(32, dtype=np.int64)[None, :, None, None]
+    a = np.arange(4, dtype=np.int64)[None, None, :, None]
+    pl = np.arange(2, dtype=np.int64)[None, None, None, :]
+    s, h, e = k >> 4, (k >> 3) & 1, k & 7
+    if layout == QLAYOUT_ROWS_F16X2:
+        return (((((i >> 3) * 2 + s) * 2 + pl) * 64) + h * 32 + (i & 7) * 4 + a) * 8 + e
+    if layout == QLAYOUT_COLS_F16X2:
+        return ((((((i >> 5) * 4 + a) * 2 + s) * 2 + pl) * 64) + h * 32 + (i & 31)) * 8 + e
+    raise ValueError(f"not a split-f16 layout: {layout}")
+
+
+def decode_split_f16(buf, n, layout):
+    """Split-f16 basis buffer (any dtype, e.g. ops.ume_orthobasis(ume, layout) copied to the host) -> (hi, lo) f16 [n,32,4]."""
+    h = np.ascontiguousarray(buf).reshape(-1).view(np.float16)
+    assert h.size >= split_f16_halfs(n, layout), (h.size, split_f16_halfs(n, layout))
+    off = split_f16_offsets(n, layout)
+    return h[off[..., 0]], h[off[..., 1]]
+
+
+def encode_split_f16(hi, lo, layout):
+    """Inverse of decode_split_f16: (hi, lo) f16 [n,32,4] -> the layout's buffer as f16 [split_f16_halfs], padding zero."""
+    n = hi.shape[0]
+    out = np.zeros(split_f16_halfs(n, layout), np.float16)
+    off = split_f16_offsets(n, layout)
+    out[off[..., 0]] = np.asarray(hi, np.float16)
+    out[off[..., 1]] = np.asarray(lo, np.float16)
+    return out
+
+
+SplitMatch = namedtuple("SplitMatch", "argmin key arg2 key2 d64 d64sec coarse_win coarse_max")
+
+# Bound on |computed - exact| of one fp64 evaluation of 4 - |Qa^T Qb|_F^2 from split bases, in ANY summation order (and with
+# or without fused multiply-adds).  Each of the 16 entries sums 32 exact products whose magnitudes add up to at most
+# |qa||vb| <= 1 + 2^-20 (column norms 1 to fp64 rounding; hi + lo is within 2^-25 of q in each of 32 entries): recursive summation
+# errs by <= 31 u (1 + 2^-20).  Squaring moves that by 2 |c| per entry, and sum |c| <= 4 |C|_F <= 8 (+ rounding): <= 16 * 31 u;
+# the 16 squares (<= 1 rounding each if not fused) and the 16-term sum add <= 4 u + 16 * 4 u, the subtraction from 4 <= 4 u.
+# In all <= 572 u (1 + 2^-19) < 6.4e-14.  Two evaluations in different orders differ by at most twice that.
+SPLIT_EVAL_ERR = 573 * 2.0 ** -53
+
+
+def match_split_f64(A_hilo, B_hilo, coarse=True):
+    """The "f16r" refine pass's arg-min over ALL targets, restated term for term (orc_match_split_f64) on the split planes the
+    library wrote.  A_hilo = (hi, lo) of the source set (decoded from ROWS_F16X2), B_hilo = (hi, lo) of the targets (COLS_F16X2).
+    The refine holds a source entry as (double)hi + (double)lo and reads a target entry as (double)((float)hi + (float)lo) (the
+    same number for planes split from |q| <= 1: hi + lo spans at most 24 bits), and so does this restatement.  The key is (fp32(max(4 - s, 0)), j): ties in fp32 go to the
+    lower index, as the kernel's LDS atomicMin on (bits(d2) << 32 | j) does.
+    -> SplitMatch(argmin i64, key f32 (the winner's d2; the kernel's d = sqrtf(key)), arg2 i64 / key2 f32 (runner-up by the
+       same key), d64 f64 (the winner's fp64 d2), d64sec f64 (the smallest fp64 d2 of every other target),
+       coarse_win / coarse_max f64 (hi-only score at the winner / the row's maximum; None unless coarse))."""
+    (ahi, alo), (bhi, blo) = A_hilo, B_hilo
+    ahi, alo, bhi, blo = (np.asarray(x, np.float16) for x in (ahi, alo, bhi, blo))
+    assert ahi.shape == alo.shape and bhi.shape == blo.shape and ahi.shape[1:] == bhi.shape[1:] == (32, 4)
+    qa = np.ascontiguousarray(ahi.astype(np.float64) + alo.astype(np.float64))
+    vb = np.ascontiguousarray((bhi.astype(np.float32) + blo.astype(np.float32)).astype(np.float64))
+    n1, n2 = qa.shape[0], vb.shape[0]
+    ah = np.ascontiguousarray(ahi, np.float64) if coarse else None
+    bh = np.ascontiguousarray(bhi, np.float64) if coarse else None
+    am, a2 = np.empty(n1, np.int64), np.empty(n1, np.int64)
+    k1, k2 = np.empty(n1, np.float32), np.empty(n1, np.float32)
+    d1, d2 = np.empty(n1, np.float64), np.empty(n1, np.float64)
+    cw = np.empty(n1, np.float64) if coarse else None
+    cm = np.empty(n1, np.float64) if coarse else None
+    rc = lib().orc_match_split_f64(_p(qa), _p(vb), _p(ah), _p(bh), ctypes.c_int64(n1), ctypes.c_int64(n2), _p(am), _p(k1), _p(a2),
+                                   _p(k2), _p(d1), _p(d2), _p(cw), _p(cm))
+    assert rc == 0, rc
+    return SplitMatch(am, k1, a2, k2, d1, d2, cw, cm)
 
 
 def orthobasis_f64(ume):

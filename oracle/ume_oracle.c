@@ -538,3 +538,96 @@ ORC_API int orc_corr_judge_f32(const float* T, int64_t M, const float* sp, int64
     free(acc);
     return 0;
 }
+
+/* --------------------------------------------------------------------------
+ * a3+a4 as the "f16r" matcher's refine pass computes it (subspace_dist.hip,
+ * match_refine_kernel), restated term for term on the split-f16 planes the
+ * library itself wrote (oracle.decode_split_f16):
+ *   qa[i]  [32,4]  row i's basis as the refine holds it: (double)hi + (double)lo,
+ *   vb[j]  [32,4]  column j's basis as the refine reads it: (double)((float)hi + (float)lo),
+ *   dot[a][b] = fma(qa[k][a], vb[k][b], dot[a][b]) for k = 0..31 in order,
+ *   s = fma(dot[a][b], dot[a][b], s) for a = 0..3, b = 0..3 (b inner),
+ *   d2 = (float)fmax(4 - s, 0), key = (bits(d2), j), the minimum key wins:
+ *   ties in fp32 go to the lower index.
+ * Per row i:
+ *   argmin[i], key[i]          the winning j and its d2 (fp32),
+ *   arg2[i], key2[i]           the runner-up by the same key (n2 == 1: -1, +inf),
+ *   d64[i], d64sec[i]          fmax(4 - s, 0) in fp64 at argmin[i], and its minimum over every other j,
+ *   coarse_win[i], coarse_max[i] (ah, bh non-NULL) the hi-only score sum_ab (sum_k hi[k][a] hi[k][b])^2
+ *                              (fp64; the products are exact) at argmin[i], and its row maximum.
+ * fma() must round once: the hot loop is compiled for the FMA unit when the host has one
+ * and calls libm's (correctly rounded) fma otherwise.
+ * -------------------------------------------------------------------------- */
+#define ORC_SPLIT_ROW_BODY(FMA)                                                                  \
+    do {                                                                                         \
+        const double* a = qa + i * 128;                                                          \
+        const double* ha = ah ? ah + i * 128 : NULL;                                             \
+        uint64_t bk = UINT64_MAX, bk2 = UINT64_MAX;                                              \
+        double bd64 = INFINITY, sec64 = INFINITY, cmax = -INFINITY, cwin = 0.0;                  \
+        for (int64_t j = 0; j < n2; ++j) {                                                       \
+            const double* b = vb + j * 128;                                                      \
+            double dot[4][4] = {{0.0}};                                                          \
+            for (int k = 0; k < 32; ++k)                                                         \
+                for (int bb = 0; bb < 4; ++bb)                                                   \
+                    for (int aa = 0; aa < 4; ++aa) dot[aa][bb] = FMA(a[k * 4 + aa], b[k * 4 + bb], dot[aa][bb]); \
+            double s = 0.0;                                                                      \
+            for (int aa = 0; aa < 4; ++aa)                                                       \
+                for (int bb = 0; bb < 4; ++bb) s = FMA(dot[aa][bb], dot[aa][bb], s);             \
+            const double v = fmax(4.0 - s, 0.0);                                                 \
+            const float f = (float)v;                                                            \
+            uint32_t fb;                                                                         \
+            memcpy(&fb, &f, 4);                                                                  \
+            const uint64_t key = ((uint64_t)fb << 32) | (uint64_t)j;                             \
+            double c = 0.0;                                                                      \
+            if (ha) {                                                                            \
+                const double* hb = bh + j * 128;                                                 \
+                for (int aa = 0; aa < 4; ++aa)                                                   \
+                    for (int bb = 0; bb < 4; ++bb) {                                             \
+                        double e = 0.0;                                                          \
+                        for (int k = 0; k < 32; ++k) e += ha[k * 4 + aa] * hb[k * 4 + bb];       \
+                        c += e * e;                                                              \
+                    }                                                                            \
+                if (c > cmax) cmax = c;                                                          \
+            }                                                                                    \
+            if (key < bk) {                                                                      \
+                bk2 = bk; bk = key;                                                              \
+                sec64 = fmin(sec64, bd64); bd64 = v; cwin = c;                                   \
+            } else {                                                                             \
+                if (key < bk2) bk2 = key;                                                        \
+                sec64 = fmin(sec64, v);                                                          \
+            }                                                                                    \
+        }                                                                                        \
+        argmin[i] = (int64_t)(bk & 0xffffffffu);                                                 \
+        uint32_t kb = (uint32_t)(bk >> 32);                                                      \
+        memcpy(&key1[i], &kb, 4);                                                                \
+        if (bk2 == UINT64_MAX) { arg2[i] = -1; key2[i] = INFINITY; }                             \
+        else { arg2[i] = (int64_t)(bk2 & 0xffffffffu); kb = (uint32_t)(bk2 >> 32); memcpy(&key2[i], &kb, 4); } \
+        d64[i] = bd64;                                                                           \
+        d64sec[i] = sec64;                                                                       \
+        if (ha) { coarse_win[i] = cwin; coarse_max[i] = cmax; }                                  \
+    } while (0)
+
+#define ORC_SPLIT_ARGS const double* qa, const double* vb, const double* ah, const double* bh, int64_t n1, int64_t n2, \
+    int64_t* argmin, float* key1, int64_t* arg2, float* key2, double* d64, double* d64sec, double* coarse_win, double* coarse_max
+
+__attribute__((target("fma,avx2"), optimize("O3"))) static void orc_match_split_rows_fma(ORC_SPLIT_ARGS)
+{
+#pragma omp parallel for schedule(dynamic, 4)
+    for (int64_t i = 0; i < n1; ++i) ORC_SPLIT_ROW_BODY(__builtin_fma);
+}
+
+static void orc_match_split_rows_libm(ORC_SPLIT_ARGS)
+{
+#pragma omp parallel for schedule(dynamic, 4)
+    for (int64_t i = 0; i < n1; ++i) ORC_SPLIT_ROW_BODY(fma);
+}
+
+ORC_API int orc_match_split_f64(ORC_SPLIT_ARGS)
+{
+    if (n1 < 0 || n2 < 1 || n2 >= ((int64_t)1 << 32) || (ah == NULL) != (bh == NULL)) return -1;
+    if (ah && (!coarse_win || !coarse_max)) return -1;
+    __builtin_cpu_init();
+    if (__builtin_cpu_supports("fma") && __builtin_cpu_supports("avx2")) orc_match_split_rows_fma(qa, vb, ah, bh, n1, n2, argmin, key1, arg2, key2, d64, d64sec, coarse_win, coarse_max);
+    else orc_match_split_rows_libm(qa, vb, ah, bh, n1, n2, argmin, key1, arg2, key2, d64, d64sec, coarse_win, coarse_max);
+    return 0;
+}

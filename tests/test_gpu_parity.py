@@ -523,6 +523,164 @@ def test_ume_match_f16r_spatially_ordered_keypoints(gpu, opts=None):
         assert np.abs(D[rows, back[diff]] - D[rows, N_(mr[0])[diff]]).max() < 1e-3
 
 
+# ---- f16r judged exactly: the refine's own arithmetic on the split planes the library wrote -----------------------------------
+def _split_planes_of(F, gpu):
+    """(hi, lo) planes of the source set (ROWS_F16X2) and of the target set (COLS_F16X2), as ume_orthobasis wrote them for F [2][n]."""
+    from umeregrobust_amd import ops
+    out = []
+    for u, layout in zip(F, (orc.QLAYOUT_ROWS_F16X2, orc.QLAYOUT_COLS_F16X2)):
+        buf = N_(ops.ume_orthobasis(T_(u, gpu), layout))
+        hi, lo = orc.decode_split_f16(buf, u.shape[0], layout)
+        # the decoder reads every byte the kernel wrote (padding is zero): the host index map IS the kernel's layout
+        assert np.array_equal(orc.encode_split_f16(hi, lo, layout).view(np.uint16), buf.view(np.uint16))
+        out.append((hi, lo))
+    return out
+
+
+def _f16r_routes(u1, u2, A, B, gpu, splits=(1, 2, 3, 8)):
+    """Every route to the "f16r" matcher on one pair of UME sets -> {route: (m i64 [n1], d f32 [n1])}.  The layered entries get
+    the planes re-encoded on the host from the decoded (A, B), so they also check the encoder against the kernel's readers."""
+    from umeregrobust_amd import _lib, ops
+    lib = _lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+    n1, n2 = u1.shape[0], u2.shape[0]
+    a, b = T_(u1, gpu)[None].contiguous(), T_(u2, gpu)[None].contiguous()
+    P = lambda **kw: ops.MatchOpts(variant=1, **kw)            # noqa: E731
+    opts = {"default": None, "pform": P(), "share_mask=0": ops.MatchOpts(share_mask=0), "pform share_mask=0": P(share_mask=0),
+            "exhaustive": ops.MatchOpts(force_exhaustive=1), "pform exhaustive": P(force_exhaustive=1)}
+    for k in splits:
+        opts[f"splits={k}"] = ops.MatchOpts(splits=k)
+        opts[f"pform splits={k}"] = P(splits=k)
+    out = {}
+    for name, o in opts.items():
+        m, d = ops.ume_match(a, b, precision="f16r", opts=o)
+        out["ume_match " + name] = (N_(m[0]), N_(d[0]))
+    ha = T_(orc.encode_split_f16(*A, orc.QLAYOUT_ROWS_F16X2), gpu)
+    hb = T_(orc.encode_split_f16(*B, orc.QLAYOUT_COLS_F16X2), gpu)
+    for name, o in (("", None), (" pform", P())):
+        op = _lib.opts_ptr(o)
+        sb = lib.umereg_ume_match_q_scratch_bytes_ex(n1, n2, op)
+        scratch = torch.empty(sb, dtype=torch.uint8, device=gpu)
+        m = torch.empty(n1, dtype=torch.int64, device=gpu); d = torch.empty(n1, device=gpu)
+        if o is None:
+            _lib.check(lib.umereg_ume_match_q_f16r(ha.data_ptr(), hb.data_ptr(), n1, n2, m.data_ptr(), d.data_ptr(), scratch.data_ptr(),
+                                                   sb, st), "umereg_ume_match_q_f16r")
+        else:
+            _lib.check(lib.umereg_ume_match_q_f16r_ex(ha.data_ptr(), hb.data_ptr(), n1, n2, m.data_ptr(), d.data_ptr(),
+                                                      scratch.data_ptr(), sb, op, st), "umereg_ume_match_q_f16r_ex")
+        out["q_f16r" + name] = (N_(m), N_(d))
+        m = torch.empty(n1, dtype=torch.int64, device=gpu); d = torch.empty(n1, device=gpu)
+        scratch.fill_(0xA5)                                    # the stages own the scratch: nothing may be left to chance
+        _lib.check(lib.umereg_ume_match_reset_f16(scratch.data_ptr(), sb, n1, n2, st), "umereg_ume_match_reset_f16")
+        if o is None:
+            _lib.check(lib.umereg_ume_match_coarse_f16(ha.data_ptr(), hb.data_ptr(), n1, n2, scratch.data_ptr(), sb, st), "coarse")
+            _lib.check(lib.umereg_ume_match_refine_f16(ha.data_ptr(), hb.data_ptr(), n1, n2, scratch.data_ptr(), sb, m.data_ptr(),
+                                                       d.data_ptr(), st), "refine")
+        else:
+            _lib.check(lib.umereg_ume_match_coarse_f16_ex(ha.data_ptr(), hb.data_ptr(), n1, n2, scratch.data_ptr(), sb, op, st), "coarse")
+            _lib.check(lib.umereg_ume_match_refine_f16_ex(ha.data_ptr(), hb.data_ptr(), n1, n2, scratch.data_ptr(), sb, m.data_ptr(),
+                                                          d.data_ptr(), op, st), "refine")
+        out["coarse+refine" + name] = (N_(m), N_(d))
+        ws_b = lib.umereg_ume_match_workspace_bytes_ex(1, n1, n2, op)
+        ws = torch.empty(ws_b, dtype=torch.uint8, device=gpu)
+        m = torch.empty((1, n1), dtype=torch.int64, device=gpu); d = torch.empty((1, n1), device=gpu)
+        if o is None:
+            _lib.check(lib.umereg_ume_match_f16r(a.data_ptr(), b.data_ptr(), 1, n1, n2, m.data_ptr(), d.data_ptr(), ws.data_ptr(), ws_b,
+                                                 st), "umereg_ume_match_f16r")
+        else:
+            _lib.check(lib.umereg_ume_match_f16r_ex(a.data_ptr(), b.data_ptr(), 1, n1, n2, m.data_ptr(), d.data_ptr(), ws.data_ptr(),
+                                                    ws_b, op, st), "umereg_ume_match_f16r_ex")
+        out["one-call f16r" + name] = (N_(m[0]), N_(d[0]))
+    torch.cuda.synchronize()
+    return out
+
+
+def _assert_routes_exact(routes, r, case):
+    """Every route returns the oracle's arg-min on every row, and d = sqrtf(the oracle's fp32 key) bit for bit: the refine's last
+    steps are d2 = (float)fmax(4 - s, 0) and sqrtf(d2), both correctly rounded (HIP's default fp32 sqrt), so d is restated exactly."""
+    want_d = np.sqrt(r.key)
+    for name, (m, d) in routes.items():
+        bad = np.flatnonzero(m != r.argmin)
+        assert bad.size == 0, (case, name, bad.size, bad[:6], m[bad[:6]], r.argmin[bad[:6]], r.key[bad[:6]])
+        badd = np.flatnonzero(d.view(np.uint32) != want_d.view(np.uint32))
+        assert badd.size == 0, (case, name, badd[:6], d[badd[:6]], want_d[badd[:6]])
+
+
+# crafted crowds: (n1, n2, crowd size, crowd rows, min. coarse inversions).  Crowd rows sit in every 16-row (Q-form) and 32-row
+# (P-form) block beside rows without a crowd and rows whose crowd sits at a lower score level; the crowds start in the first, a
+# middle and the last target split of every forced plan (splits 1, 2, 3, 8 and the automatic one).
+_CROWD_CASES = {
+    "c20": (256, 6000, 20, 48, 24),
+    "c500": (64, 6000, 500, 8, 4),          # just under kRegionCap: one region of a 2-split plan holds a whole crowd
+    "c600": (64, 6000, 600, 6, 3),          # above kRegionCap: the block's region overflows, the refine re-scans it exhaustively
+    "c1100": (96, 7000, 1100, 4, 2),        # above kPRegionCap (P-form)
+    "c20tiny": (256, 6000, 20, 48, 24),     # many near-zero basis entries: lo (and some hi) are f16 subnormals
+}
+
+
+def _crowd_case(case):
+    """u1 [n1,32,4], u2 [n2,32,4] f32 and the placed winners {row: target}.  A crowd for row i is `size` targets
+    u1[i] * (1 + c) * (1 + eps * noise) with eps log-uniform in 1e-7 .. 1e-3 and a level c = 0 or a fixed 2e-2 perturbation (a
+    lower score level for the whole crowd).  D^2 ~ 3 eps^2, but the split planes carry ~2^-25 of rounding per entry, so any D^2
+    below ~1e-8 is decided by that rounding (many clamp to 0, and the lowest index among them wins).  Placed crowds therefore put
+    eps = 1e-7 at the crowd's first, last or a random position and keep the others in 1e-3 .. 5e-3 (D^2 3e-6 .. 8e-5: far above
+    the rounding, far below the coarse error), so that the exact winner is known; free crowds leave it to the oracle."""
+    n1, n2, size, rows, _ = _CROWD_CASES[case]
+    rng = np.random.RandomState(sum(map(ord, case)))
+    u1 = rng.standard_normal((n1, 32, 4))
+    u2 = rng.standard_normal((n2, 32, 4))
+    if case.endswith("tiny"):
+        u1[:, 6:] *= 10.0 ** rng.uniform(-6, -3, (n1, 26, 1))
+        u2[:, 6:] *= 10.0 ** rng.uniform(-6, -3, (n2, 26, 1))
+    crowd_rows = np.sort(rng.choice(n1, rows, replace=False))
+    room = n2 - size
+    starts = np.linspace(0, room, rows).astype(np.int64)                   # first split ... last split (last crowd ends at n2)
+    assert np.all(np.diff(starts) >= size) or rows * size > n2
+    placed = {}
+    for c, (i, s) in enumerate(zip(crowd_rows, starts)):
+        level = (1.0 + 2e-2 * rng.standard_normal((32, 4))) if c % 3 == 2 else 1.0
+        mode = ("low", "high", "rand", None)[c % 4] if c % 3 != 2 else None   # around a shifted centre the smallest eps need not win
+        if mode is None:
+            eps = 10.0 ** rng.uniform(-7, -3, size)
+        else:
+            eps = 10.0 ** rng.uniform(-3, -2.3, size)
+            pos = {"low": 0, "high": size - 1, "rand": rng.randint(size)}[mode]
+            eps[pos] = 1e-7
+            placed[int(i)] = int(s + pos)
+        u2[s:s + size] = (u1[i] * level)[None] * (1.0 + eps[:, None, None] * rng.standard_normal((size, 32, 4)))
+    return u1.astype(np.float32), u2.astype(np.float32), crowd_rows, placed
+
+
+@pytest.mark.parametrize("case", list(_CROWD_CASES))
+def test_ume_match_f16r_crowds_exact_in_every_route(gpu, case):
+    """Near-duplicate crowds whose exact D^2 differ by far less than the coarse (hi-only) score error: inside a crowd the coarse
+    order is NOT the exact order, so a filter that loses the exact winner (a polluted or stale limit, a margin applied the wrong way,
+    a candidate lost on region overflow or at a split boundary) returns a near neighbour instead -- which the 2e-5 tie band of the
+    fp64-from-UME gates accepts.  Judged here against oracle.match_split_f64 on the planes the library itself wrote: the refine's
+    arithmetic term for term, so every row is judged exactly (no tie band), in every route of ume_match(precision="f16r")."""
+    u1, u2, crowd_rows, placed = _crowd_case(case)
+    assert len(placed) >= len(crowd_rows) // 3
+    min_inv = _CROWD_CASES[case][4]
+    A, B = _split_planes_of((u1, u2), gpu)
+    r = orc.match_split_f64(A, B)
+    # premises: the placed winners win, the crowds' coarse order is inverted, the tiny case has subnormal planes
+    assert all(r.argmin[i] == j for i, j in placed.items()), {i: (j, int(r.argmin[i])) for i, j in placed.items() if r.argmin[i] != j}
+    inv = np.flatnonzero(r.coarse_max - r.coarse_win > 1e-4)          # > fp32 accumulation noise of the coarse MFMA score
+    assert np.isin(crowd_rows, inv).sum() >= min_inv, (np.isin(crowd_rows, inv).sum(), min_inv)
+    sub_lo = float(((A[1] != 0) & (np.abs(A[1].astype(np.float32)) < 2.0 ** -14)).mean())
+    if case.endswith("tiny"):
+        assert ((A[0] != 0) & (np.abs(A[0].astype(np.float32)) < 2.0 ** -14)).sum() > 1000
+        flushed = orc.match_split_f64((A[0], np.where(np.abs(A[1].astype(np.float32)) < 2.0 ** -14, np.float16(0), A[1])), B,
+                                      coarse=False)
+        assert (flushed.key != r.key).mean() > 0.25          # flushing the subnormal lo planes would change the answer
+    near = np.float32(r.d64sec - 2 * orc.SPLIT_EVAL_ERR) <= np.float32(r.d64 + 2 * orc.SPLIT_EVAL_ERR)
+    routes = _f16r_routes(u1, u2, A, B, gpu)
+    _assert_routes_exact(routes, r, case)
+    print(f"[f16r crowds {case}] routes {len(routes)}, crowd rows {len(crowd_rows)}, coarse inversions {int(np.isin(crowd_rows, inv).sum())}"
+          f" in crowd rows / {inv.size} in all, rows undecidable by a reference of another summation order {int(near.sum())},"
+          f" subnormal lo {sub_lo:.2f}")
+
+
 def test_ume_cdist_batch(gpu):
     from umeregrobust_amd import ops
     rng = np.random.RandomState(2)
@@ -2325,14 +2483,18 @@ def _ume_cond(F):
         return np.where(s[:, -1] > 0, s[:, 0] / s[:, -1], np.inf)
 
 
-def _match_gate(F_src, F_tgt, m, d):
+def _match_gate(F_src, F_tgt, m, d, gpu=None):
     """a3/a4 against the fp64 truth (the bars of test_ume_match_f16r_vs_oracle) on every row whose source basis is determined
     (_COND_UNDETERMINED): the chosen target is the fp64 arg-min wherever the two smallest D^2 are more than 2e-5 apart, and within 2e-5
     of the minimum D^2; d = D64 at the chosen target to 2e-5 (2e-3 near D = 0).  The truth is taken over the targets with a determined
     basis; a row whose pick is an undetermined target (no fp64 value for its D) must still claim a D^2 no more than 2e-5 above the
     determined minimum.
     -> dict(gap = max D^2 gap, off_argmin = rows off the arg-min (inside the tie band), d_err = max |d - D64|,
-            undetermined_src = rows not judged, undetermined_pick = rows judged by the claim only)"""
+            undetermined_src = rows not judged, undetermined_pick = rows judged by the claim only)
+    gpu: also judge EVERY row exactly -- tie-band rows included -- against oracle.match_split_f64 on the split-f16 planes the library
+    writes for these F (first shown to be the planes the pipeline matched on: ume_match on the same F returns its m and d); adds
+    tie_band = rows inside the 2e-5 band above, split_near = rows a reference of another summation order could not decide, and
+    coarse_inversions = rows whose exact winner is not the coarse (hi-only) arg-max."""
     und_s, und_t = _ume_cond(F_src) > _COND_UNDETERMINED, _ume_cond(F_tgt) > _COND_UNDETERMINED
     assert not und_t.all()
     r = orc.ume_match_f64(F_src, F_tgt, cols=m)
@@ -2353,8 +2515,22 @@ def _match_gate(F_src, F_tgt, m, d):
     pick_und = ~und_s & und_t[m]
     claim = d[pick_und].astype(np.float64) ** 2 - d2min[pick_und]
     assert claim.max(initial=-1.0) <= 2e-5, (claim.max(), np.flatnonzero(pick_und)[claim.argmax()])
-    return dict(gap=float(gap.max(initial=0.0)), off_argmin=int((m != argmin)[judged].sum()), d_err=float(err[judged].max(initial=0.0)),
-                undetermined_src=int(und_s.sum()), undetermined_pick=int(pick_und.sum()))
+    out = dict(gap=float(gap.max(initial=0.0)), off_argmin=int((m != argmin)[judged].sum()), d_err=float(err[judged].max(initial=0.0)),
+               undetermined_src=int(und_s.sum()), undetermined_pick=int(pick_und.sum()))
+    if gpu is not None:
+        from umeregrobust_amd import ops
+        m2, d2 = ops.ume_match(T_(F_src, gpu)[None], T_(F_tgt, gpu)[None])
+        assert np.array_equal(N_(m2[0]), m) and np.array_equal(N_(d2[0]), d)
+        A, B = _split_planes_of((F_src, F_tgt), gpu)
+        rs = orc.match_split_f64(A, B)
+        bad = np.flatnonzero(m != rs.argmin)
+        assert bad.size == 0, (bad.size, bad[:6], m[bad[:6]], rs.argmin[bad[:6]], rs.key[bad[:6]], rs.key2[bad[:6]])
+        badd = np.flatnonzero(d.view(np.uint32) != np.sqrt(rs.key).view(np.uint32))
+        assert badd.size == 0, (badd.size, badd[:6])
+        out.update(tie_band=int((judged & ((d2sec - d2min) <= 2e-5)).sum()),
+                   split_near=int((np.float32(rs.d64sec - 2 * orc.SPLIT_EVAL_ERR) <= np.float32(rs.d64 + 2 * orc.SPLIT_EVAL_ERR)).sum()),
+                   coarse_inversions=int((rs.coarse_max - rs.coarse_win > 1e-4).sum()))
+    return out
 
 
 @pytest.mark.parametrize("shape", ["KT", "KTr", "ROT", "NS", "SY"])
@@ -2365,7 +2541,8 @@ def test_full_size_stages_against_fp64_truth(gpu, shape):
     agree to about output rounding, and the bars are maxima, not quantiles:
       a1/a2  all keypoints of both clouds: counts == the oracle's, every F entry within 1 ulp of the oracle's fp64-rounded value (entries
              below 1e-6 of their matrix's scale: 3e-7 * scale); ball indices bit-exact on 256 keypoints; SY has saturated balls;
-      a3/a4  library F -> oracle.ume_match_f64 (_match_gate);
+      a3/a4  library F -> oracle.ume_match_f64 (_match_gate), and every row exactly against oracle.match_split_f64 on the
+             library's own split-f16 planes;
       a5     prob against an fp64 softmax of the library's d: relative 1e-5;
       a6     library F, cond, matches -> oracle.batch_estimate_transform_ume_f64: |dR| <= 1e-6, |dt| <= 1e-5 max(1, |t|) except on
              hypotheses ill-posed in fp64 (_KAPPA_*_MAX; at most 0.5 %, still finite with det R = 1);
@@ -2439,7 +2616,7 @@ def test_full_size_stages_against_fp64_truth(gpu, shape):
     report["F_ulps"], report["t_a12"] = max(ulps), round(time.time() - t0, 1)
     # ---- a3 / a4
     t0 = time.time()
-    g34 = _match_gate(Fs, Ft, m, d)
+    g34 = _match_gate(Fs, Ft, m, d, gpu=gpu)
     assert g34["undetermined_src"] == 0 and g34["undetermined_pick"] == 0, g34          # every row of the full-size pairs is judged
     report.update({"a34_" + k_: v_ for k_, v_ in g34.items()})
     report["t_a34"] = round(time.time() - t0, 1)

@@ -533,3 +533,135 @@ def test_corr_judge_lattice_ties_go_to_the_lower_index():
             full = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
             n_ties += int((full == d2[:, -1:]).sum(1).__gt__((d2 == d2[:, -1:]).sum(1)).sum())
     assert n_ties > 100, n_ties                        # K-boundary ties were there to break
+
+
+# ---- the "f16r" refine restated on split-f16 planes (oracle.decode_split_f16 / orc_match_split_f64) ------------------------
+def split_planes(Q):
+    """hi = f16(q), lo = f16(q - hi) of an fp64 basis, as the library's orthobasis kernel splits it."""
+    Q = np.asarray(Q, np.float64)
+    hi = Q.astype(np.float16)
+    return hi, (Q - hi.astype(np.float64)).astype(np.float16)
+
+
+def _crowd_bases(rng, n1, n2, crowd=40, tiny=False):
+    """fp64 bases: n2 targets, the first n1 // 2 sources each with a crowd of `crowd` near-duplicate targets (eps 1e-7 .. 1e-3)."""
+    def orth(u):
+        return np.linalg.qr(u)[0]
+    u1 = rng.standard_normal((n1, 32, 4))
+    u2 = rng.standard_normal((n2, 32, 4))
+    if tiny:                                          # many near-zero channels: lo (and some hi) in the f16 subnormal range
+        u1[:, 4:] *= 10.0 ** rng.uniform(-6, -3, (n1, 28, 1))
+        u2[:, 4:] *= 10.0 ** rng.uniform(-6, -3, (n2, 28, 1))
+    for r in range(min(n1 // 2, n2 // crowd)):
+        s = r * crowd
+        eps = 10.0 ** rng.uniform(-7, -3, crowd)
+        u2[s:s + crowd] = u1[r] * (1.0 + eps[:, None, None] * rng.standard_normal((crowd, 32, 4)))
+    return orth(u1), orth(u2)
+
+
+def _split_brute_force(A, B):
+    """D2 = 4 - |Qa^T Qb|_F^2 of the split bases in numpy's own order (float64(hi) + float64(lo)), and the hi-only coarse score."""
+    qa = A[0].astype(np.float64) + A[1].astype(np.float64)
+    qb = B[0].astype(np.float64) + B[1].astype(np.float64)
+    C = np.einsum("ika,jkb->ijab", qa, qb)
+    D2 = np.maximum(4.0 - (C * C).sum(axis=(2, 3)), 0.0)
+    Ch = np.einsum("ika,jkb->ijab", A[0].astype(np.float64), B[0].astype(np.float64))
+    return D2, (Ch * Ch).sum(axis=(2, 3))
+
+
+def _fma_exact(a, b, c):
+    from fractions import Fraction
+    return float(Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c)))    # one rounding (Fraction.__float__ is exact-rounded)
+
+
+def test_split_f16_layout_decoder_round_trips():
+    """decode_split_f16 inverts encode_split_f16 bit for bit (subnormals, signed zeros), the index map is injective and in range,
+    padding stays zero, and a few offsets equal qlayout.h's formulas evaluated by hand."""
+    rng = np.random.RandomState(0)
+    for layout in (orc.QLAYOUT_ROWS_F16X2, orc.QLAYOUT_COLS_F16X2):
+        for n in (1, 7, 33, 129, 300):
+            hi = rng.standard_normal((n, 32, 4)).astype(np.float16)
+            lo = (rng.standard_normal((n, 32, 4)) * 2.0 ** rng.randint(-26, -10, (n, 32, 4))).astype(np.float16)
+            lo[0, 0, 0], hi[-1, 31, 3] = np.float16(-0.0), np.float16(2.0 ** -24)
+            buf = orc.encode_split_f16(hi, lo, layout)
+            assert buf.size == orc.split_f16_halfs(n, layout)
+            h2, l2 = orc.decode_split_f16(buf, n, layout)
+            assert np.array_equal(h2.view(np.uint16), hi.view(np.uint16)) and np.array_equal(l2.view(np.uint16), lo.view(np.uint16))
+            off = orc.split_f16_offsets(n, layout).reshape(-1)
+            assert np.unique(off).size == off.size and off.min() >= 0 and off.max() < buf.size
+            pad = np.ones(buf.size, bool); pad[off] = False
+            assert not buf.view(np.uint16)[pad].any()
+            # the decoder reads any dtype viewing the same bytes (the library's buffers come back as float32)
+            assert np.array_equal(orc.decode_split_f16(buf.view(np.float32), n, layout)[1].view(np.uint16), lo.view(np.uint16))
+    # hoff_rows(i = 9, a = 2, k = 21, plane = 1): s = 1, h = 0, e = 5 -> ((((1*2+1)*2+1)*64 + 0 + 1*4 + 2)*8 + 5
+    assert orc.split_f16_offsets(10, orc.QLAYOUT_ROWS_F16X2)[9, 21, 2, 1] == 3637
+    # hoff_cols(j = 37, b = 3, k = 10, plane = 0): s = 0, h = 1, e = 2 -> (((((1*4+3)*2+0)*2+0)*64 + 32 + 5)*8 + 2
+    assert orc.split_f16_offsets(40, orc.QLAYOUT_COLS_F16X2)[37, 10, 3, 0] == 14634
+    assert orc.split_f16_halfs(1, orc.QLAYOUT_ROWS_F16X2) == 128 * 256 and orc.split_f16_halfs(33, orc.QLAYOUT_COLS_F16X2) == 64 * 256
+
+
+def test_match_split_f64_restates_the_refine_term_for_term():
+    """The oracle's key is the refine kernel's, bit for bit: its fma chain in the kernel's order, evaluated in exact rationals with
+    one rounding per fma, then (float)max(4 - s, 0) -- on crowd pairs whose D^2 lives in the last bits of 4 - s."""
+    rng = np.random.RandomState(1)
+    A, B = (split_planes(Q) for Q in _crowd_bases(rng, 6, 40, crowd=12))
+    r = orc.match_split_f64(A, B)
+    qa = A[0].astype(np.float64) + A[1].astype(np.float64)
+    vb = (B[0].astype(np.float32) + B[1].astype(np.float32)).astype(np.float64)
+    for i in range(3):
+        keys = []
+        for j in range(B[0].shape[0]):
+            dot = np.zeros((4, 4))
+            for k in range(32):
+                for a in range(4):
+                    for b in range(4):
+                        dot[a, b] = _fma_exact(qa[i, k, a], vb[j, k, b], dot[a, b])
+            s = 0.0
+            for a in range(4):
+                for b in range(4):
+                    s = _fma_exact(dot[a, b], dot[a, b], s)
+            keys.append((np.float32(max(4.0 - s, 0.0)), j))
+        best = min(keys, key=lambda t: (t[0], t[1]))
+        assert r.argmin[i] == best[1] and r.key[i].view(np.uint32) == best[0].view(np.uint32), (i, r.argmin[i], r.key[i], best)
+        second = min((t for t in keys if t[1] != best[1]), key=lambda t: (t[0], t[1]))
+        assert r.arg2[i] == second[1] and r.key2[i] == second[0]
+    assert (r.key[:3] < 1e-7).all()                   # the crowd rows' winners are near-duplicates (key 0: s rounded to >= 4)
+
+
+@pytest.mark.parametrize("tiny", [False, True])
+def test_match_split_f64_equals_brute_force_on_the_summed_planes(tiny):
+    """orc_match_split_f64 against numpy's brute force on float64(hi) + float64(lo), which sums in another order: every row whose
+    best two fp64 D^2 cannot swap their fp32 keys within 2 SPLIT_EVAL_ERR has the same arg-min; any other row picks a target within
+    4 SPLIT_EVAL_ERR of numpy's minimum.  Keys, runner-ups and coarse hi-only scores agree to the same bound.  tiny: bases with many
+    near-zero entries, whose lo planes are mostly f16 subnormals -- they must survive (flushing them changes the answer)."""
+    rng = np.random.RandomState(7 if tiny else 3)
+    A, B = (split_planes(Q) for Q in _crowd_bases(rng, 120, 900, crowd=30, tiny=tiny))
+    r = orc.match_split_f64(A, B)
+    D2, Ch = _split_brute_force(A, B)
+    n1 = D2.shape[0]
+    rows = np.arange(n1)
+    e2 = 2 * orc.SPLIT_EVAL_ERR
+    srt = np.sort(D2, axis=1)
+    decided = np.float32(srt[:, 1] - e2) > np.float32(srt[:, 0] + e2)
+    assert np.array_equal(r.argmin[decided], D2.argmin(axis=1)[decided])
+    assert (D2[rows, r.argmin] - srt[:, 0]).max() <= 2 * e2
+    assert np.abs(r.d64 - D2[rows, r.argmin]).max() <= e2 and np.abs(r.d64sec - srt[:, 1]).max() <= 2 * e2
+    assert np.abs(r.key.astype(np.float64) - r.d64).max() <= np.spacing(r.key).max()
+    assert np.all(r.key <= r.key2) and np.all((r.key < r.key2) | (r.argmin < r.arg2))
+    assert np.abs(r.coarse_max - Ch.max(axis=1)).max() <= 1e-12 and np.abs(r.coarse_win - Ch[rows, r.argmin]).max() <= 1e-12
+    crowd = rows < min(n1 // 2, B[0].shape[0] // 30)
+    assert (r.key[crowd] < 1e-5).all()
+    # rows a reference summing in another order cannot decide: D^2 below the evaluation error (eps ~1e-7); these are the rows only
+    # a term-for-term restatement can judge
+    assert (~decided[crowd]).sum() >= 3 and decided.mean() > 0.7, (decided[crowd].mean(), decided.mean())
+    # the point of the split check: inside a crowd the coarse order is not the exact order
+    inv = (r.coarse_max - r.coarse_win > 1e-4) & crowd
+    assert inv.sum() >= 20, inv.sum()
+    sub = (A[1] != 0) & (np.abs(A[1].astype(np.float32)) < 2.0 ** -14)
+    assert sub.mean() > 0.1, sub.mean()
+    if tiny:                                          # near-zero entries: hi itself is subnormal in places
+        assert ((A[0] != 0) & (np.abs(A[0].astype(np.float32)) < 2.0 ** -14)).sum() > 1000
+    flushed = (A[0], np.where(sub, np.float16(0), A[1]))
+    rf = orc.match_split_f64(flushed, B, coarse=False)
+    assert (rf.key != r.key).sum() >= n1 // 4 and (rf.argmin != r.argmin).any(), ((rf.key != r.key).sum(), (rf.argmin != r.argmin).sum())
+    print(f"[split oracle tiny={tiny}] decided {int(decided.sum())}/{n1}, inversions {int(inv.sum())}, subnormal lo {sub.mean():.2f}")
