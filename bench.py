@@ -12,7 +12,9 @@ reference evaluate.py:238) -> closed-form SE(3) per match -> RRE/RTE of every hy
 Pairs are independent, so N GPUs run N disjoint pair streams (weak scaling); the only collective is the
 final all-reduce of the metric counters.  Rank 0 prints ONE JSON line.  `value` = named-path pairs/s.
 
-Beside the named-path value the line carries
+A plain run does what `value` needs: set-up, warm-up, the timed steps, `--dump-outputs` and the line (whose moment / coarse-kernel
+rooflines price HIP events taken inside the timed steps).  `--full` also runs every other leg -- the named path over resident, hard
+and ragged pairs, the stream-plan check, the f1 profiles -- and adds to the line
   * `end_to_end`: the whole loop iteration of reference evaluate.py:195-309 on the same KT pairs, timed separately --
     host keypoint draws + a1-a7 + raw-cloud prep (:260-285) + f1 hypothesis selection + f2 ICP -- with pairs/s,
     per-stage ms and the numbers the reference prints (:304-309: recall at the gates, mRRE, mRTE);
@@ -66,6 +68,9 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond `value`: resident-replay, hard-pair, ragged-pair and stream-plan legs, end-to-end legs, "
+                         "f1 profiles, CPU baseline and recall check.  The options that size those legs take effect under --full only")
     ap.add_argument("--pairs-per-step", type=int, default=64, help="registration pairs per step and GPU")
     ap.add_argument("--config", default="KT", choices=["K1", "KT", "NS", "SY"])
     ap.add_argument("--kind", default="test", choices=["test", "rot"])
@@ -140,6 +145,9 @@ def parse():
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:      # every leg after the timed steps is sized to zero: a plain run ends with the line
+        a.resident_steps = a.hard_steps = a.ragged_steps = a.plan_check_pairs = a.e2e_pairs = a.e2e_hard_pairs = 0
+        a.no_cpu_baseline = True
     return a
 
 
@@ -667,6 +675,7 @@ def main():
                    "sampler": "host numpy RNG (reference evaluate.py:238)", "distance_gemm": a.precision,
                    "pairs_in_flight": depth, "phase_a_as_hipgraph": graph_mode,
                    "distinct_pairs_in_the_pool": len(pool),
+                   "full": a.full,      # (False: every leg beyond the timed steps was skipped)
                    "value_is": ("named path a1-a7, pairs/s, over a stream of DISTINCT resident pairs, each read where it lies by ONE hipGraph "
                                 "per pipeline slot (captured at the capacity max_pc_size; a pair = a 64-byte device record + a replay): "
                                 "what a loop like evaluate.py:175 gets" if graph_mode != "none" else "named path a1-a7, pairs/s, plain launches"),

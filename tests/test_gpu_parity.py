@@ -1069,7 +1069,7 @@ def test_bench_collectives_on_rccl(gpu, tmp_path):
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
-    common = ["--config", "K1", "--warmup", "1", "--steps", "2", "--pairs-per-step", "8", "--no-cpu-baseline", "--e2e-pairs", "2",
+    common = ["--full", "--config", "K1", "--warmup", "1", "--steps", "2", "--pairs-per-step", "8", "--no-cpu-baseline", "--e2e-pairs", "2",
               "--e2e-hard-pairs", "0"]
     l2, j2, _ = _run_bench([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
                             "127.0.0.1", "--master-port", "29631", os.path.join(repo, "bench.py"), "--gpus", "1", "--dist-backend", "nccl",
@@ -1093,7 +1093,7 @@ def test_bench_two_ranks_equal_one_rank_over_the_same_pairs(gpu):
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
-    common = ["--config", "K1", "--warmup", "1", "--steps", "2", "--no-cpu-baseline", "--e2e-hard-pairs", "0", "--e2e-side-by-side", "0",
+    common = ["--full", "--config", "K1", "--warmup", "1", "--steps", "2", "--no-cpu-baseline", "--e2e-hard-pairs", "0", "--e2e-side-by-side", "0",
               "--hard-steps", "1"]           # (the named-path leg over hard pairs: its own barrier + all-reduce pair)
     l2, j2, _ = _run_bench([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                             "127.0.0.1", "--master-port", "29641", os.path.join(repo, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
@@ -1129,7 +1129,7 @@ def test_bench_four_ranks_equal_one_rank_over_the_same_pairs(gpu):
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
-    common = ["--config", "K1", "--warmup", "1", "--steps", "1", "--no-cpu-baseline", "--e2e-hard-pairs", "0", "--e2e-side-by-side", "0",
+    common = ["--full", "--config", "K1", "--warmup", "1", "--steps", "1", "--no-cpu-baseline", "--e2e-hard-pairs", "0", "--e2e-side-by-side", "0",
               "--pool", "8"]
     bad = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "4"] + common, capture_output=True, text=True,
                          timeout=300, env=dict(env, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"), cwd=repo)

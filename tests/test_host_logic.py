@@ -418,6 +418,27 @@ def test_bench_dump_outputs_fit_their_budget(tmp_path, monkeypatch):
     assert a.steps == 7 and a.dump_outputs == "d"
 
 
+def test_bench_legs_beyond_the_timed_steps_run_under_full_only(monkeypatch):
+    """A plain bench.py run sizes every leg after the timed steps to zero (each leg's own `0 = skip`), whatever its options say;
+    --full keeps the legs' defaults and the options given.  Every other option parses the same either way."""
+    import bench
+    legs = ("resident_steps", "hard_steps", "ragged_steps", "plan_check_pairs", "e2e_pairs", "e2e_hard_pairs")
+    for argv in (["--steps", "7"], ["--steps", "7", "--hard-steps", "2", "--e2e-pairs", "4", "--resident-steps", "3"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        a = bench.parse()
+        assert not a.full and a.no_cpu_baseline and all(getattr(a, k) == 0 for k in legs) and a.steps == 7
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--steps", "7"])
+    f = bench.parse()
+    assert f.full and not f.no_cpu_baseline and not f.no_e2e
+    assert [getattr(f, k) for k in legs] == [5, None, None, 96, 32, 16]        # (hard / ragged: None = by config)
+    same = lambda n: {k: v for k, v in vars(n).items() if k not in legs + ("full", "no_cpu_baseline")}     # noqa: E731
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "7"])
+    assert same(bench.parse()) == same(f)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--hard-steps", "2", "--e2e-pairs", "4", "--no-cpu-baseline"])
+    f = bench.parse()
+    assert f.hard_steps == 2 and f.e2e_pairs == 4 and f.no_cpu_baseline
+
+
 def test_ragged_synthetic_pairs_contract():
     """synth_pair / synth_pair_hard with n_src != n_tgt (what the reference's collate produces: datasets/kitti/kitti_dataset.py:568-569
     dilutes the two clouds independently; evaluate.py:195-204 draws min(10000, N_src, N_tgt) keypoints from each): sizes, keypoint rule,

@@ -17,7 +17,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 python -c "import sys; sys.path.insert(0, '$ROOT'); from umeregrobust_amd import _lib; print(_lib.load().umereg_build_source_hash().decode())" > $OUT/library_hash.txt
 echo "$CFG" > $OUT/config.txt
-if [ "$CFG" = "KT" ]; then BENCH_ARGS=""; else BENCH_ARGS="--config $CFG --no-cpu-baseline --e2e-pairs 8 --e2e-hard-pairs 4"; fi
+if [ "$CFG" = "KT" ]; then BENCH_ARGS="--full"; else BENCH_ARGS="--full --config $CFG --no-cpu-baseline --e2e-pairs 8 --e2e-hard-pairs 4"; fi
 if [ -z "$ONLY_PMC" ]; then    # (ONLY_PMC=1: the counter passes alone, for a look at a kernel between two builds)
 timeout -s KILL 1500 python $ROOT/bench.py $BENCH_ARGS --detail $OUT/bench_detail.json > $OUT/bench.log 2>&1; grep "^{" $OUT/bench.log | tail -1 > $OUT/bench.json
 timeout -s KILL 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- python $ROOT/bench.py $BENCH_ARGS --no-cpu-baseline --detail $OUT/stats_detail.json > $OUT/stats.log 2>&1

@@ -2,6 +2,7 @@
 # usage (GPU box): tools/e2e_stats.sh [extra bench args] -- rocprofv3 kernel stats of bench.py's end-to-end leg alone (plain KT pairs)
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
+set -- --full "$@"     # (the end-to-end leg is one of bench.py --full's)
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/e2eprof -o run -- python $R/bench.py --steps 1 --warmup 1 --pairs-per-step 4 --no-cpu-baseline --e2e-hard-pairs 0 --detail $R/gpurun_out/e2eprof_detail.json "$@" > $R/gpurun_out/e2eprof.log 2>&1
 f=$(ls $R/gpurun_out/e2eprof/*/run_kernel_stats.csv $R/gpurun_out/e2eprof/run_kernel_stats.csv 2>/dev/null | head -1)
 python - "$f" <<EOF
