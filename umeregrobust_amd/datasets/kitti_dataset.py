@@ -10,10 +10,11 @@ weights and a sparse-convolution backend:
     (batch index in column 0 of the coordinates);
   * the weight-file schema of reference train_coloring.py:214-222 (`evaluate.py:164` reads `['model_state_dict']`).
 
-The feature network itself (reference models.py:691-698) needs MinkowskiEngine: not installable here, so features stay
-an input.  A cache pickle may carry two extra keys, `src_feat` / `tgt_feat` [n,32] (the network's output at the cached
-points, dumped by whoever can run it); the collate function then dilutes them with the same indices and appends them
-to its return tuple, and `python -m umeregrobust_amd.evaluate --cache <dir>` runs the reference's loop from such a cache.
+A cache pickle may carry two extra keys, `src_feat` / `tgt_feat` [n,32] (the feature network's output at the cached points);
+the collate function then dilutes them with the same indices and appends them to its return tuple, and `python -m
+umeregrobust_amd.evaluate --cache <dir>` runs the reference's loop from such a cache.  Without them, `--checkpoint W.pth`
+computes the features with `umeregrobust_amd.models.ResUNetSmall2` (reference models.py:691-698) from the collate's
+coordinates.
 
 MinkowskiEngine 0.5.4 `sparse_collate` is restated from its documented behaviour (parity unpinned, like the other
 third-party boundaries); everything else is pinned by golden G10 (the reference's own collate on seeded items)."""
@@ -46,8 +47,8 @@ def read_cached_pair(path, with_features=False):
     item = tuple(d[k] for k in CACHE_KEYS)
     if with_features:
         if not all(k in d for k in FEATURE_KEYS):
-            raise KeyError(f"{path}: no `src_feat` / `tgt_feat`: the feature network (reference models.py:691-698, "
-                           "MinkowskiEngine) is not part of this library -- dump its outputs into the cache files")
+            raise KeyError(f"{path}: no `src_feat` / `tgt_feat`: compute the features with the feature network "
+                           "(evaluate --checkpoint / cached_pairs(checkpoint=...)) or dump them into the cache files")
         item = item + tuple(d[k] for k in FEATURE_KEYS)
     return item
 

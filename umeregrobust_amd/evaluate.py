@@ -860,29 +860,45 @@ def synthetic_pairs(benchmark, indices, device):
                    tgt_feat=t(p.tgt_feat)[None], gt_tform=t(p.gt_tform))
 
 
-def cached_pairs(cache, cache_raw, split, indices, args, device, rng=np.random):
+def cached_pairs(cache, cache_raw, split, indices, args, device, rng=np.random, checkpoint=None):
     """Pairs from the reference's pre-processed cache (`datasets.CachedPairDataset`) through the reference's
     collate (`batch_collate_fn_dset`, batch_size 1: the dilution to args.max_pc_size with the host RNG), as the evaluation
-    loop unpacks them (evaluate.py:175-187).  The cache files must carry the feature network's outputs (`src_feat` /
-    `tgt_feat`); the raw clouds of the correlation stage (`dset_no_nksr[itr]`, :260) come from `cache_raw` (default: the
+    loop unpacks them (evaluate.py:175-187).  Without `checkpoint` the cache files must carry the feature network's outputs
+    (`src_feat` / `tgt_feat`); with it (a weight file of the reference's save_checkpoint schema, or a state dict) the
+    features are computed from the collate's coordinates by `models.ResUNetSmall2` (evaluate.py:163-165, :178-179,
+    :190-192).  The raw clouds of the correlation stage (`dset_no_nksr[itr]`, :260) come from `cache_raw` (default: the
     same files)."""
     from .datasets import CachedPairDataset, batch_collate_fn_dset
     kind = getattr(args, "dataset", "kitti")
-    ds = CachedPairDataset(cache, split=split, with_features=True, dataset=kind)
+    net = None
+    if checkpoint is not None:
+        from .datasets import checkpoint_state_dict
+        from .models import ResUNetSmall2
+        from .sparse import SparseTensor
+        net = ResUNetSmall2(in_channels=1, out_channels=getattr(args, "out_ch", 32))
+        net.load_state_dict(checkpoint_state_dict(checkpoint))
+        net = net.to(device).eval()
+    ds = CachedPairDataset(cache, split=split, with_features=net is None, dataset=kind)
     ds_raw = CachedPairDataset(cache_raw or cache, split=split, files=ds.files, dataset=kind)
     for i in indices(len(ds)) if callable(indices) else indices:
         b = batch_collate_fn_dset([ds[i]], num_matches=args.num_samples, max_pc_size=args.max_pc_size, rng=rng)
         raw = ds_raw[i]
-        yield dict(src_pts=b[0].float().to(device), tgt_pts=b[4].float().to(device), src_feat=b[11].float().to(device),
-                   tgt_feat=b[12].float().to(device), gt_tform=b[9][0].float().to(device),
+        if net is None:
+            src_feat, tgt_feat = b[11].float().to(device), b[12].float().to(device)
+        else:
+            with torch.no_grad():
+                src_feat = torch.stack(net(SparseTensor(b[3], coordinates=b[2], device=device)).decomposed_features, dim=0)
+                tgt_feat = torch.stack(net(SparseTensor(b[7], coordinates=b[6], device=device)).decomposed_features, dim=0)
+        yield dict(src_pts=b[0].float().to(device), tgt_pts=b[4].float().to(device), src_feat=src_feat,
+                   tgt_feat=tgt_feat, gt_tform=b[9][0].float().to(device),
                    src_pts_raw=raw[0].float().to(device), tgt_pts_raw=raw[3].float().to(device))
 
 
 def main(argv=None):
     """`python -m umeregrobust_amd.evaluate --benchmark kitti_test` - the reference's command line (evaluate.py:113-124)
-    and result lines (:304-309).  Datasets and the feature network are not part of this library: pairs come
-    from --pairs files (points + features as the loader/network would hand them over) or, by default, from the synthetic
-    generator at the benchmark's shape.  Under torch.distributed.run every rank takes pairs[rank::world] and the metric
+    and result lines (:304-309).  Pairs come from the reference's pair cache (--cache; features from the cache files, or
+    computed by the feature network with --checkpoint), from --pairs files (points + features as the loader/network would
+    hand them over) or, by default, from the synthetic generator at the benchmark's shape.  Under torch.distributed.run every rank takes pairs[rank::world] and the metric
     counts are summed with one all-reduce; each rank then seeds its host RNG with seed + rank."""
     import argparse
     import glob
@@ -895,6 +911,9 @@ def main(argv=None):
     parser.add_argument("--cache", default=None, help="the reference's pair cache (<dir>/<split>/<seq>/<f0>_<f1>.pickle) with "
                                                       "`src_feat`/`tgt_feat` added: datasets.CachedPairDataset + batch_collate_fn_dset")
     parser.add_argument("--cache-raw", default=None, help="cache of the raw clouds for the correlation stage (dset_no_nksr); default: --cache")
+    parser.add_argument("--checkpoint", default=None, help="with --cache: weights of the feature network (the reference's "
+                                                           "model_checkpoint_path); features are computed by models.ResUNetSmall2 "
+                                                           "instead of read from the cache")
     parser.add_argument("--synthetic", type=int, default=8, help="number of synthetic pairs when no --pairs are given")
     parser.add_argument("--no-refine", action="store_true", help="skip the ICP refinement (evaluate.py:301)")
     cli = parser.parse_args(argv)
@@ -911,7 +930,8 @@ def main(argv=None):
     if rank == 0:
         print(f"Evaluate {args.dataset} Benchmark: {args.benchmark} config file: {config_path}")
     if cli.cache:
-        pairs = cached_pairs(cli.cache, cli.cache_raw, args.split, lambda n: shard_indices(n, rank, world), args, device, rng=rng)
+        pairs = cached_pairs(cli.cache, cli.cache_raw, args.split, lambda n: shard_indices(n, rank, world), args, device, rng=rng,
+                             checkpoint=cli.checkpoint)
     elif cli.pairs:
         files = []
         for p in cli.pairs:

@@ -1,0 +1,272 @@
+"""`ResUNetSmall2(in_channels=1, out_channels=32)` -- the reference's feature network (models.py:392-618 with the
+configuration of :691-698), forward pass only, on the HIP sparse convolution of csrc/sparse_map.hip + csrc/featnet.hip
+(C ABI: include/umereg_featnet.h).
+
+Drop-in for the reference's evaluation loop (evaluate.py:163-165, :178-179, :190-192):
+
+    model = ResUNetSmall2(in_channels=1, out_channels=32).to(device)
+    model.load_state_dict(checkpoint_state_dict(path))        # the reference's names and shapes
+    model.eval()
+    with torch.no_grad():
+        feat = torch.stack(model(SparseTensor(ones, coordinates=coords, device=device)).decomposed_features, 0)
+
+The network: channels [_, 32, 64, 64, 128, 256], transposed-conv channels [_, 64, 64, 64, 128, 128], kernel size 3,
+strides [1, 2, 2, 2, 3] (tensor strides 1, 2, 4, 8, 24), blocks conv3 -> BN -> + residual -> ReLU; encoder levels conv -> BN
+-> block -> ReLU, decoder levels transposed conv -> BN -> block -> ReLU -> cat(tr, skip); mlp1 (1x1, 96 -> 64) -> ReLU;
+final (1x1, 64 -> 32, bias); row-wise L2 normalisation without epsilon.  Eval batch norm (eps 1e-5) is folded into a
+per-channel scale and shift in fp64 before the parameters go to the device as f32.
+
+MinkowskiEngine 0.5.4 semantics restated (parity unpinned; the kernels keep each in one place, csrc/sparse.h):
+  1. strided output map: unique(floor(c / (ts s)) ts s) per axis, batch index kept;
+  2. kernel offsets {-1, 0, 1} ts_in per axis, offset index k = (dx+1) + 3(dy+1) + 9(dz+1) (x fastest);
+  3. kernel shapes [27, C_in, C_out], 1x1 kernels [C_in, C_out], bias [1, C_out];
+  4. convolution: out[o] = sum_k in[o + off_k(ts_in)] @ W[k] over the offsets that exist;
+  5. transposed convolution onto the encoder map at ts_in / s: out[f] = sum_k in[f - off_k(ts_out)] @ W[k] over the
+     f - off_k that exist in the coarse map;
+  6. output rows in input order (`decomposed_features` splits them by batch index).
+Input coordinates must be unique per batch item (a duplicate raises); x, y, z in [-2^17, 2^17), at most 127 clouds.
+
+No CPU fallback and no autograd: CPU tensors, train mode and a forward that would need gradients raise."""
+import ctypes
+
+import torch
+from torch import nn
+
+from . import _lib
+from .sparse import SparseTensor
+
+c_void_p, c_int, c_size_t = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+
+# name -> (restype, argtypes); mirrors include/umereg_featnet.h one to one
+FEATNET_SIGNATURES = {
+    "umereg_featnet_params_count": (c_size_t, []),
+    "umereg_featnet_layer_info": (c_int, [c_int, c_void_p]),
+    "umereg_featnet_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "umereg_featnet_buffer": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p]),
+    "umereg_featnet_build_maps": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "umereg_featnet_forward_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                           c_void_p]),
+}
+
+# include/umereg_featnet.h
+N_LAYERS, OUT_CHANNELS, N_STATUS, MAX_BATCH = 20, 32, 8, 127
+BUF_COORDS0, BUF_CAT0, BUF_S4, BUF_HIDDEN, BUF_PERM, BUF_MASKS = 0, 5, 9, 10, 11, 12
+ERR_RANGE, ERR_DUPLICATE = 1, 2
+
+# the packed parameter block's layer order (umereg_featnet_layer_info) -> (kernel, batch norm or None)
+LAYERS = (
+    ("conv1", "norm1"), ("block1.conv1", "block1.norm1"),
+    ("conv2", "norm2"), ("block2.conv1", "block2.norm1"),
+    ("conv3", "norm3"), ("block3.conv1", "block3.norm1"),
+    ("conv4", "norm4"), ("block4.conv1", "block4.norm1"),
+    ("conv5", "norm5"), ("block5.conv1", "block5.norm1"),
+    ("conv4_tr", "norm4_tr"), ("block4_tr.conv1", "block4_tr.norm1"),
+    ("conv3_tr", "norm3_tr"), ("block3_tr.conv1", "block3_tr.norm1"),
+    ("conv2_tr", "norm2_tr"), ("block2_tr.conv1", "block2_tr.norm1"),
+    ("conv1_tr", "norm1_tr"), ("block1_tr.conv1", "block1_tr.norm1"),
+    ("mlp1", None), ("final", None))
+
+_typed = None
+
+
+def load_native():
+    """libumereg.so with the entry points of include/umereg_featnet.h typed (raises without the built library)."""
+    global _typed
+    lib = _lib.load()
+    if _typed is not lib:
+        for name, (res, args) in FEATNET_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as e:
+                raise _lib.NativeLibraryError(f"{_lib.LIB_PATH} does not export {name}") from e
+            fn.restype, fn.argtypes = res, args
+        _typed = lib
+    return lib
+
+
+def layer_info():
+    """[(K, C_in, C_out, offset of W, offset of scale)] of the packed parameter block, from the library."""
+    lib = load_native()
+    info = (ctypes.c_int32 * 5)()
+    out = []
+    for i in range(N_LAYERS):
+        _lib.check(lib.umereg_featnet_layer_info(i, ctypes.addressof(info)), "featnet_layer_info")
+        out.append(tuple(info))
+    return out
+
+
+def workspace_bytes(n, batch):
+    return int(load_native().umereg_featnet_workspace_bytes(int(n), int(batch)))
+
+
+def buffer_view(ws, n, batch, which, rows, dtype=torch.float32):
+    """A [rows, cols] view of workspace buffer `which` (include/umereg_featnet.h, UMEREG_FN_*)."""
+    off, cols = ctypes.c_size_t(), ctypes.c_int32()
+    _lib.check(load_native().umereg_featnet_buffer(int(n), int(batch), int(which), ctypes.addressof(off), ctypes.addressof(cols)),
+               "featnet_buffer")
+    esz = torch.empty(0, dtype=dtype).element_size()
+    return ws[off.value:off.value + rows * cols.value * esz].view(dtype).view(rows, cols.value)
+
+
+def forward_raw(coords, feat, batch, params, ws, out, status):
+    """One forward pass through the C ABI on the current stream; no host sync, no error check of `status`."""
+    lib = load_native()
+    n = coords.shape[0]
+    rc = lib.umereg_featnet_forward_f32(coords.data_ptr(), feat.data_ptr(), int(n), int(batch), params.data_ptr(), out.data_ptr(),
+                                        status.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(coords.device).cuda_stream)
+    _lib.check(rc, "featnet_forward")
+
+
+def build_maps_raw(coords, batch, ws, status):
+    """The coordinate maps alone (the first half of forward_raw), on the current stream; no host sync."""
+    rc = load_native().umereg_featnet_build_maps(coords.data_ptr(), int(coords.shape[0]), int(batch), status.data_ptr(), ws.data_ptr(),
+                                                 ws.numel(), torch.cuda.current_stream(coords.device).cuda_stream)
+    _lib.check(rc, "featnet_build_maps")
+
+
+def check_status(status):
+    """Raise on the error bits of a forward pass's status (one device read); -> level sizes [5]."""
+    s = status.cpu().tolist()
+    if s[0] & ERR_DUPLICATE:
+        raise ValueError("ResUNetSmall2: duplicate coordinates in a batch item (MinkowskiEngine would merge them; "
+                         "the reference's inputs come from sparse_quantize and are unique)")
+    if s[0] & ERR_RANGE:
+        raise ValueError("ResUNetSmall2: a batch index outside [0, batch) or a coordinate outside [-2^17, 2^17)")
+    return s[1:6]
+
+
+class _Conv(nn.Module):
+    """MinkowskiConvolution(Transpose)'s parameters: `kernel` [27, C_in, C_out] (1x1: [C_in, C_out]), `bias` [1, C_out]."""
+
+    def __init__(self, cin, cout, kernel_size, bias=False):
+        super().__init__()
+        shape = (27, cin, cout) if kernel_size == 3 else (cin, cout)
+        self.kernel = nn.Parameter(torch.empty(shape))
+        self.bias = nn.Parameter(torch.zeros(1, cout)) if bias else None
+        with torch.no_grad():
+            bound = 1.0 / (cin * (27 if kernel_size == 3 else 1)) ** 0.5
+            self.kernel.uniform_(-bound, bound)
+
+
+class _Norm(nn.Module):
+    """MinkowskiBatchNorm: the parameters live in `.bn` (torch.nn.BatchNorm1d, eps 1e-5)."""
+
+    def __init__(self, c, bn_momentum=0.1):
+        super().__init__()
+        self.bn = nn.BatchNorm1d(c, momentum=bn_momentum)
+
+
+class _Block(nn.Module):
+    """BasicBlockBase2 (reference models.py:70-96): conv3 -> BN -> + residual -> ReLU."""
+
+    def __init__(self, c, bn_momentum=0.1):
+        super().__init__()
+        self.conv1 = _Conv(c, c, 3)
+        self.norm1 = _Norm(c, bn_momentum)
+
+
+class ResUNetSmall2(nn.Module):
+    CHANNELS = [None, 32, 64, 64, 128, 256]
+    TR_CHANNELS = [None, 64, 64, 64, 128, 128]
+    STRIDES = [1, 2, 2, 2, 3]
+
+    def __init__(self, in_channels=1, out_channels=32, bn_momentum=0.1, normalize_feature=True, D=3):
+        super().__init__()
+        if (in_channels, out_channels, bool(normalize_feature), D) != (1, OUT_CHANNELS, True, 3):
+            raise ValueError("the HIP network is built for in_channels=1, out_channels=32, normalize_feature=True, D=3 "
+                             "(the configuration of reference evaluate.py:163)")
+        ch, tr = self.CHANNELS, self.TR_CHANNELS
+        for i in range(1, 6):
+            setattr(self, f"conv{i}", _Conv(in_channels if i == 1 else ch[i - 1], ch[i], 3))
+            setattr(self, f"norm{i}", _Norm(ch[i], bn_momentum))
+            setattr(self, f"block{i}", _Block(ch[i], bn_momentum))
+        for i in range(4, 0, -1):
+            cin = ch[5] if i == 4 else ch[i + 1] + tr[i + 2]
+            setattr(self, f"conv{i}_tr", _Conv(cin, tr[i + 1], 3))
+            setattr(self, f"norm{i}_tr", _Norm(tr[i + 1], bn_momentum))
+            setattr(self, f"block{i}_tr", _Block(tr[i + 1], bn_momentum))
+        self.mlp1 = _Conv(tr[2] + ch[1], tr[1], 1)
+        self.final = _Conv(tr[1], out_channels, 1, bias=True)
+        self._packed_key = None
+        self._packed = None
+        self._ws = {}
+
+    # ---- parameters ------------------------------------------------------------------------------------------------------
+    def packed_parameters(self):
+        """The packed f32 parameter block of include/umereg_featnet.h on the parameters' device: kernels as they are, eval
+        batch norm folded in fp64 into scale = gamma / sqrt(var + eps), shift = beta - mean scale; cached until a parameter or
+        buffer changes."""
+        key = tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+        if key == self._packed_key:
+            return self._packed
+        info = layer_info()
+        dev = self.conv1.kernel.device
+        total = int(load_native().umereg_featnet_params_count())
+        block = torch.zeros(total, dtype=torch.float64, device=dev)
+        mods = dict(self.named_modules())
+        with torch.no_grad():
+            for (name, norm), (K, cin, cout, off_w, off_s) in zip(LAYERS, info):
+                conv = mods[name]
+                w = conv.kernel.detach().double()
+                if tuple(w.shape) != ((K, cin, cout) if K > 1 else (cin, cout)):
+                    raise ValueError(f"{name}.kernel: shape {tuple(w.shape)} != the library's {(K, cin, cout)}")
+                block[off_w:off_w + K * cin * cout] = w.reshape(-1)
+                if norm is not None:
+                    bn = mods[norm].bn
+                    scale = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
+                    shift = bn.bias.double() - bn.running_mean.double() * scale
+                else:
+                    scale = torch.ones(cout, dtype=torch.float64, device=dev)
+                    shift = conv.bias.detach().double().reshape(-1) if conv.bias is not None else torch.zeros_like(scale)
+                block[off_s:off_s + cout] = scale
+                block[off_s + cout:off_s + 2 * cout] = shift
+        self._packed = block.float().contiguous()
+        self._packed_key = key
+        return self._packed
+
+    def _workspace(self, n, batch, dev):
+        need = workspace_bytes(n, batch)
+        ws = self._ws.get(dev)
+        if ws is None or ws.numel() < need:
+            self._ws[dev] = ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        return ws
+
+    # ---- forward ---------------------------------------------------------------------------------------------------------
+    def forward(self, x, debug=False):
+        """x: SparseTensor with features [N, 1] and coordinates [N, 4] on the GPU -> SparseTensor of [N, 32] unit rows on the
+        same coordinates, rows in input order.  debug=True: (output, intermediates) with the per-level coordinates, both
+        halves of every level's concatenation, block5's output and mlp1's output (see include/umereg_featnet.h)."""
+        if self.training:
+            raise RuntimeError("ResUNetSmall2 runs forward only with eval-mode batch norm: call .eval() first")
+        F, C = x.F, x.C
+        if torch.is_grad_enabled() and (F.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise RuntimeError("ResUNetSmall2 has no backward pass: run it under torch.no_grad()")
+        if F.device.type != "cuda" or C.device.type != "cuda":
+            raise RuntimeError("ResUNetSmall2: CPU tensors given; umeregrobust_amd has no CPU fallback (move the input to the GPU)")
+        params = self.packed_parameters()
+        if params.device != F.device:
+            raise RuntimeError(f"ResUNetSmall2: parameters on {params.device}, input on {F.device}")
+        if F.shape[1] != 1:
+            raise ValueError(f"ResUNetSmall2: in_channels is 1, got features [N, {F.shape[1]}]")
+        n, batch = C.shape[0], x.batch_size
+        if n == 0:
+            raise ValueError("ResUNetSmall2: empty input")
+        if batch > MAX_BATCH:
+            raise ValueError(f"ResUNetSmall2: at most {MAX_BATCH} clouds per call, got batch index {batch - 1}")
+        coords = C.to(torch.int32).contiguous()
+        feat = F.to(torch.float32).contiguous()
+        ws = self._workspace(n, batch, F.device)
+        out = torch.empty(n, OUT_CHANNELS, dtype=torch.float32, device=F.device)
+        status = torch.empty(N_STATUS, dtype=torch.int32, device=F.device)
+        forward_raw(coords, feat, batch, params, ws, out, status)
+        sizes = check_status(status)
+        res = SparseTensor(out, coordinates=coords)
+        res._batch_size = batch
+        if not debug:
+            return res
+        inter = dict(levels=sizes, perm=buffer_view(ws, n, batch, BUF_PERM, n, torch.int32)[:, 0].clone(),
+                     hidden=buffer_view(ws, n, batch, BUF_HIDDEN, n).clone(),
+                     s4=buffer_view(ws, n, batch, BUF_S4, sizes[4]).clone())
+        inter["coords"] = [buffer_view(ws, n, batch, BUF_COORDS0 + l, sizes[l], torch.int32).clone() for l in range(5)]
+        inter["cat"] = [buffer_view(ws, n, batch, BUF_CAT0 + l, sizes[l]).clone() for l in range(4)]
+        return res, inter
