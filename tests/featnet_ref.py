@@ -12,13 +12,37 @@ TSTRIDES = (1, 2, 4, 8, 24)
 # offset index k = (dx+1) + 3(dy+1) + 9(dz+1), x fastest
 OFFSETS = np.array([(k % 3 - 1, (k // 3) % 3 - 1, k // 9 - 1) for k in range(27)], dtype=np.int64)
 _BIAS = 1 << 18
+# the device's coordinate key and hash (csrc/sparse.h: fn_key, fn_hash, fn_ws), mirrored for the tests that aim at hash slots;
+# tests/test_featnet_cpu.py pins these constants against the header
+KEY_SHIFTS = (57, 38, 19, 0)        # batch 7 bits | x, y, z 19 bits each, biased by _BIAS
+HASH_MUL = 0x9E3779B97F4A7C15
+MIN_CAP = 1024
+MAX_BATCH = 127
+COORD_LIM = 1 << 17
 
 
 def keys(c):
-    """int [n,4] (batch, x, y, z) -> int64 keys, ordered as (batch, x, y, z) lexicographically."""
-    c = np.asarray(c, dtype=np.int64)
-    w = 2 * _BIAS
-    return ((c[:, 0] * w + c[:, 1] + _BIAS) * w + c[:, 2] + _BIAS) * w + c[:, 3] + _BIAS
+    """int [n,4] (batch, x, y, z) -> uint64 keys, ordered as (batch, x, y, z) lexicographically: the device's fn_key, bit for
+    bit (batch in [0, 127], x / y / z in [-2^18, 2^18); asserted)."""
+    c = np.asarray(c, dtype=np.int64).reshape(-1, 4)
+    assert ((c[:, 0] >= 0) & (c[:, 0] < MAX_BATCH + 1)).all() and ((c[:, 1:] >= -_BIAS) & (c[:, 1:] < _BIAS)).all(), \
+        "a coordinate outside the key's range"
+    u = (c + np.array([0, _BIAS, _BIAS, _BIAS])).astype(np.uint64)
+    return (u[:, 0] << np.uint64(KEY_SHIFTS[0])) | (u[:, 1] << np.uint64(KEY_SHIFTS[1])) | (u[:, 2] << np.uint64(KEY_SHIFTS[2])) | u[:, 3]
+
+
+def table_cap(n):
+    """slots per hash table of a pass over n points (fn_ws): the smallest power of two >= max(1024, 2 n)"""
+    cap = MIN_CAP
+    while cap < 2 * n:
+        cap <<= 1
+    return cap
+
+
+def hash_slot(k, cap):
+    """fn_hash: the home slot of uint64 keys in a table of `cap` slots (the product wraps mod 2^64)"""
+    with np.errstate(over="ignore"):
+        return ((np.asarray(k, dtype=np.uint64) * np.uint64(HASH_MUL)) >> np.uint64(32)) & np.uint64(cap - 1)
 
 
 class Index:
@@ -49,6 +73,43 @@ def strided_map(c, ts_out):
     cc = coarsen(c, ts_out)
     _, first = np.unique(keys(cc), return_index=True)
     return cc[first]
+
+
+def levels(coords):
+    """the five maps of a cloud: level 0 = the input rows (in input order), level l = strided_map(level l - 1, TSTRIDES[l])"""
+    lv = [np.asarray(coords, dtype=np.int64)]
+    for l in range(1, 5):
+        lv.append(strided_map(lv[-1], TSTRIDES[l]))
+    return lv
+
+
+def cells(coords):
+    """number of locality cells of the level-0 row order: distinct (batch, floor(c / 8)) (include/umereg_featnet.h, status[6])"""
+    return len(np.unique(keys(coarsen(coords, 8))))
+
+
+# the 13 neighbour tables in the header's order (UMEREG_FN_MASKS): (query level, read level, sign of the offset); the offsets
+# are in units of the finer level's tensor stride
+TABLES = [(l, l, 1) for l in range(5)] + [(l + 1, l, 1) for l in range(4)] + [(l, l + 1, -1) for l in range(4)]
+
+
+def neighbour_masks(levels):
+    """The offset masks of the 13 neighbour tables over the five maps `levels` (each in its own row order): table l (self)
+    queries level l and reads level l at +off_k ts_l; 5 + l (strided) queries level l + 1 and reads level l at +off_k ts_l;
+    9 + l (transposed) queries level l and reads level l + 1 at -off_k ts_l.  -> 13 uint32 arrays, one word per query row,
+    bit k set exactly when a row exists at that offset (the rule of `conv`)."""
+    lv = [np.asarray(c, dtype=np.int64) for c in levels]
+    idx = [Index(c) for c in lv]
+    out = []
+    for ql, tl, sign in TABLES:
+        ts = TSTRIDES[min(ql, tl)]
+        mask = np.zeros(len(lv[ql]), dtype=np.uint32)
+        for k in range(27):
+            q = lv[ql].copy()
+            q[:, 1:] += sign * OFFSETS[k] * ts
+            mask |= (idx[tl].find(q) >= 0).astype(np.uint32) << np.uint32(k)
+        out.append(mask)
+    return out
 
 
 def conv(feat, in_coords, out_coords, W, ts, transposed=False, index=None):
@@ -82,9 +143,7 @@ def network(coords, feat, sd):
     coordinates (`coords[l]`), the concatenation [decoder block | encoder block] (`cat[l]`, l < 4), block5's output (`s4`),
     mlp1's output (`hidden`, input order)."""
     relu = lambda x: np.maximum(x, 0.0)     # noqa: E731
-    lv = [np.asarray(coords, dtype=np.int64)]
-    for l in range(1, 5):
-        lv.append(strided_map(lv[-1], TSTRIDES[l]))
+    lv = levels(coords)
     idx = [Index(c) for c in lv]
 
     def block(x, l, name):

@@ -116,6 +116,119 @@ def test_restated_network_runs_on_partial_occupancy():
     assert [x.shape[1] for x in inter["cat"]] == [96, 128, 192, 256] and inter["s4"].shape == (sizes[4], 256)
 
 
+def _dense_cube(lo, hi, batch=0):
+    g = np.stack(np.meshgrid(*[np.arange(lo, hi)] * 3, indexing="ij"), -1).reshape(-1, 3)
+    return np.concatenate([np.full((len(g), 1), batch), g], axis=1).astype(np.int64)
+
+
+def _mask_clouds():
+    rng = np.random.default_rng(11)
+    return {"sparse": _cloud(rng, 500, -60, 60, batch=2), "dense": _cloud(rng, 3000, -9, 9, batch=2),
+            "cube": _dense_cube(-12, 12), "isolated": np.array([[0, 0, 0, 0], [0, 100, 0, 0], [1, 0, 0, 0]])}
+
+
+@pytest.mark.parametrize("cloud", ["sparse", "dense", "cube", "isolated"])
+def test_neighbour_masks_follow_the_rule_of_conv(cloud):
+    """Bit k of a row's mask in every one of the 13 tables is set exactly when `conv` gathers a row at offset k: a one-hot
+    kernel per offset (W[k] = e_k) over features of ones counts each offset's neighbour."""
+    lv = ref.levels(_mask_clouds()[cloud])
+    masks = ref.neighbour_masks(lv)
+    assert len(masks) == 13 and all(m.dtype == np.uint32 for m in masks)
+    W = np.zeros((27, 1, 27))
+    W[np.arange(27), 0, np.arange(27)] = 1.0
+    for t, (ql, tl, sign) in enumerate(ref.TABLES):
+        assert len(masks[t]) == len(lv[ql])
+        hit = ref.conv(np.ones((len(lv[tl]), 1)), lv[tl], lv[ql], W, ref.TSTRIDES[min(ql, tl)], transposed=sign < 0)
+        assert set(np.unique(hit)) <= {0.0, 1.0}
+        bits = (masks[t][:, None] >> np.arange(27, dtype=np.uint32)) & 1
+        assert np.array_equal(bits, hit.astype(np.uint32)), f"table {t}"
+    if cloud == "cube":         # every offset of an interior row of the self tables hits
+        inner = (np.abs(lv[0][:, 1:] + 0.5) < 11).all(axis=1)
+        assert inner.any() and (masks[0][inner] == (1 << 27) - 1).all()
+
+
+def test_neighbour_masks_follow_the_header_order():
+    """Tables in the order of UMEREG_FN_MASKS on two points one voxel apart: self l, strided l -> l+1 (5 + l, queried on the
+    coarse map), transposed l+1 -> l (9 + l, queried on the fine map at -offset)."""
+    m = ref.neighbour_masks(ref.levels(np.array([[0, 0, 0, 0], [0, 1, 0, 0]])))
+    b = lambda *ks: sum(1 << k for k in ks)      # noqa: E731
+    assert m[0].tolist() == [b(13, 14), b(12, 13)]          # k = 13 is the row itself; k = 14 is dx = +1
+    assert m[1].tolist() == [b(13)] and m[4].tolist() == [b(13)]
+    assert m[5].tolist() == [b(13, 14)]                     # level 1's (0, 0, 0) reads level 0 at (0, 0, 0) and (1, 0, 0)
+    assert m[9].tolist() == [b(13), b(14)]                  # level 0's (1, 0, 0) reads level 1 at (1 - 1, 0, 0)
+    assert [len(x) for x in m] == [2, 1, 1, 1, 1, 1, 1, 1, 1, 2, 1, 1, 1]
+
+
+def test_keys_and_lookup_stay_exact_at_batch_and_coordinate_limits():
+    """Keys are the device's unsigned 64-bit fn_key: exact and ordered (batch, x, y, z) lexicographically up to batch 127 and
+    the coordinate limits, where a signed key would wrap from batch 64 on; a lookup never confuses batch items that differ in
+    the top bit of the batch index."""
+    lim, bias = ref.COORD_LIM, 1 << 18
+    vals = [-lim, -lim + 1, -1, 0, 1, lim - 2, lim - 1]
+    xyz = np.array(np.meshgrid(vals, vals, vals, indexing="ij")).reshape(3, -1).T
+    c = np.concatenate([np.concatenate([np.full((len(xyz), 1), b), xyz], 1) for b in (0, 1, 62, 63, 64, 65, 126, 127)])
+    c = np.concatenate([c, [[127, bias - 1, bias - 1, bias - 1], [0, -bias, -bias, -bias]]]).astype(np.int64)
+    k = ref.keys(c)
+    assert k.dtype == np.uint64
+    want = [(int(b) << 57) | ((int(x) + bias) << 38) | ((int(y) + bias) << 19) | (int(z) + bias) for b, x, y, z in c]
+    assert [int(v) for v in k] == want
+    assert int(k[c[:, 0] <= 126].max()) < (1 << 64) - 1     # never the empty slot's all-ones key up to batch 126 ...
+    assert int(k[-2]) == (1 << 64) - 1                      # ... which is why the header stops there
+    order = np.lexsort(c[:, ::-1].T)
+    assert (np.diff(k[order].astype(object)) > 0).all()     # strictly increasing in lexicographic order
+    idx = ref.Index(c[::-1])
+    assert np.array_equal(idx.find(c), np.arange(len(c))[::-1])
+    for have, other in ((63, 64), (62, 126), (64, 0), (126, 127), (1, 65)):
+        part = ref.Index(c[c[:, 0] == have])
+        q = c[c[:, 0] == have].copy()
+        q[:, 0] = other
+        assert (part.find(q) == -1).all(), (have, other)
+    with pytest.raises(AssertionError):
+        ref.keys([[128, 0, 0, 0]])
+    with pytest.raises(AssertionError):
+        ref.keys([[0, bias, 0, 0]])
+
+
+def _sparse_h():
+    return open(os.path.join(REPO, "umeregrobust_amd", "csrc", "sparse.h")).read()
+
+
+def test_key_and_hash_mirror_match_sparse_h():
+    """featnet_ref's mirror of fn_key / fn_hash / the table size (which the hash wraparound test aims with) is the header's:
+    a change of key layout, bias, multiplier or capacity rule fails here instead of quietly making that test ordinary."""
+    h = _sparse_h()
+    body = lambda name: re.search(name + r"\(.*?\n\{(.*?)\n\}", h, re.S).group(1)       # noqa: E731
+    assert int(re.search(r"kFnKeyBias = 1 << (\d+);", h).group(1)) == 18 and ref._BIAS == 1 << 18
+    assert int(re.search(r"kFnCoordLim = 1 << (\d+);", h).group(1)) == 17 and ref.COORD_LIM == 1 << 17
+    key = re.sub(r"\s+", " ", body("fn_key"))
+    packed = re.search(r"key = (.*?);", key).group(1)
+    terms = [t.strip() for t in packed.split("|")]
+    assert terms == ["((unsigned long long)b << %d)" % ref.KEY_SHIFTS[0],
+                     "((unsigned long long)(x + kFnKeyBias) << %d)" % ref.KEY_SHIFTS[1],
+                     "((unsigned long long)(y + kFnKeyBias) << %d)" % ref.KEY_SHIFTS[2],
+                     "(unsigned long long)(z + kFnKeyBias)"], terms
+    assert "x < -kFnKeyBias || x >= kFnKeyBias" in key
+    hb = re.sub(r"\s+", " ", body("fn_hash"))
+    m = re.search(r"return \(unsigned int\)\(\(key \* (0x[0-9A-Fa-f]+)ull\) >> (\d+)\) & \(cap - 1u\);", hb)
+    assert m and int(m.group(1), 16) == ref.HASH_MUL and int(m.group(2)) == 32, hb
+    ws = re.sub(r"\s+", " ", body("inline FnWs fn_ws"))
+    assert "unsigned int cap = %du; while (cap < 2u * (unsigned int)n) cap <<= 1;" % ref.MIN_CAP in ws, ws
+    assert [ref.table_cap(n) for n in (1, 512, 513, 50000, 132308)] == [1024, 1024, 2048, 131072, 524288]
+    assert re.search(r"#define UMEREG_FEATNET_MAX_BATCH (\d+)", open(os.path.join(REPO, "include", "umereg_featnet.h")).read()).group(1) \
+        == str(ref.MAX_BATCH)
+    # the mirror's arithmetic: the top 32 bits of the 64-bit product, masked (exact integers)
+    for k in (0, 1, 0x9E3779B97F4A7C15, int(ref.keys([[126, -5, 7, 131071]])[0])):
+        want = ((k * ref.HASH_MUL) % (1 << 64)) >> 32 & (2048 - 1)
+        assert int(ref.hash_slot(np.uint64(k), 2048)) == want
+
+
+def test_restated_levels_and_cells():
+    c = np.array([[0, -1, -1, -1], [0, -8, -8, -8], [0, 0, 0, 0], [0, 7, 7, 7], [3, 0, 0, 0], [0, -9, 0, 0]])
+    lv = ref.levels(c)
+    assert [len(x) for x in lv] == [6, 6, 6, 4, 4] and ref.cells(c) == 4
+    assert np.array_equal(lv[0], c) and np.array_equal(lv[4][:, 1:] % 24, np.zeros((4, 3)))
+
+
 # ---- state dict ----------------------------------------------------------------------------------------------------------
 
 def test_state_dict_names_and_shapes_match_the_reference():
