@@ -293,6 +293,9 @@ int umereg_pair_match_graph_create_ex(const float* pts, const float* feat, const
                                       float radius, float tau, float* F, int64_t* match_idx, float* match_dist, float* prob,
                                       void* workspace, size_t workspace_bytes, const umereg_match_opts* opts, void* stream,
                                       void** graph_out);
+/* Both replays below are for a graph over fixed buffers.  On a handle made by umereg_pair_match_graph_create_cap they
+ * return UMEREG_EINVAL and launch nothing (the captured kernels read their clouds through a record that only
+ * umereg_pair_match_graph_launch_ragged writes): replay a capacity graph with that entry. */
 int umereg_pair_match_graph_launch(void* graph, void* stream);
 /* Replay + the device -> host copy of the match probabilities (the operand of the host draw, evaluate.py:238; prob_host:
  * pinned host memory, n_kp floats, or NULL) in one call. */

@@ -540,7 +540,7 @@ ORC_API int orc_corr_judge_f32(const float* T, int64_t M, const float* sp, int64
 }
 
 /* --------------------------------------------------------------------------
- * a3+a4 as the "f16r" matcher's refine pass computes it (subspace_dist.hip,
+ * a3+a4 as the "f16r" matcher's refine pass computes it (match_f16r.hip,
  * match_refine_kernel), restated term for term on the split-f16 planes the
  * library itself wrote (oracle.decode_split_f16):
  *   qa[i]  [32,4]  row i's basis as the refine holds it: (double)hi + (double)lo,

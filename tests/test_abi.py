@@ -87,3 +87,31 @@ def test_corr_kernel_declarations_match_the_definitions():
     # ... and every launch in corr.hip names a declared kernel
     launched = set(re.findall(r"hipLaunchKernelGGL\(\(?(\w+)", open(os.path.join(csrc, "corr.hip")).read()))
     assert launched and launched <= set(declared), sorted(launched - set(declared))
+
+
+def test_match_kernels_are_launched_where_they_are_defined():
+    """The matcher sources are four translation units over match_dev.h: each of the eight kernels is DEFINED in exactly
+    one of them and LAUNCHED only from that unit -- no kernel is declared across units; the units call each other through the
+    public umereg_* entries.  pair_match.hip (host composition) and the shared header define none; the one kernel pair_match.hip
+    instantiates is the record writer, a template that grid.h defines and launches."""
+    csrc = os.path.join(REPO, "umeregrobust_amd", "csrc")
+    units = ("ume_dist.hip", "match_f16r.hip", "match.hip", "pair_match.hip")
+    want = {"ume_dist_kernel", "ume_dist_h_kernel", "match_finalize_kernel", "ume_coarse_h_kernel", "pform_pack_kernel",
+            "ume_coarse_p_kernel", "match_refine_kernel", "match_prob_kernel"}
+    assert not os.path.exists(os.path.join(csrc, "subspace_dist.hip"))
+    from_grid = set(_kernels_of(os.path.join(csrc, "grid.h")))
+    assert "record_write_kernel" in from_grid
+    defined = {f: _kernels_of(os.path.join(csrc, f)) for f in units}
+    every = [n for names in defined.values() for n in names]
+    assert sorted(every) == sorted(want), "a kernel is defined twice, is missing, or a new one is not listed here"
+    assert defined["pair_match.hip"] == [] and _kernels_of(os.path.join(csrc, "match_dev.h")) == []
+    assert set(defined["ume_dist.hip"]) == {"ume_dist_kernel", "ume_dist_h_kernel", "match_finalize_kernel"}
+    assert defined["match.hip"] == ["match_prob_kernel"]
+    for f in units:
+        launched = set(re.findall(r"hipLaunchKernelGGL\(\(?(\w+)", open(os.path.join(csrc, f)).read()))
+        assert launched <= set(defined[f]) | from_grid, f"{f} launches a kernel of another unit: {sorted(launched - set(defined[f]) - from_grid)}"
+        assert set(defined[f]) <= launched, f"{f} defines a kernel it never launches: {sorted(set(defined[f]) - launched)}"
+    # (no unit of the library declares one of these kernels without defining it: the definitions above are all there is)
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h")) and f not in units:
+            assert not (set(_kernels_of(os.path.join(csrc, f))) & want), f

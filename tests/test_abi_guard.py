@@ -362,6 +362,11 @@ def case_pair_match_graphs(G):
     ws, nws = G.ws(G.lib.umereg_pair_match_workspace_bytes_ex(cap_N, n, None))
     h = ctypes.c_void_p()
     G.call("umereg_pair_match_graph_create_cap", cap_N, n, K, 5.0, 0.05, F, m, d, pr, ws, nws, None, cap.cuda_stream, ctypes.byref(h))
+    # a plain replay of a capacity graph would run kernels that read a record nobody has written (here: before any ragged launch):
+    # both entries refuse on the host with UMEREG_EINVAL and name the entry to use; nothing is enqueued
+    for fn, args in (("umereg_pair_match_graph_launch", (h, G.stream)), ("umereg_pair_match_graph_launch_ex", (h, prob_h.data_ptr(), G.stream))):
+        rc, msg = getattr(G.lib, fn)(*args), G.lib.umereg_last_error().decode()
+        assert rc == -1 and "umereg_pair_match_graph_launch_ragged" in msg, f"{fn} on a capacity graph -> {rc}: {msg}"
     for tag, Ns, Nt in (("a", N, 1777), ("b", 1025, N - 1)):
         a = [G.inp(x)[0] for x in (sp[:Ns], tp[:Nt], sf[:Ns], tf[:Nt], sk % Ns, tk % Nt)]
         G.call("umereg_pair_match_graph_launch_ragged", h, *a, Ns, Nt, prob_h.data_ptr(), G.stream)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (build container): tools/exp_coarse_ablate.sh build   -> tools/libumereg_ca<mask>.so for a few masks
 #       (GPU box):         tools/exp_coarse_ablate.sh run     -> coarse-stage time of each variant on the KT pair
-# masks (UMEREG_COARSE_ABLATE in subspace_dist.hip; results are wrong by construction): 1 no squares, 2 no filter, 4 no MFMAs, 8 no LDS reads
+# masks (UMEREG_COARSE_ABLATE in match_f16r.hip; results are wrong by construction): 1 no squares, 2 no filter, 4 no MFMAs, 8 no LDS reads
 cd "$(dirname "$0")/.."
 MASKS="${MASKS:-0 1 2 3 4 6 8 11}"
 if [ "$1" = build ]; then

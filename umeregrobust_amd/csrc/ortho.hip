@@ -1,7 +1,7 @@
 // ortho.hip -- a3 first half: orthonormal basis of every 32x4 UME matrix
 // (torch.linalg.qr(...).Q at reference utils/loc_utils.py:9,11), written straight into the
-// MFMA fragment order the distance GEMM (subspace_dist.hip) consumes, so that GEMM's operand
-// loads are whole coalesced 1 KiB dwordx4 wave-loads.
+// MFMA fragment order the distance GEMM (ume_dist.hip, match_f16r.hip) consumes, so that GEMM's
+// operand loads are whole coalesced 1 KiB dwordx4 wave-loads.
 //
 // 32 lanes per matrix (lane = feature channel = matrix row), two matrices per wavefront.
 #include "householder.h"

@@ -234,15 +234,9 @@ def my_ume_generation(pts, kpts, feat, args):
 
 
 def _phase_a(src_pts, tgt_pts, src_feat, tgt_feat, args, src_inds, tgt_inds, materialize_D=False, timing=None,
-             pair=None, graph=None, match_opts=None):
-    """evaluate.py:195-236 up to the match probabilities: everything before the host RNG draw.
-    graph: an ops.PairMatchGraph built over `pair`'s buffers -- the same kernels replayed as one hipGraph launch."""
+             pair=None, match_opts=None):
+    """evaluate.py:195-236 up to the match probabilities: everything before the host RNG draw."""
     dev = src_pts.device
-    if graph is not None:
-        F, m_tgt, ume_d, prob = graph.launch()
-        return SimpleNamespace(ume_src=F[0:1], ume_tgt=F[1:2], match=m_tgt, match_d=ume_d, prob=prob, D=None,
-                               src_inds=src_inds, tgt_inds=tgt_inds, num_kpts=F.shape[1], dev=dev,
-                               src_pts=src_pts, tgt_pts=tgt_pts)
     # UME matrices (:206-212); the keypoint gathers src_pts[0, src_inds] (:201-202) are fused into the kernel
     t_mom = None if timing is None else timing.setdefault("moments", [])
     t_dist = None if timing is None else timing.setdefault("dist", ops.TimingList())
@@ -610,7 +604,7 @@ class RegistrationPipeline:
             a.keep = (pair, src_feat, tgt_feat)
             return a
         with torch.cuda.stream(st):
-            a = _phase_a(src_pts, tgt_pts, src_feat, tgt_feat, self.args, src_inds, tgt_inds, False, timing, pair, None,
+            a = _phase_a(src_pts, tgt_pts, src_feat, tgt_feat, self.args, src_inds, tgt_inds, False, timing, pair,
                          match_opts=self.match_opts)
             if a.prob is not None:
                 if self.host_prob[k] is None or self.host_prob[k].numel() != a.prob.numel():

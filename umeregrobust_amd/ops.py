@@ -879,39 +879,63 @@ def pair_match_ragged(src_pts, tgt_pts, src_feat, tgt_feat, src_kp, tgt_kp, K, r
     return F, m, d, prob
 
 
-class PairMatchCapGraph:
+class _PairGraph:
+    """What the two graph classes below share: the outputs F, m, d, prob and the workspace the captured chain writes (owned by the
+    object), the capture itself, the continuation after the host draw and the lifetime of the native handle."""
+
+    def _capture(self, dev, N, n, tau, opts, create, what):
+        """Outputs and workspace of a chain sized for clouds of N points and n keypoints, then the capture:
+        create(lib, op, capture stream, handle reference) -> return code of the native entry `what`."""
+        import ctypes
+        lib = self._lib = _lib.load()
+        self.dev, self.opts = dev, opts
+        self.F = torch.empty((2, n, 32, 4), dtype=torch.float32, device=dev)
+        self.m = torch.empty((1, n), dtype=torch.int64, device=dev)
+        self.d = torch.empty((1, n), dtype=torch.float32, device=dev)
+        self.prob = torch.empty((n,), dtype=torch.float32, device=dev) if tau is not None else None
+        op = _lib.opts_ptr(opts)
+        need = lib.umereg_pair_match_workspace_bytes_ex(N, n, op)
+        if need == 0:
+            _lib.check(-1, "umereg_pair_match_workspace_bytes_ex")
+        self.ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        handle = ctypes.c_void_p()
+        cap = torch.cuda.Stream(dev)                     # capture needs a non-default stream; nothing runs on it
+        cap.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.device(dev):
+            rc = create(lib, op, cap.cuda_stream, ctypes.byref(handle))
+        _lib.check(rc, what)
+        self.handle = handle
+
+    def solve(self, cond_host_ptr, n_cond, cond_dev, T_out, stream_ptr):
+        """evaluate.py:238-254 after the host draw, from this graph's outputs (see umereg_pair_match_graph_solve)."""
+        rc = self._lib.umereg_pair_match_graph_solve(self.handle, cond_host_ptr or None, int(n_cond), cond_dev.data_ptr() if cond_dev is not None else None,
+                                                     T_out.data_ptr(), stream_ptr)
+        if rc:
+            _lib.check(rc, "umereg_pair_match_graph_solve")
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                self._lib.umereg_pair_match_graph_destroy(self.handle)
+                self.handle = None
+        except Exception:   # noqa: BLE001  (interpreter shutdown)
+            pass
+
+
+class PairMatchCapGraph(_PairGraph):
     """a1..a5 of a registration pair captured ONCE as a hipGraph at a capacity (clouds of up to `capacity` points, `n_kp` keypoints)
     and replayed for any pair that fits: the captured kernels read the clouds through a 64-byte device record that launch() rewrites
     (umereg_pair_match_graph_create_cap / _launch_ragged).  Outputs and workspace are owned by this object: F, m, d, prob are valid
     until its next launch().  A pair's clouds must stay alive until its launch has completed."""
 
     def __init__(self, device, capacity, n_kp, K, radius, tau=None, opts=None):
-        import ctypes
-        lib = _lib.load()
-        dev = self.dev = torch.device(device)
         self.capacity, self.n_kp = int(capacity), int(n_kp)
         self.params = (int(K), float(radius), None if tau is None else float(tau), None if opts is None else opts.key())
-        self.opts = opts
-        n = self.n_kp
-        self.F = torch.empty((2, n, 32, 4), dtype=torch.float32, device=dev)
-        self.m = torch.empty((1, n), dtype=torch.int64, device=dev)
-        self.d = torch.empty((1, n), dtype=torch.float32, device=dev)
-        self.prob = torch.empty((n,), dtype=torch.float32, device=dev) if tau is not None else None
-        op = _lib.opts_ptr(opts)
-        need = lib.umereg_pair_match_workspace_bytes_ex(self.capacity, n, op)
-        if need == 0:
-            _lib.check(-1, "umereg_pair_match_workspace_bytes_ex")
-        self.ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        self._lib = lib
-        handle = ctypes.c_void_p()
-        cap = torch.cuda.Stream(dev)                     # capture needs a non-default stream; nothing runs on it
-        cap.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.device(dev):
-            rc = lib.umereg_pair_match_graph_create_cap(self.capacity, n, int(K), float(radius), float(tau) if tau is not None else 0.0,
-                                                        _ptr(self.F), _ptr(self.m), _ptr(self.d), _ptr(self.prob), _ptr(self.ws),
-                                                        self.ws.numel(), op, cap.cuda_stream, ctypes.byref(handle))
-        _lib.check(rc, "umereg_pair_match_graph_create_cap")
-        self.handle = handle
+        self._capture(torch.device(device), self.capacity, self.n_kp, tau, opts, lambda lib, op, cap, handle:
+                      lib.umereg_pair_match_graph_create_cap(self.capacity, self.n_kp, int(K), float(radius), float(tau) if tau is not None else 0.0,
+                                                             _ptr(self.F), _ptr(self.m), _ptr(self.d), _ptr(self.prob), _ptr(self.ws),
+                                                             self.ws.numel(), op, cap, handle),
+                      "umereg_pair_match_graph_create_cap")
 
     def fits(self, n_src, n_tgt, n_kp, K, radius, tau, opts=None):
         """True if a replay of this graph computes a1..a5 of a pair of these sizes with these parameters."""
@@ -933,30 +957,13 @@ class PairMatchCapGraph:
         if rc:
             _lib.check(rc, "umereg_pair_match_graph_launch_ragged")
 
-    def solve(self, cond_host_ptr, n_cond, cond_dev, T_out, stream_ptr):
-        """evaluate.py:238-254 after the host draw, from this graph's outputs (see umereg_pair_match_graph_solve)."""
-        rc = self._lib.umereg_pair_match_graph_solve(self.handle, cond_host_ptr or None, int(n_cond), cond_dev.data_ptr() if cond_dev is not None else None,
-                                                     T_out.data_ptr(), stream_ptr)
-        if rc:
-            _lib.check(rc, "umereg_pair_match_graph_solve")
 
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self._lib.umereg_pair_match_graph_destroy(self.handle)
-                self.handle = None
-        except Exception:   # noqa: BLE001  (interpreter shutdown)
-            pass
-
-
-class PairMatchGraph:
+class PairMatchGraph(_PairGraph):
     """a1..a5 of one registration pair (pair_match) captured as ONE hipGraph over fixed buffers: the inputs given here,
     and outputs / workspace owned by this object.  launch() replays it on the current stream and returns the same
     (F, match, match_d, prob) tensors every time -- valid until the next launch() of this object."""
 
     def __init__(self, pts, feat, kp_index, K, radius, tau=None, opts=None):
-        import ctypes
-        lib = _lib.load()
         self.pts = _dev(pts, "pts"); self.feat = _dev(feat, "feat"); self.kp_index = _dev(kp_index, "kp_index", torch.int64)
         for given, used, name in ((pts, self.pts, "pts"), (feat, self.feat, "feat"), (kp_index, self.kp_index, "kp_index")):
             if used.data_ptr() != given.data_ptr():
@@ -968,29 +975,14 @@ class PairMatchGraph:
                 or self.kp_index.dim() != 2 or self.kp_index.shape[0] != 2 or self.kp_index.shape[1] == 0:
             raise ValueError("PairMatchGraph: expected pts [2,N,3], feat [2,N,32], kp_index [2,n_kp]")
         N, n = self.pts.shape[1], self.kp_index.shape[1]
-        dev = self.pts.device
-        self.dev = dev
         # what the captured kernels were recorded against: replaying the graph for anything else would silently compute
         # from the old buffers / parameters (see `matches`)
-        self.opts = opts
         self.signature = self.signature_of(self.pts, self.feat, self.kp_index, K, radius, tau, opts)
-        self.F = torch.empty((2, n, 32, 4), dtype=torch.float32, device=dev)
-        self.m = torch.empty((1, n), dtype=torch.int64, device=dev)
-        self.d = torch.empty((1, n), dtype=torch.float32, device=dev)
-        self.prob = torch.empty((n,), dtype=torch.float32, device=dev) if tau is not None else None
-        op = _lib.opts_ptr(opts)
-        self.ws = torch.empty(lib.umereg_pair_match_workspace_bytes_ex(N, n, op), dtype=torch.uint8, device=dev)
-        self._lib = lib
-        handle = ctypes.c_void_p()
-        cap = torch.cuda.Stream(dev)                     # capture needs a non-default stream; nothing runs on it
-        cap.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.device(dev):
-            rc = lib.umereg_pair_match_graph_create_ex(_ptr(self.pts), _ptr(self.feat), _ptr(self.kp_index), N, n, int(K), float(radius),
-                                                       float(tau) if tau is not None else 0.0, _ptr(self.F), _ptr(self.m), _ptr(self.d),
-                                                       _ptr(self.prob), _ptr(self.ws), self.ws.numel(), op, cap.cuda_stream,
-                                                       ctypes.byref(handle))
-        _lib.check(rc, "umereg_pair_match_graph_create_ex")
-        self.handle = handle
+        self._capture(self.pts.device, N, n, tau, opts, lambda lib, op, cap, handle:
+                      lib.umereg_pair_match_graph_create_ex(_ptr(self.pts), _ptr(self.feat), _ptr(self.kp_index), N, n, int(K), float(radius),
+                                                            float(tau) if tau is not None else 0.0, _ptr(self.F), _ptr(self.m), _ptr(self.d),
+                                                            _ptr(self.prob), _ptr(self.ws), self.ws.numel(), op, cap, handle),
+                      "umereg_pair_match_graph_create_ex")
 
     @staticmethod
     def signature_of(pts, feat, kp_index, K, radius, tau, opts=None):
@@ -1027,18 +1019,3 @@ class PairMatchGraph:
                                                            prob_host_ptr or None, stream_ptr)
         if rc:
             _lib.check(rc, "umereg_pair_match_graph_launch_from")
-
-    def solve(self, cond_host_ptr, n_cond, cond_dev, T_out, stream_ptr):
-        """evaluate.py:238-254 after the host draw, from this graph's outputs (see umereg_pair_match_graph_solve)."""
-        rc = self._lib.umereg_pair_match_graph_solve(self.handle, cond_host_ptr or None, int(n_cond), cond_dev.data_ptr() if cond_dev is not None else None,
-                                                     T_out.data_ptr(), stream_ptr)
-        if rc:
-            _lib.check(rc, "umereg_pair_match_graph_solve")
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                self._lib.umereg_pair_match_graph_destroy(self.handle)
-                self.handle = None
-        except Exception:   # noqa: BLE001  (interpreter shutdown)
-            pass
