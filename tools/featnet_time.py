@@ -9,6 +9,17 @@
     its rows (conv1 and `final` run on the VALU and are left out of both counts).
 
     python tools/featnet_time.py [--config KT|NS] [--iters 50] [--warmup 10]
+
+`--train`: the trainable network (ResUNetSmall2(trainable=True), train mode) at the same cloud, or with `--batch B` at B such
+clouds in one call (16 KITTI-test clouds are 800 000 rows, the upper end of the reference's training shape: batch 8 x
+max_pc_size 100 000).  One JSON line with ms per call of the fused eval forward (re-measured here, same session), the layer-
+wise forward, forward + backward and their difference, the useful flops of the weight gradients (the forward's useful pairs:
+the same products) and, with `--stats-csv`, the split of a profiled run into kernel groups:
+
+    rocprofv3 --kernel-trace --stats -d DIR -o train -- python tools/featnet_time.py --train --profile-steps 5 [--batch B]
+    python tools/featnet_time.py --train [--batch B] --stats-csv DIR/train_kernel_stats.csv >> profiles/featnet/featnet_time.jsonl
+
+(`--profile-steps N`: N forward + backward passes and nothing else, no timing: the run to put under the profiler.)
 """
 import argparse
 import json
@@ -65,8 +76,111 @@ def flop_counts(masks, levels, info):
     return useful, issued
 
 
+# kernel groups of a profiled training run (rocprofv3 kernel_stats.csv, by kernel name)
+GROUPS = (("conv_forward_and_input_gradient", ("fn_conv_kernel", "fn_conv1_kernel")),
+          ("weight_gradient", ("wg_mfma_kernel", "wg_c1_kernel", "wg_reduce_kernel")),
+          ("repack", ("wg_repack_kernel",)))
+
+
+def kernel_groups(path, steps):
+    """rocprofv3 kernel_stats.csv of `steps` forward + backward passes -> ms per pass by kernel group (anything that is not
+    one of the library's kernels is a torch op)"""
+    import csv
+    ms = {g: 0.0 for g, _ in GROUPS}
+    ms["maps"] = ms["torch_ops"] = 0.0          # (maps: every other kernel of the library)
+    top = []
+    for row in csv.DictReader(open(path)):
+        t = float(row["TotalDurationNs"]) / 1e6 / steps
+        for g, keys in GROUPS:
+            if "umereg::" in row["Name"] and any(k in row["Name"] for k in keys):
+                ms[g] += t
+                break
+        else:
+            ms["torch_ops" if "umereg::" not in row["Name"] else "maps"] += t
+        top.append((t, row["Name"][:60]))
+    return {k: round(v, 4) for k, v in ms.items()}, [f"{t:.3f} ms {nm}" for t, nm in sorted(top, reverse=True)[:4]]
+
+
+def train_mode(a, dev):
+    from umeregrobust_amd.sparse import SparseTensor
+    clouds = []
+    for b in range(a.batch):
+        c = voxel_cloud(a.seed + b, a.config)
+        c[:, 0] = b
+        clouds.append(c)
+    coords = torch.from_numpy(np.concatenate(clouds)).to(dev)
+    n = coords.shape[0]
+    torch.manual_seed(a.seed)
+    m = models.ResUNetSmall2(in_channels=1, out_channels=32, trainable=True).to(dev)
+    st = SparseTensor(torch.ones(n, 1, device=dev), coordinates=coords)
+    st._batch_size = a.batch
+    G = torch.randn(n, 32, device=dev)
+
+    def fused():
+        with torch.no_grad():
+            m(st)
+
+    def forward():
+        return m(st).F
+
+    def step():
+        m.zero_grad(set_to_none=True)
+        (forward() * G).sum().backward()
+
+    if a.profile_steps:
+        m.train()
+        for _ in range(a.profile_steps):
+            step()
+        torch.cuda.synchronize()
+        return
+
+    def timed(fn):
+        for _ in range(a.warmup):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(a.iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / a.iters
+
+    m.eval()
+    ms_fused = timed(fused)
+    m.train()
+    ms_fwd = timed(forward)
+    ms_step = timed(step)
+    # useful flops of the weight gradients = those of the forward's 27-offset layers: one product per (pair, C_in, C_out)
+    ws = torch.empty(models.workspace_bytes(n, a.batch), dtype=torch.uint8, device=dev)
+    status = torch.empty(models.N_STATUS, dtype=torch.int32, device=dev)
+    models.build_maps_raw(coords, a.batch, ws, status)
+    levels = models.check_status(status)
+    masks = models.buffer_view(ws, n, a.batch, models.BUF_MASKS, n, torch.int32)
+    masks = masks.reshape(-1)[:13 * n].cpu().numpy().view(np.uint32).reshape(13, n)
+    useful, _ = flop_counts(masks, levels, models.layer_info())
+    wgrad_flop = float(sum(u for (mp, _), u in zip(LAYER_MAPS, useful) if mp is not None))
+    line = dict(tool="featnet_time", mode="train", config=a.config, batch=a.batch, n=n, levels=levels, iters=a.iters,
+                ms_per_call=dict(fused_eval_forward=round(ms_fused, 4), layerwise_forward=round(ms_fwd, 4),
+                                 forward_backward=round(ms_step, 4), backward=round(ms_step - ms_fwd, 4)),
+                wgrad_useful_gflop=round(wgrad_flop / 1e9, 3))
+    if a.stats_csv:
+        groups, top = kernel_groups(a.stats_csv, a.stats_steps)
+        line["profiled_ms_per_pass"] = groups
+        line["profiled_top_kernels"] = top
+        wg = groups["weight_gradient"]
+        line["wgrad_useful_tflops"] = round(wgrad_flop / (wg * 1e-3) / 1e12, 2)
+        line["wgrad_frac_fp32_matrix_peak"] = round(wgrad_flop / (wg * 1e-3) / PEAK_FP32_MATRIX, 4)
+    print(json.dumps(line))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--train", action="store_true", help="time the trainable network's forward and backward")
+    ap.add_argument("--batch", type=int, default=1, help="--train: clouds per call")
+    ap.add_argument("--profile-steps", type=int, default=0, help="--train: run N forward + backward passes only (for the profiler)")
+    ap.add_argument("--stats-csv", default=None, help="--train: rocprofv3 kernel_stats.csv of a --profile-steps run to fold in")
+    ap.add_argument("--stats-steps", type=int, default=5, help="--train: the --profile-steps of that run")
     ap.add_argument("--config", default="KT", choices=["KT", "NS"])
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
@@ -74,6 +188,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     assert torch.cuda.is_available(), "featnet_time measures on the GPU"
     dev = torch.device("cuda:0")
+    if a.train:
+        return train_mode(a, dev)
     torch.manual_seed(a.seed)
     m = models.ResUNetSmall2(in_channels=1, out_channels=32)
     with torch.no_grad():

@@ -8,9 +8,14 @@
 // atomics.  The epilogue applies the folded eval batch norm (scale, shift), the block's residual and ReLU, and writes at a
 // column offset of a wider row, so ME.cat(tr, skip) is where the two producers write: no copy.  conv1 (C_in = 1) and the
 // `final` 1x1 layer with its L2 normalisation have their own small kernels; mlp1 is the generic kernel with K = 1.
+//
+// The single-layer entries of include/umereg_sparse_conv.h that launch these kernels live here too (a kernel is launched only
+// from the unit that defines it): the plain convolution over one table (fn_conv_kernel with the caller's scale / shift block,
+// no ReLU, the residual input used only to accumulate channel slices into the output) and conv1's forward.  The training path's own kernels are in sparse_wgrad.hip.
 #include <math.h>
 
 #include "sparse.h"
+#include "umereg_sparse_conv.h"
 
 namespace umereg {
 
@@ -351,5 +356,62 @@ UMEREG_API int umereg_featnet_forward_f32(const int32_t* coords, const float* fe
     hipLaunchKernelGGL(fn_final_kernel, dim3((n + 255) / 256), dim3(256), 0, st, X, perm, status + 1, params + f.po.w[19],
                        params + f.po.scale[19], params + f.po.scale[19] + 32, out);
     UMEREG_CHECK_LAUNCH("fn_final_kernel");
+    return UMEREG_OK;
+}
+
+// ---- include/umereg_sparse_conv.h: the entries that launch this unit's kernels ---------------------------------------------------
+
+UMEREG_API int umereg_sparse_conv_f32(const void* workspace, size_t workspace_bytes, const int32_t* status, int n, int table,
+                                      const float* in, int ld_in, const float* W, int c_in, int c_out, const float* scale,
+                                      const float* shift, float* out, int ld_out, int accumulate, void* stream)
+{
+    UMEREG_REQUIRE(workspace && status && in && W && scale && shift && out, "sparse_conv: null pointer");
+    UMEREG_REQUIRE(n > 0, "sparse_conv: n must be positive (got %d)", n);
+    UMEREG_REQUIRE(table >= 0 && table < UMEREG_SPARSE_CONV_TABLES, "sparse_conv: table %d outside [0, %d)", table, UMEREG_SPARSE_CONV_TABLES);
+    UMEREG_REQUIRE(c_in > 0 && c_in % 32 == 0 && c_in <= UMEREG_SPARSE_CONV_MAX_CH && c_out > 0 && c_out % 32 == 0 &&
+                       c_out <= UMEREG_SPARSE_CONV_MAX_CH,
+                   "sparse_conv: channels %d -> %d must be multiples of 32 up to %d", c_in, c_out, UMEREG_SPARSE_CONV_MAX_CH);
+    UMEREG_REQUIRE(ld_in >= c_in && ld_in % 4 == 0 && ld_out >= c_out, "sparse_conv: bad leading dimensions %d / %d", ld_in, ld_out);
+    UMEREG_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)W & 15) == 0, "sparse_conv: in and W must be 16-byte aligned");
+    if (int rc = check_device()) return rc;
+    const FnWs w = fn_ws(n);
+    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) {
+        set_error("sparse_conv: workspace too small or not 256-byte aligned (%zu < %zu)", workspace_bytes, w.total);
+        return UMEREG_EWORKSPACE;
+    }
+    const char* ws = (const char*)workspace;
+    ConvArgs a;
+    a.in = in, a.W = W, a.scale = scale, a.shift = shift, a.res = accumulate ? out : nullptr, a.out = out;   // (res == out: each
+                                                                                                             // element is read, then written, by one thread)
+    a.nbr = reinterpret_cast<const int*>(ws + w.off_nbr) + (size_t)table * w.n * kFnVol;
+    a.mask = reinterpret_cast<const unsigned int*>(ws + w.off_mask) + (size_t)table * w.n;
+    a.n_out = status + 1 + fn_map_out_level(table);
+    a.ld_in = ld_in, a.ld_res = ld_out, a.ld_out = ld_out, a.cin = c_in, a.cout = c_out, a.K = kFnVol, a.relu = 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (c_out % 64 == 0) {
+        hipLaunchKernelGGL((fn_conv_kernel<64, 64>), dim3((n + 63) / 64, c_out / 64), dim3(256), 0, st, a);
+    } else {
+        hipLaunchKernelGGL((fn_conv_kernel<128, 32>), dim3((n + 127) / 128, c_out / 32), dim3(256), 0, st, a);
+    }
+    UMEREG_CHECK_LAUNCH("fn_conv_kernel");
+    return UMEREG_OK;
+}
+
+UMEREG_API int umereg_sparse_conv1_f32(const void* workspace, size_t workspace_bytes, const int32_t* status, int n, const float* feat,
+                                       const float* W, const float* scale, const float* shift, float* out, void* stream)
+{
+    UMEREG_REQUIRE(workspace && status && feat && W && scale && shift && out, "sparse_conv1: null pointer");
+    UMEREG_REQUIRE(n > 0, "sparse_conv1: n must be positive (got %d)", n);
+    if (int rc = check_device()) return rc;
+    const FnWs w = fn_ws(n);
+    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) {
+        set_error("sparse_conv1: workspace too small or not 256-byte aligned (%zu < %zu)", workspace_bytes, w.total);
+        return UMEREG_EWORKSPACE;
+    }
+    const char* ws = (const char*)workspace;
+    hipLaunchKernelGGL(fn_conv1_kernel, dim3((n + 7) / 8), dim3(256), 0, (hipStream_t)stream, feat,
+                       reinterpret_cast<const int*>(ws + w.off_perm), reinterpret_cast<const int*>(ws + w.off_nbr), status + 1, W, scale,
+                       shift, out);
+    UMEREG_CHECK_LAUNCH("fn_conv1_kernel");
     return UMEREG_OK;
 }

@@ -28,6 +28,8 @@ __host__ __device__ constexpr int fn_tstride(int l) { return l == 0 ? 1 : l == 1
 __host__ __device__ constexpr int fn_map_self(int l) { return l; }
 __host__ __device__ constexpr int fn_map_down(int l) { return kFnLevels + l; }
 __host__ __device__ constexpr int fn_map_up(int l) { return kFnLevels + 4 + l; }
+// the level whose rows a map's table has one row for (its outputs)
+__host__ __device__ constexpr int fn_map_out_level(int m) { return m < kFnLevels ? m : m < kFnLevels + 4 ? m - kFnLevels + 1 : m - kFnLevels - 4; }
 
 // THE kernel-offset table (assumed to be MinkowskiEngine's hypercube order): k = (dx+1) + 3(dy+1) + 9(dz+1)
 __host__ __device__ inline void fn_offset(int k, int& dx, int& dy, int& dz)

@@ -1,6 +1,7 @@
 """`ResUNetSmall2(in_channels=1, out_channels=32)` -- the reference's feature network (models.py:392-618 with the
-configuration of :691-698), forward pass only, on the HIP sparse convolution of csrc/sparse_map.hip + csrc/featnet.hip
-(C ABI: include/umereg_featnet.h).
+configuration of :691-698) on the HIP sparse convolution of csrc/sparse_map.hip + csrc/featnet.hip (C ABI:
+include/umereg_featnet.h): one fused forward call in eval mode, and with `trainable=True` a layer-wise differentiable
+path over csrc/sparse_wgrad.hip (include/umereg_sparse_conv.h, umeregrobust_amd/sparse_conv.py).
 
 Drop-in for the reference's evaluation loop (evaluate.py:163-165, :178-179, :190-192):
 
@@ -26,7 +27,14 @@ MinkowskiEngine 0.5.4 semantics restated (parity unpinned; the kernels
   6. output rows in input order (`decomposed_features` splits them by batch index).
 Input coordinates must be unique per batch item (a duplicate raises); x, y, z in [-2^17, 2^17), at most 127 clouds.
 
-No CPU fallback and no autograd: CPU tensors, train mode and a forward that would need gradients raise."""
+No CPU fallback: CPU tensors raise.  By default (`trainable=False`) there is no autograd either: train mode and a forward
+that would need gradients raise.
+
+`ResUNetSmall2(..., trainable=True)` (reference train_coloring.py:33-73): in train mode, and in eval mode whenever gradients
+are needed, the forward runs layer by layer -- every 27-offset convolution is `sparse_conv.sparse_conv` (HIP forward, HIP
+input and weight gradients), batch norm is the model's own `nn.BatchNorm1d` modules (batch statistics over all rows of the
+call and running-stat updates in train mode, running statistics in eval mode), residual / ReLU / concatenation / the two
+1x1 layers / the L2 normalisation are torch ops.  Eval mode under `torch.no_grad()` stays the fused call, bit for bit."""
 import ctypes
 
 import torch
@@ -170,8 +178,9 @@ class ResUNetSmall2(nn.Module):
     TR_CHANNELS = [None, 64, 64, 64, 128, 128]
     STRIDES = [1, 2, 2, 2, 3]
 
-    def __init__(self, in_channels=1, out_channels=32, bn_momentum=0.1, normalize_feature=True, D=3):
+    def __init__(self, in_channels=1, out_channels=32, bn_momentum=0.1, normalize_feature=True, D=3, trainable=False):
         super().__init__()
+        self.trainable = bool(trainable)
         if (in_channels, out_channels, bool(normalize_feature), D) != (1, OUT_CHANNELS, True, 3):
             raise ValueError("the HIP network is built for in_channels=1, out_channels=32, normalize_feature=True, D=3 "
                              "(the configuration of reference evaluate.py:163)")
@@ -236,13 +245,18 @@ class ResUNetSmall2(nn.Module):
         """x: SparseTensor with features [N, 1] and coordinates [N, 4] on the GPU -> SparseTensor of [N, 32] unit rows on the
         same coordinates, rows in input order.  debug=True: (output, intermediates) with the per-level coordinates, both
         halves of every level's concatenation, block5's output and mlp1's output (see include/umereg_featnet.h)."""
-        if self.training:
-            raise RuntimeError("ResUNetSmall2 runs forward only with eval-mode batch norm: call .eval() first")
         F, C = x.F, x.C
-        if torch.is_grad_enabled() and (F.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise RuntimeError("ResUNetSmall2 has no backward pass: run it under torch.no_grad()")
+        needs_grad = torch.is_grad_enabled() and (F.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if not self.trainable:
+            if self.training:
+                raise RuntimeError("ResUNetSmall2 runs forward only with eval-mode batch norm: call .eval() first "
+                                   "(or build it with trainable=True)")
+            if needs_grad:
+                raise RuntimeError("ResUNetSmall2 has no backward pass: run it under torch.no_grad() (or build it with trainable=True)")
         if F.device.type != "cuda" or C.device.type != "cuda":
             raise RuntimeError("ResUNetSmall2: CPU tensors given; umeregrobust_amd has no CPU fallback (move the input to the GPU)")
+        if self.training or needs_grad:
+            return self._forward_layers(x, debug)
         params = self.packed_parameters()
         if params.device != F.device:
             raise RuntimeError(f"ResUNetSmall2: parameters on {params.device}, input on {F.device}")
@@ -269,4 +283,59 @@ class ResUNetSmall2(nn.Module):
                      s4=buffer_view(ws, n, batch, BUF_S4, sizes[4]).clone())
         inter["coords"] = [buffer_view(ws, n, batch, BUF_COORDS0 + l, sizes[l], torch.int32).clone() for l in range(5)]
         inter["cat"] = [buffer_view(ws, n, batch, BUF_CAT0 + l, sizes[l]).clone() for l in range(4)]
+        return res, inter
+
+    def _forward_layers(self, x, debug):
+        """The trainable path: the same network layer by layer (see the module docstring).  Rows travel in the level-0 order of
+        the coordinate maps between the first and the last layer."""
+        from . import sparse_conv as sc
+        F, C = x.F, x.C
+        if F.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError("ResUNetSmall2: the input features require grad, and conv1 has no input gradient "
+                               "(the reference's input features are ones); detach them")
+        dev = self.conv1.kernel.device
+        if dev != F.device:
+            raise RuntimeError(f"ResUNetSmall2: parameters on {dev}, input on {F.device}")
+        if F.shape[1] != 1:
+            raise ValueError(f"ResUNetSmall2: in_channels is 1, got features [N, {F.shape[1]}]")
+        n, batch = C.shape[0], x.batch_size
+        if n == 0:
+            raise ValueError("ResUNetSmall2: empty input")
+        if batch > MAX_BATCH:
+            raise ValueError(f"ResUNetSmall2: at most {MAX_BATCH} clouds per call, got batch index {batch - 1}")
+        maps = sc.CoordinateMaps(C, batch)
+        sizes = maps.sizes
+        if self.training:
+            for l, rows in enumerate(sizes):
+                if rows == 1:
+                    raise ValueError(f"ResUNetSmall2: level {l} of this input has a single row, and train-mode batch norm needs "
+                                     "more than one value per channel (use a larger cloud or .eval())")
+        relu = torch.relu
+
+        def block(h, l, blk):
+            return relu(blk.norm1.bn(sc.sparse_conv(h, blk.conv1.kernel, maps, l)) + h)
+
+        skips = []
+        h = F.detach().to(torch.float32)
+        for l in range(5):
+            conv, norm, blk = getattr(self, f"conv{l + 1}"), getattr(self, f"norm{l + 1}"), getattr(self, f"block{l + 1}")
+            h = block(norm.bn(sc.sparse_conv(h, conv.kernel, maps, 0 if l == 0 else 5 + l - 1)), l, blk)
+            skips.append(h)
+        s4 = h
+        cats = [None] * 4
+        for l in range(3, -1, -1):
+            conv, norm, blk = getattr(self, f"conv{l + 1}_tr"), getattr(self, f"norm{l + 1}_tr"), getattr(self, f"block{l + 1}_tr")
+            tr = block(norm.bn(sc.sparse_conv(h, conv.kernel, maps, 9 + l)), l, blk)
+            h = cats[l] = torch.cat([tr, skips[l]], dim=1)
+        hidden = relu(sc.linear(h, self.mlp1.kernel))
+        o = sc.linear(hidden, self.final.kernel) + self.final.bias
+        o = o / o.norm(dim=1, keepdim=True)
+        inv = torch.empty_like(maps.perm)
+        inv[maps.perm] = torch.arange(n, device=dev)
+        res = SparseTensor(o.index_select(0, inv), coordinates=maps.coords)
+        res._batch_size = batch
+        if not debug:
+            return res
+        inter = dict(levels=sizes, perm=maps.perm32.clone(), hidden=hidden.detach(), s4=s4.detach(),
+                     coords=[maps.level_coords(l).clone() for l in range(5)], cat=[c.detach() for c in cats])
         return res, inter

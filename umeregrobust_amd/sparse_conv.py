@@ -1,0 +1,283 @@
+"""Sparse 3-D convolution as a differentiable torch op, on the HIP operators of include/umereg_sparse_conv.h: what
+`ResUNetSmall2(trainable=True)` is made of.
+
+    maps = CoordinateMaps(coords, batch)              # once per coordinate set: every level, all 13 neighbour tables
+    y = sparse_conv(x, kernel, maps, table)           # out[o] = sum_k x[nbr_table(o, k)] @ kernel[k]
+
+Tables (include/umereg_featnet.h): self map of level l = l, strided l -> l+1 = 5 + l, transposed l+1 -> l = 9 + l.  Rows of
+every level are in the library's own order; `maps.perm[j]` is the input row of level-0 row j.
+
+Backward: the input gradient is the same convolution kernel over the ADJOINT table with the kernel's slices transposed
+(self l: the same table with the offsets mirrored, k -> 26 - k; strided 5 + l <-> transposed 9 + l, same k), skipped when
+the input needs no gradient; the weight gradient dW[k] = sum_o x[nbr(o, k)]^T dY[o] is the library's deterministic
+segmented MFMA kernel.  Everything runs on the current stream and nothing waits for the device."""
+import ctypes
+
+import torch
+
+from . import _lib
+from . import models as _models
+
+c_void_p, c_int, c_size_t = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+
+# name -> (restype, argtypes); mirrors include/umereg_sparse_conv.h one to one
+SPARSE_CONV_SIGNATURES = {
+    "umereg_sparse_conv_f32": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
+                                       c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "umereg_sparse_conv1_f32": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "umereg_sparse_conv_repack_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "umereg_sparse_conv_wgrad_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "umereg_sparse_conv_wgrad_segments": (c_int, [c_int, c_int, c_int]),
+    "umereg_sparse_conv_wgrad_f32": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
+                                             c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
+N_TABLES, MAX_CH = 13, 256
+# input channels per launch of the plain convolution: a longer contraction runs as slices accumulated in order (two-level
+# summation; one chain over 27 x 256 products carries about twice the rounding error of eight chains over 27 x 32)
+SLICE = 32
+
+_typed = None
+
+
+def load_native():
+    """libumereg.so with the entry points of include/umereg_sparse_conv.h typed (raises without the built library)."""
+    global _typed
+    lib = _models.load_native()
+    if _typed is not lib:
+        for name, (res, args) in SPARSE_CONV_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as e:
+                raise _lib.NativeLibraryError(f"{_lib.LIB_PATH} does not export {name}") from e
+            fn.restype, fn.argtypes = res, args
+        _typed = lib
+    return lib
+
+
+def out_level(table):
+    """the level whose rows table `table` has one row for"""
+    return table if table < 5 else table - 4 if table < 9 else table - 9
+
+
+def in_level(table):
+    """the level whose rows table `table`'s entries index"""
+    return table if table < 5 else table - 5 if table < 9 else table - 8
+
+
+def adjoint(table):
+    """(table, mirror) of the adjoint convolution: <conv_t(x; W), y> = <x, conv_t'(y; repack(W, mirror))>"""
+    if table < 5:
+        return table, True
+    return (table + 4, False) if table < 9 else (table - 4, False)
+
+
+def _stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+class CoordinateMaps:
+    """The five levels and 13 neighbour tables of one coordinate set (int32 [n, 4]: batch index, x, y, z; on the GPU), built
+    once with umereg_featnet_build_maps.  Owns the workspace the tables live in -- keep it alive until the backward pass is
+    over (the autograd graph of `sparse_conv` does).  `sizes`: rows of the five levels, read once from the device (the one
+    host sync; duplicate or out-of-range coordinates raise here); `perm`: int64 [n], the input row of level-0 row j."""
+
+    def __init__(self, coords, batch):
+        if coords.device.type != "cuda":
+            raise RuntimeError("CoordinateMaps: CPU tensors given; umeregrobust_amd has no CPU fallback (move the input to the GPU)")
+        load_native()
+        self.coords = coords.to(torch.int32).contiguous()
+        self.n, self.batch, self.device = int(coords.shape[0]), int(batch), coords.device
+        if self.n == 0:
+            raise ValueError("CoordinateMaps: empty input")
+        if self.batch > _models.MAX_BATCH:
+            raise ValueError(f"CoordinateMaps: at most {_models.MAX_BATCH} clouds per call, got batch index {self.batch - 1}")
+        self.ws = torch.empty(_models.workspace_bytes(self.n, self.batch), dtype=torch.uint8, device=self.device)
+        self.status = torch.empty(_models.N_STATUS, dtype=torch.int32, device=self.device)
+        _models.build_maps_raw(self.coords, self.batch, self.ws, self.status)
+        self.sizes = _models.check_status(self.status)
+        self.perm32 = _models.buffer_view(self.ws, self.n, self.batch, _models.BUF_PERM, self.n, torch.int32)[:, 0]
+        self.perm = self.perm32.long()
+        # the plain convolution's epilogue: acc * 1 + 0 (exact)
+        self.ones = torch.ones(MAX_CH, dtype=torch.float32, device=self.device)
+        self.zeros = torch.zeros(MAX_CH, dtype=torch.float32, device=self.device)
+        self._scratch = None
+
+    def level_coords(self, l):
+        return _models.buffer_view(self.ws, self.n, self.batch, _models.BUF_COORDS0 + l, self.sizes[l], torch.int32)
+
+    def scratch(self, nbytes):
+        """weight-gradient scratch, grown on demand (one stream: the kernels of successive layers run in order)"""
+        if self._scratch is None or self._scratch.numel() < nbytes:
+            self._scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._scratch
+
+
+def _rows(t, what):
+    if t.device.type != "cuda":
+        raise RuntimeError(f"sparse_conv: {what} on the CPU; umeregrobust_amd has no CPU fallback")
+    if t.dtype != torch.float32 or t.dim() != 2:
+        raise ValueError(f"sparse_conv: {what} must be f32 [rows, channels], got {t.dtype} {tuple(t.shape)}")
+    if t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < t.shape[1] or t.data_ptr() % 16:
+        t = t.contiguous()
+    return t
+
+
+def conv_raw(x, kernel, maps, table, transpose=False, mirror=False):
+    """out[o] = sum_k x[nbr_table(o, k)] @ M[k], M = kernel, or with `transpose` M[k'] = kernel[k]^T (k' = 26 - k if `mirror`):
+    x f32 [rows of in_level(table), C] -> [rows of out_level(table), C']; kernel [27, C, C'] ([27, C', C] with `transpose`)"""
+    lib = load_native()
+    x = _rows(x, "input")
+    K, cin, cout = kernel.shape
+    if transpose:
+        cin, cout = cout, cin
+    rows_in, rows_out = maps.sizes[in_level(table)], maps.sizes[out_level(table)]
+    if x.shape != (rows_in, cin):
+        raise ValueError(f"sparse_conv: table {table} reads [{rows_in}, {cin}] rows, got {tuple(x.shape)}")
+    out = torch.empty(rows_out, cout, dtype=torch.float32, device=x.device)
+    step = SLICE if cin > SLICE and cin % SLICE == 0 else cin
+    if transpose or step < cin:
+        kernel = repack_raw(kernel, transpose, mirror, step)        # [cin / step] blocks [27, step, cout]
+    else:
+        kernel = kernel.contiguous()
+    for s in range(cin // step):
+        _lib.check(lib.umereg_sparse_conv_f32(maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, table,
+                                              x.data_ptr() + 4 * s * step, x.stride(0), kernel.data_ptr() + 4 * s * 27 * step * cout, step,
+                                              cout, maps.ones.data_ptr(), maps.zeros.data_ptr(), out.data_ptr(), cout, int(s > 0),
+                                              _stream(x.device)), "sparse_conv")
+    return out
+
+
+def conv1_raw(feat, kernel, maps):
+    """conv1: feat f32 [n, 1] in INPUT row order, kernel [27, 1, 32] -> [rows of level 0, 32] in level-0 order"""
+    lib = load_native()
+    feat = feat.contiguous()
+    if feat.shape != (maps.n, 1) or tuple(kernel.shape) != (27, 1, 32):
+        raise ValueError(f"sparse_conv1: features [{maps.n}, 1] and a [27, 1, 32] kernel, got {tuple(feat.shape)} / {tuple(kernel.shape)}")
+    out = torch.empty(maps.n, 32, dtype=torch.float32, device=feat.device)
+    kernel = kernel.contiguous()
+    _lib.check(lib.umereg_sparse_conv1_f32(maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, feat.data_ptr(),
+                                           kernel.data_ptr(), maps.ones.data_ptr(), maps.zeros.data_ptr(), out.data_ptr(),
+                                           _stream(feat.device)), "sparse_conv1")
+    return out
+
+
+def repack_raw(kernel, transpose, mirror, slice):
+    """[27, C_in, C_out] -> R / slice blocks [27, slice, C] of M (M[k'] = kernel[k]^T if `transpose` else kernel[k]; R, C its rows
+    and columns; k' = 26 - k if `mirror`), as one flat tensor (include/umereg_sparse_conv.h)"""
+    lib = load_native()
+    K, cin, cout = kernel.shape
+    kernel = kernel.contiguous()
+    out = torch.empty(K * cin * cout, dtype=torch.float32, device=kernel.device)
+    _lib.check(lib.umereg_sparse_conv_repack_f32(kernel.data_ptr(), cin, cout, int(bool(transpose)), int(bool(mirror)), int(slice),
+                                                 out.data_ptr(), _stream(kernel.device)), "sparse_conv_repack")
+    return out
+
+
+def wgrad_raw(x, dy, maps, table):
+    """dW [27, C_in, C_out] = sum_o x[nbr_table(o, k)]^T dy[o]; x [rows of in_level(table), C_in] (C_in = 1 included)"""
+    lib = load_native()
+    dy = _rows(dy, "output gradient")
+    if x.shape[1] == 1:
+        x = x.contiguous()
+    else:
+        x = _rows(x, "input")
+    cin, cout = x.shape[1], dy.shape[1]
+    if x.shape[0] != maps.sizes[in_level(table)] or dy.shape[0] != maps.sizes[out_level(table)]:
+        raise ValueError(f"sparse_conv_wgrad: table {table}: {x.shape[0]} input rows / {dy.shape[0]} gradient rows")
+    need = int(lib.umereg_sparse_conv_wgrad_scratch_bytes(maps.n, cin, cout))
+    if need == 0:
+        raise ValueError(f"sparse_conv_wgrad: channels {cin} -> {cout} not supported")
+    scratch = maps.scratch(need)
+    dw = torch.empty(27, cin, cout, dtype=torch.float32, device=x.device)
+    _lib.check(lib.umereg_sparse_conv_wgrad_f32(maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, table, x.data_ptr(),
+                                                x.stride(0), cin, dy.data_ptr(), dy.stride(0), cout, dw.data_ptr(), scratch.data_ptr(),
+                                                scratch.numel(), _stream(x.device)), "sparse_conv_wgrad")
+    return dw
+
+
+class _SparseConv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, kernel, maps, table):
+        ctx.maps, ctx.table = maps, table
+        ctx.save_for_backward(x, kernel)
+        return conv_raw(x, kernel.detach(), maps, table)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, kernel = ctx.saved_tensors
+        maps, table = ctx.maps, ctx.table
+        dy = dy.contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            adj, mirror = adjoint(table)
+            dx = conv_raw(dy, kernel.detach(), maps, adj, transpose=True, mirror=mirror)
+        if ctx.needs_input_grad[1]:
+            dw = wgrad_raw(x, dy, maps, table)
+        return dx, dw, None, None
+
+
+class _SparseConv1(torch.autograd.Function):
+    """conv1 (C_in = 1): features in input row order; no input gradient (the reference's input features are ones)."""
+
+    @staticmethod
+    def forward(ctx, feat, kernel, maps):
+        ctx.maps = maps
+        ctx.save_for_backward(feat, kernel)
+        return conv1_raw(feat, kernel.detach(), maps)
+
+    @staticmethod
+    def backward(ctx, dy):
+        feat, _ = ctx.saved_tensors
+        dw = wgrad_raw(feat.index_select(0, ctx.maps.perm), dy.contiguous(), ctx.maps, 0) if ctx.needs_input_grad[1] else None
+        return None, dw, None
+
+
+def sparse_conv(x, kernel, maps, table):
+    """Differentiable sparse convolution over table `table` of `maps`.  x: f32 [rows of the table's input level, C_in] in the
+    level's row order -- for a [27, 1, 32] kernel (conv1, table 0): [n, 1] in INPUT row order, and it may not require grad;
+    kernel: [27, C_in, C_out].  -> f32 [rows of the table's output level, C_out]."""
+    if not 0 <= table < N_TABLES:
+        raise ValueError(f"sparse_conv: table {table} outside [0, {N_TABLES})")
+    if x.device.type != "cuda" or kernel.device.type != "cuda":
+        raise RuntimeError("sparse_conv: CPU tensors given; umeregrobust_amd has no CPU fallback (move the input to the GPU)")
+    if kernel.dim() != 3 or kernel.shape[0] != 27:
+        raise ValueError(f"sparse_conv: kernel must be [27, C_in, C_out], got {tuple(kernel.shape)}")
+    if kernel.shape[1] == 1:
+        if table != 0:
+            raise ValueError("sparse_conv: a C_in = 1 kernel runs over table 0 only (conv1)")
+        if x.requires_grad:
+            raise RuntimeError("sparse_conv: conv1 has no input gradient (the network's input features are constants); "
+                               "detach the input features")
+        return _SparseConv1.apply(x, kernel, maps)
+    return _SparseConv.apply(x, kernel, maps, table)
+
+
+class _Linear(torch.autograd.Function):
+    """x @ W for the 1x1 layers.  torch's own matmul, except that the weight gradient x^T dy -- a contraction over all rows --
+    is summed in blocks of ROWS rows and then over the blocks: one chain over 10^5 rows would carry several times the rounding
+    error of every other gradient of the network."""
+    ROWS = 256
+
+    @staticmethod
+    def forward(ctx, x, W):
+        ctx.save_for_backward(x, W)
+        return x @ W
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, W = ctx.saved_tensors
+        dx = dy @ W.t() if ctx.needs_input_grad[0] else None
+        dw = None
+        if ctx.needs_input_grad[1]:
+            n, r = x.shape[0], _Linear.ROWS
+            pad = (-n) % r
+            xp = torch.nn.functional.pad(x, (0, 0, 0, pad)).view(-1, r, x.shape[1])
+            dp = torch.nn.functional.pad(dy, (0, 0, 0, pad)).view(-1, r, dy.shape[1])
+            dw = torch.bmm(xp.transpose(1, 2), dp).sum(dim=0)
+        return dx, dw
+
+
+def linear(x, W):
+    """x [rows, C_in] @ W [C_in, C_out] with a block-summed weight gradient (the 1x1 layers of the network)"""
+    return _Linear.apply(x, W)
