@@ -8,9 +8,6 @@
 
 namespace umereg {
 
-int launch_orthobasis_pair(const float* ume1, int n1, int layout1, float* Q1, const float* ume2, int n2, int layout2,
-                           float* Q2, hipStream_t st);
-
 // a5: a = exp((1 - d)/tau); prob = a / sum(a)   (evaluate.py:235-236), one workgroup
 __global__ __launch_bounds__(1024) void match_prob_kernel(const float* __restrict__ d, int n, float tau,
                                                           float* __restrict__ prob)
@@ -73,18 +70,30 @@ UMEREG_API int umereg_ume_match_reset_f16(void* scratch, size_t scratch_bytes, i
         set_error("ume_match_reset_f16: scratch too small or misaligned (%zu < %zu)", scratch_bytes, (size_t)n1 * sizeof(unsigned int));
         return UMEREG_EWORKSPACE;
     }
+#if defined(UMEREG_COARSE_KEEP_LIMITS) && UMEREG_COARSE_KEEP_LIMITS
+    // timing experiment (tools/exp_coarse_skip.py on a replayed pair): the coarse pass starts from the limits the previous pass over
+    // the SAME pair left behind -- what any publishing schedule can at best approach.  Wrong for any other use.
+    return UMEREG_OK;
+#endif
     // the per-row limits start at 0; everything else in the scratch is written before it is read
     return launch_zero(scratch, (size_t)n1 * sizeof(unsigned int), 1, 0, (hipStream_t)stream);
 }
 
-UMEREG_API int umereg_ume_match_q_f16r_ex(const void* Q1_rows_h, const void* Q2_cols_h, int n1, int n2,
-                                          int64_t* match_idx, float* match_dist, void* scratch, size_t scratch_bytes,
-                                          const umereg_match_opts* opts, void* stream)
+// order1 / order2: the slot order the bases were written in (MatchScratch, match_dev.h); the coarse pass works on slots and needs none
+static int match_q_f16r(const void* Q1_rows_h, const void* Q2_cols_h, int n1, int n2, int64_t* match_idx, float* match_dist,
+                        void* scratch, size_t scratch_bytes, const umereg_match_opts* opts, const int* order1, const int* order2,
+                        void* stream)
 {
     UMEREG_REQUIRE(match_idx, "ume_match_q_f16r: null match_idx");
     if (int rc = umereg_ume_match_reset_f16(scratch, scratch_bytes, n1, n2, stream)) return rc;
     if (int rc = umereg_ume_match_coarse_f16_ex(Q1_rows_h, Q2_cols_h, n1, n2, scratch, scratch_bytes, opts, stream)) return rc;
-    return umereg_ume_match_refine_f16_ex(Q1_rows_h, Q2_cols_h, n1, n2, scratch, scratch_bytes, match_idx, match_dist, opts, stream);
+    return match_refine_f16(Q1_rows_h, Q2_cols_h, n1, n2, scratch, scratch_bytes, match_idx, match_dist, opts, order1, order2, stream);
+}
+UMEREG_API int umereg_ume_match_q_f16r_ex(const void* Q1_rows_h, const void* Q2_cols_h, int n1, int n2,
+                                          int64_t* match_idx, float* match_dist, void* scratch, size_t scratch_bytes,
+                                          const umereg_match_opts* opts, void* stream)
+{
+    return match_q_f16r(Q1_rows_h, Q2_cols_h, n1, n2, match_idx, match_dist, scratch, scratch_bytes, opts, nullptr, nullptr, stream);
 }
 UMEREG_API int umereg_ume_match_q_f16r(const void* Q1_rows_h, const void* Q2_cols_h, int n1, int n2,
                                        int64_t* match_idx, float* match_dist, void* scratch, size_t scratch_bytes,
@@ -96,12 +105,13 @@ UMEREG_API int umereg_ume_match_q_f16r(const void* Q1_rows_h, const void* Q2_col
 static int dist_common(const float* ume1, const float* ume2, int B, int n1, int n2, float* D,
                        int64_t* match_idx, float* match_dist, void* workspace, size_t workspace_bytes,
                        size_t need, void* stream, const char* who, bool f16x2 = false, bool refine = false,
-                       const umereg_match_opts* opts = nullptr)
+                       const umereg_match_opts* opts = nullptr, const int* order1 = nullptr, const int* order2 = nullptr)
 {
     MatchOpts mo;
     if (int rc = resolve_opts(opts, mo, who)) return rc;
     UMEREG_REQUIRE(ume1 && ume2, "%s: null UME pointer", who);
     UMEREG_REQUIRE(B > 0 && n1 > 0 && n2 > 0, "%s: B, n1, n2 must be positive (got %d, %d, %d)", who, B, n1, n2);
+    UMEREG_REQUIRE((!order1 && !order2) || (order1 && order2 && refine && B == 1), "%s: a slot order needs both sets, f16r and B = 1", who);
     UMEREG_REQUIRE(((uintptr_t)ume1 & 15) == 0 && ((uintptr_t)ume2 & 15) == 0, "%s: UME pointers must be 16-byte aligned", who);
     if (int rc = check_device()) return rc;
     if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)) {
@@ -115,11 +125,11 @@ static int dist_common(const float* ume1, const float* ume2, int B, int n1, int 
     for (int b = 0; b < B; ++b) {
         if (int rc = launch_orthobasis_pair(ume1 + (size_t)b * n1 * 128, n1, f16x2 ? UMEREG_QLAYOUT_ROWS_F16X2 : UMEREG_QLAYOUT_ROWS, QA,
                                             ume2 + (size_t)b * n2 * 128, n2, f16x2 ? UMEREG_QLAYOUT_COLS_F16X2 : UMEREG_QLAYOUT_COLS, QB,
-                                            st)) return rc;
+                                            st, order1, order2)) return rc;
         float* Db = D ? D + (size_t)b * n1 * n2 : nullptr;
         int64_t* mi = match_idx ? match_idx + (size_t)b * n1 : nullptr;
         float* md = match_dist ? match_dist + (size_t)b * n1 : nullptr;
-        const int rc = refine  ? umereg_ume_match_q_f16r_ex(QA, QB, n1, n2, mi, md, keys, match_scratch_bytes(n1, n2, mo), opts, stream)
+        const int rc = refine  ? match_q_f16r(QA, QB, n1, n2, mi, md, keys, match_scratch_bytes(n1, n2, mo), opts, order1, order2, stream)
                        : f16x2 ? umereg_ume_dist_q_f16x2(QA, QB, n1, n2, Db, mi, md, match_idx ? keys : nullptr, stream)
                                : umereg_ume_dist_q_f32(QA, QB, n1, n2, Db, mi, md, match_idx ? keys : nullptr, stream);
         if (rc) return rc;
@@ -172,6 +182,14 @@ UMEREG_API int umereg_ume_match_f16r_ex(const float* ume1, const float* ume2, in
     if (int rc = resolve_opts(opts, mo, "ume_match_f16r")) return rc;
     return dist_common(ume1, ume2, B, n1, n2, nullptr, match_idx, match_dist, workspace, workspace_bytes,
                        umereg_ume_match_workspace_bytes_ex(B, n1, n2, opts), stream, "ume_match_f16r", true, true, opts);
+}
+int umereg::match_f16r_ordered(const float* ume1, const float* ume2, int n1, int n2, const int* order1, const int* order2,
+                               int64_t* match_idx, float* match_dist, void* workspace, size_t workspace_bytes,
+                               const umereg_match_opts* opts, void* stream)
+{
+    UMEREG_REQUIRE(match_idx, "ume_match_f16r: null match_idx");
+    return dist_common(ume1, ume2, 1, n1, n2, nullptr, match_idx, match_dist, workspace, workspace_bytes,
+                       umereg_ume_match_workspace_bytes_ex(1, n1, n2, opts), stream, "ume_match_f16r", true, true, opts, order1, order2);
 }
 UMEREG_API int umereg_ume_match_f16r(const float* ume1, const float* ume2, int B, int n1, int n2,
                                      int64_t* match_idx, float* match_dist, void* workspace,

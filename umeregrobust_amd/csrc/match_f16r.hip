@@ -32,6 +32,18 @@ namespace umereg {
 // atomics, nothing the tile loop has to wait for.  A region that overflows (hundreds of exact duplicates
 // among the targets) makes the refine kernel re-scan that block of rows exhaustively.
 constexpr float kCoarseMargin = 0.03125f + 0.0009765625f;   // 2 delta + slack
+// EARLY EXIT.  s~ = sum_b |Qi~^T q~jb|^2 is accumulated column by column of the target basis, and each term is bounded by
+// |Qi~|_2^2 |q~jb|^2 with Qi~, q~jb the hi planes: |hi - q| <= 2^-11 |q| entry by entry, so a unit column keeps a norm <= 1 + 2^-11 and
+// |Qi~|_2 <= |Qi|_2 + |Qi~ - Qi|_F <= 1 + 2 * 2^-11.  A term is therefore <= (1 + 2^-10)^2 (1 + 2^-11)^2 < 1.00294, and the fp32
+// accumulation of its 32 + 4 terms adds < 1e-5: after m columns  s~ <= s~_partial(m) + (4 - m) c  with any c >= 1.00295.  c is that
+// rounded up to 1 + 2^-8; the 9.5e-4 to spare per column also cover the rounding of the test itself, which is evaluated as
+// (s~_partial - lim) >= -(4 - m) c in fp32.  A tile whose every (row, target) fails that test can append nothing (s~ >= lim fails) and
+// can raise no limit (s~ - margin < lim): it is dropped, filter() included, and everything the proof above rests on still holds.
+// The test only bites when rows that sit together share their good targets and meet one early -- the slot order of qlayout.h.
+constexpr float kCoarseTermMax = 1.00390625f;
+#ifndef UMEREG_COARSE_EXIT
+#define UMEREG_COARSE_EXIT 3   // bit 0: test after column 0, bit 1: after columns 0-1, bit 2: column 1's MFMAs are issued before the first test
+#endif
 
 // all-reduce (max) over aligned groups of 32 lanes: DPP inside rows of 16, one swizzle across the two rows
 __device__ __forceinline__ float group32_max(float v)
@@ -50,27 +62,32 @@ __device__ __forceinline__ float group32_max(float v)
 // stage.  The tile body is software-pipelined by hand in units of "groups" (one basis column b x two A
 // tiles = 4 MFMAs): the squares of group k run in the shadow of the MFMAs of group k+1.
 #ifndef UMEREG_COARSE_ABLATE
-#define UMEREG_COARSE_ABLATE 0   // timing experiments only (tools/exp_coarse_ablate.sh; results are wrong by construction): 1 no squares, 2 no filter, 4 no MFMAs, 8 no LDS reads
+#define UMEREG_COARSE_ABLATE 0   // timing experiments only (tools/exp_coarse_ablate.sh; results are wrong by construction): 1 no squares, 2 no filter, 4 no MFMAs, 8 no LDS reads, 16 every tile stops at the first test (the floor of the early exit)
 #endif
 #ifndef UMEREG_COARSE_TPS
-#define UMEREG_COARSE_TPS 1   // (2: 140-146 us against 138-147, 4: 162 -- round-3 measurement: the barrier is not the bound either)
+#define UMEREG_COARSE_TPS 2   // round 7, with the early exit: 2 against 1 -- the same kernel time, fewer candidates (profiles/r07/coarse_skip.txt); before: (2: 140-146 us against 138-147, 4: 162 -- round-3 measurement: the barrier is not the bound either)
 #endif
 constexpr int kCoarseTPS = UMEREG_COARSE_TPS;        // target tiles staged (and consumed) per workgroup barrier
 
 // Workgroup = 4 waves x kCoarseRows source keypoints (stationary A tiles, hi planes only); every 32-target
 // tile (8 KiB of hi fragments) is staged once per workgroup through a double-buffered LDS stage, two
-// further tiles are in flight in registers.
+// further tiles are in flight in registers.  A wave leaves a tile after one or two of its four column groups when the partial
+// scores prove that nothing in it can reach a limit (kCoarseTermMax); the workgroup's barrier then waits for the waves that stay.
 __global__ __launch_bounds__(kWave* kDistWaves, 2) void ume_coarse_h_kernel(
-    const half8* __restrict__ Afrag, const half8* __restrict__ Bfrag, int n1, int n2, int n_ablk, int n_btiles,
-    int tiles_per_split, MatchScratch ms)
+    const half8* __restrict__ Afrag, const half8* __restrict__ Bfrag, int n1, int n2, int n_ablk, int tile_lo, int tile_mid, int tile_hi,
+    int lead_tps, int lead_splits, int tiles_per_split, int sp0, MatchScratch ms)
 {
+    // this launch: the target tiles [tile_lo, tile_mid) in lead_splits runs of lead_tps, then [tile_mid, tile_hi) in runs of
+    // tiles_per_split; the candidate regions of the splits sp0, sp0 + 1, ... (CoarsePlan, match_dev.h)
     __shared__ half8 ldsB[2][kCoarseTPS * 512];             // 2 x (kCoarseTPS x 8 KiB): hi planes of kCoarseTPS 32-target tiles per barrier
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = lane_id();
     const int ablk = blockIdx.x % n_ablk;
-    const int sp = blockIdx.x / n_ablk;
-    const int jt0 = sp * tiles_per_split;
-    const int jt1 = min(jt0 + tiles_per_split, n_btiles);
+    const int spl = blockIdx.x / n_ablk;
+    const int sp = sp0 + spl;
+    const bool lead = spl < lead_splits;
+    const int jt0 = lead ? tile_lo + spl * lead_tps : tile_mid + (spl - lead_splits) * tiles_per_split;
+    const int jt1 = lead ? min(jt0 + lead_tps, tile_mid) : min(jt0 + tiles_per_split, tile_hi);
     const int h = lane >> 5;
     const int i_base = ablk * kCoarseWG + wave * kCoarseRows;
 
@@ -93,7 +110,8 @@ __global__ __launch_bounds__(kWave* kDistWaves, 2) void ume_coarse_h_kernel(
         for (int g = 0; g < 4; ++g) {
             const int i = i_base + t * 8 + 2 * g + h;
             seen[t][g] = __hip_atomic_load(ms.rowlim + min(i, n1 - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            lim[t][g] = __float_as_int(i < n1 ? 1.0e-30f : 3.0e38f);
+            // what the splits before this one have published (the subsample's, in slot order) holds from the first tile on
+            lim[t][g] = i < n1 ? max(__float_as_int(1.0e-30f), (int)seen[t][g]) : __float_as_int(3.0e38f);
         }
 #pragma unroll
     for (int t = 0; t < kCoarseTA; ++t)
@@ -161,6 +179,26 @@ __global__ __launch_bounds__(kWave* kDistWaves, 2) void ume_coarse_h_kernel(
     // (a limit that is one tile staler is still "some coarse score of that row - margin", the proof obligation is untouched):
     // 168 us against 143 -- the scheduling fences and the eight score registers carried across the tile cost more than the
     // shadow returns.  The variant is gone from the source (round 4); the measurement stays in DESIGN 3.3.
+    // the sharing points are a property of the tile count, whether a tile ran to its end or not
+    auto share_point = [&](const int jt) __attribute__((always_inline)) {
+        const int kt = jt - jt0;
+        if ((ms.share_mask >> (kt < 31 ? kt : 31)) & 1u) {
+            if (kt < 31 || (kt & 31) == 31) share(true);
+        }
+    };
+#if UMEREG_COARSE_STATS
+    unsigned int n_stop1 = 0, n_stop2 = 0;
+#endif
+    // true: after `cols` columns no (row, target) of this wave's tile can still reach its limit (see kCoarseTermMax)
+    auto hopeless = [&](const float (&sc)[kCoarseTA][4], const int cols) __attribute__((always_inline)) {
+        float d = sc[0][0] - __int_as_float(lim[0][0]);
+#pragma unroll
+        for (int t = 0; t < kCoarseTA; ++t)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) d = fmaxf(d, sc[t][g] - __int_as_float(lim[t][g]));
+        const bool stop = __builtin_amdgcn_ballot_w64(!(d < -(float)(4 - cols) * kCoarseTermMax)) == 0ull;
+        return (UMEREG_COARSE_ABLATE & 16) ? true : stop;
+    };
     auto filter = [&](const int jt, const float (&sc)[kCoarseTA][4]) __attribute__((always_inline)) {
         if (UMEREG_COARSE_ABLATE & 2) {
             // no limits, no ballots, no candidates: the scores are folded into one register that is stored once at the end
@@ -174,10 +212,7 @@ __global__ __launch_bounds__(kWave* kDistWaves, 2) void ume_coarse_h_kernel(
         for (int t = 0; t < kCoarseTA; ++t)
 #pragma unroll
             for (int g = 0; g < 4; ++g) lim[t][g] = max(lim[t][g], __float_as_int(sc[t][g] - kCoarseMargin));
-        const int kt = jt - jt0;
-        if ((ms.share_mask >> (kt < 31 ? kt : 31)) & 1u) {
-            if (kt < 31 || (kt & 31) == 31) share(true);
-        }
+        share_point(jt);
         unsigned long long hit[kCoarseTA][4], any = 0;
 #pragma unroll
         for (int t = 0; t < kCoarseTA; ++t)
@@ -187,7 +222,8 @@ __global__ __launch_bounds__(kWave* kDistWaves, 2) void ume_coarse_h_kernel(
                 any |= hit[t][g];
             }
         if (__builtin_popcountll(any) > 8) {
-            // a crowd of lanes hits at once: neighbouring targets are similar (spatially ordered keypoints) and
+            // a crowd of lanes hits at once: neighbouring targets are similar (the pair chain hands the targets over in cell
+            // order, qlayout.h; a caller of the layered entries may have sorted them too) and
             // each lane only knows its own column's history.  Pool the limits of the 32 columns first, so that
             // only scores within the margin of this tile's row maximum remain.
 #pragma unroll
@@ -222,11 +258,10 @@ __global__ __launch_bounds__(kWave* kDistWaves, 2) void ume_coarse_h_kernel(
     auto tile = [&](const int jt, const int q) __attribute__((always_inline)) {
         const half8* const lB = &ldsB[cur][q * 512];
         float sc[kCoarseTA][4];    // coarse scores of this lane's 4*TA (source, target) pairs
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
+        // one group: the 2 * kCoarseTA MFMAs of basis column b ...
+        auto products = [&](const int b, f32x16 (&cc)[kCoarseTA]) __attribute__((always_inline)) {
             const half8 b0 = (UMEREG_COARSE_ABLATE & 8) ? a[0][0] : lB[(b * 2 + 0) * 64 + lane];
             const half8 b1 = (UMEREG_COARSE_ABLATE & 8) ? a[0][1] : lB[(b * 2 + 1) * 64 + lane];
-            f32x16 cc[kCoarseTA];
             if (UMEREG_COARSE_ABLATE & 4) {
 #pragma unroll
                 for (int t = 0; t < kCoarseTA; ++t)
@@ -238,6 +273,9 @@ __global__ __launch_bounds__(kWave* kDistWaves, 2) void ume_coarse_h_kernel(
 #pragma unroll
                 for (int t = 0; t < kCoarseTA; ++t) cc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[t][1], b1, cc[t], 0, 0, 0);
             }
+        };
+        // ... and its squares
+        auto squares = [&](const int b, const f32x16 (&cc)[kCoarseTA]) __attribute__((always_inline)) {
 #pragma unroll
             for (int t = 0; t < kCoarseTA; ++t)
 #pragma unroll
@@ -252,6 +290,34 @@ __global__ __launch_bounds__(kWave* kDistWaves, 2) void ume_coarse_h_kernel(
                     acc = fmaf(cc[t][4 * g + 2], cc[t][4 * g + 2], acc);
                     sc[t][g] = fmaf(cc[t][4 * g + 3], cc[t][4 * g + 3], acc);
                 }
+        };
+        constexpr bool kTest1 = (UMEREG_COARSE_EXIT & 1) && !(UMEREG_COARSE_ABLATE & 15), kTest2 = (UMEREG_COARSE_EXIT & 2) && !(UMEREG_COARSE_ABLATE & 15);
+        constexpr bool kAhead = (UMEREG_COARSE_EXIT & 4) != 0;   // column 1's MFMAs in flight while column 0 is squared and tested
+        f32x16 c0[kCoarseTA], c1[kCoarseTA];
+        products(0, c0);
+        if (kAhead || !kTest1) products(1, c1);
+        squares(0, c0);
+        if (kTest1 && hopeless(sc, 1)) {
+#if UMEREG_COARSE_STATS
+            ++n_stop1;
+#endif
+            share_point(jt);
+            return;
+        }
+        if (!kAhead && kTest1) products(1, c1);
+        squares(1, c1);
+        if (kTest2 && hopeless(sc, 2)) {
+#if UMEREG_COARSE_STATS
+            ++n_stop2;
+#endif
+            share_point(jt);
+            return;
+        }
+#pragma unroll
+        for (int b = 2; b < 4; ++b) {
+            f32x16 cc[kCoarseTA];
+            products(b, cc);
+            squares(b, cc);
         }
         filter(jt, sc);
     };
@@ -268,6 +334,14 @@ __global__ __launch_bounds__(kWave* kDistWaves, 2) void ume_coarse_h_kernel(
     // publish what this split learned for the workgroups that start later
     share(false);
     if (lane == 0) ms.cnt[(size_t)blk * ms.splits + sp] = (unsigned int)qn;
+#if UMEREG_COARSE_STATS
+    if (lane == 0) {
+        atomicAdd(ms.stats + 0, (unsigned long long)max(jt1 - jt0, 0));
+        atomicAdd(ms.stats + 1, (unsigned long long)n_stop1);
+        atomicAdd(ms.stats + 2, (unsigned long long)n_stop2);
+        atomicAdd(ms.stats + 3, (unsigned long long)qn);
+    }
+#endif
 }
 
 // ---- P-form coarse filter ---------------------------------------------------------------------------------------------
@@ -550,6 +624,8 @@ __global__ __launch_bounds__(kWave* kPWaves, 2) void ume_coarse_p_kernel(const h
 // refine: one workgroup per block of kCoarseRows source rows (= one wave of the coarse kernel), one
 // thread per candidate.  d2 = 4 - sum_ab (Qi[:,a] . Qj[:,b])^2 in fp64 from hi+lo; per-row arg-min through
 // an LDS atomicMin on (bits(float(d2)) << 32 | j): lowest index among candidates whose d2 agree to fp32.
+// Rows and candidates are SLOTS of the basis buffers; with a slot order (ms.ord1 / ms.ord2, qlayout.h) j in the key and the row
+// that is written are the keypoints behind the slots, so the tie rule and the outputs are those of the identity order.
 constexpr int kQiStride = 130;   // doubles per row in LDS: 128 + 2 (rows land on different banks)
 
 template <int kRows, int kCap>   // rows per block = rows per wave of the coarse kernel that filled the regions; region capacity
@@ -642,15 +718,18 @@ __global__ __launch_bounds__(256, 4) void match_refine_kernel(const _Float16* __
 #pragma unroll
             for (int b = 0; b < 4; ++b) s = fma(dot[a][b], dot[a][b], s);
         const float d2 = (float)fmax(4.0 - s, 0.0);
-        if (d2 == d2 && (int)(i0 + r) < n1)   // NaN scores never win
-            atomicMin(&best[r], ((unsigned long long)__float_as_uint(d2) << 32) | j);
+        if (d2 == d2 && (int)(i0 + r) < n1) {   // NaN scores never win
+            const unsigned int jk = ms.ord2 ? (unsigned int)ms.ord2[target_slot_pos((int)j, n2)] : j;
+            atomicMin(&best[r], ((unsigned long long)__float_as_uint(d2) << 32) | jk);
+        }
     }
     __syncthreads();
     if (tid < kCoarseRows && i0 + tid < n1) {
         const unsigned long long k = best[tid];
         const bool ok = k != ~0ull;   // all-NaN rows: report target 0 at the maximum distance
-        idx[i0 + tid] = ok ? (int64_t)(unsigned int)(k & 0xffffffffull) : 0;
-        if (dist) dist[i0 + tid] = ok ? sqrtf(__uint_as_float((unsigned int)(k >> 32))) : 2.0f;
+        const int ik = ms.ord1 ? ms.ord1[i0 + tid] : i0 + tid;
+        idx[ik] = ok ? (int64_t)(unsigned int)(k & 0xffffffffull) : 0;
+        if (dist) dist[ik] = ok ? sqrtf(__uint_as_float((unsigned int)(k >> 32))) : 2.0f;
     }
 }
 
@@ -679,8 +758,18 @@ UMEREG_API int umereg_ume_match_coarse_f16_ex(const void* Q1_rows_h, const void*
         UMEREG_CHECK_LAUNCH("ume_coarse_p_kernel");
         return UMEREG_OK;
     }
-    hipLaunchKernelGGL(ume_coarse_h_kernel, dim3(p.n_ablk * p.splits), dim3(kWave * kDistWaves), 0, st,
-                       (const half8*)Q1_rows_h, (const half8*)Q2_cols_h, n1, n2, p.n_ablk, p.n_btiles, p.tiles_per_split, ms);
+    const dim3 wg(kWave * kDistWaves);
+    if (p.sub_tiles && UMEREG_COARSE_PHASES == 2) {
+        hipLaunchKernelGGL(ume_coarse_h_kernel, dim3(p.n_ablk * p.sub_splits), wg, 0, st, (const half8*)Q1_rows_h, (const half8*)Q2_cols_h,
+                           n1, n2, p.n_ablk, 0, p.sub_tiles, p.sub_tiles, p.sub_tps, p.sub_splits, 1, 0, ms);
+        UMEREG_CHECK_LAUNCH("ume_coarse_h_kernel");
+        hipLaunchKernelGGL(ume_coarse_h_kernel, dim3(p.n_ablk * (p.splits - p.sub_splits)), wg, 0, st, (const half8*)Q1_rows_h,
+                           (const half8*)Q2_cols_h, n1, n2, p.n_ablk, p.sub_tiles, p.sub_tiles, p.n_btiles, 1, 0, p.tiles_per_split,
+                           p.sub_splits, ms);
+    } else {
+        hipLaunchKernelGGL(ume_coarse_h_kernel, dim3(p.n_ablk * p.splits), wg, 0, st, (const half8*)Q1_rows_h, (const half8*)Q2_cols_h,
+                           n1, n2, p.n_ablk, 0, p.sub_tiles, p.n_btiles, p.sub_tiles ? p.sub_tps : 1, p.sub_splits, p.tiles_per_split, 0, ms);
+    }
     UMEREG_CHECK_LAUNCH("ume_coarse_h_kernel");
     return UMEREG_OK;
 }
@@ -690,16 +779,16 @@ UMEREG_API int umereg_ume_match_coarse_f16(const void* Q1_rows_h, const void* Q2
     return umereg_ume_match_coarse_f16_ex(Q1_rows_h, Q2_cols_h, n1, n2, scratch, scratch_bytes, nullptr, stream);
 }
 
-UMEREG_API int umereg_ume_match_refine_f16_ex(const void* Q1_rows_h, const void* Q2_cols_h, int n1, int n2,
-                                              const void* scratch, size_t scratch_bytes, int64_t* match_idx,
-                                              float* match_dist, const umereg_match_opts* opts, void* stream)
+int umereg::match_refine_f16(const void* Q1_rows_h, const void* Q2_cols_h, int n1, int n2, const void* scratch, size_t scratch_bytes,
+                             int64_t* match_idx, float* match_dist, const umereg_match_opts* opts, const int* order1,
+                             const int* order2, void* stream)
 {
     UMEREG_REQUIRE(match_idx, "ume_match_refine_f16: null match_idx");
     MatchOpts o;
     if (int rc = resolve_opts(opts, o, "ume_match_refine_f16")) return rc;
     if (int rc = match_args(Q1_rows_h, Q2_cols_h, n1, n2, (void*)scratch, scratch_bytes, o, "ume_match_refine_f16")) return rc;
     const CoarsePlan p = coarse_plan(n1, n2, o);
-    const MatchScratch ms = carve_scratch((void*)scratch, n1, p, o);
+    const MatchScratch ms = carve_scratch((void*)scratch, n1, p, o, order1, order2);
     if (use_pform(o))
         hipLaunchKernelGGL((match_refine_kernel<kPRows, kPRegionCap>), dim3(p.n_blocks), dim3(256), 0, (hipStream_t)stream,
                            (const _Float16*)Q1_rows_h, (const _Float16*)Q2_cols_h, n1, n2, ms, match_idx, match_dist);
@@ -708,6 +797,12 @@ UMEREG_API int umereg_ume_match_refine_f16_ex(const void* Q1_rows_h, const void*
                            (const _Float16*)Q1_rows_h, (const _Float16*)Q2_cols_h, n1, n2, ms, match_idx, match_dist);
     UMEREG_CHECK_LAUNCH("match_refine_kernel");
     return UMEREG_OK;
+}
+UMEREG_API int umereg_ume_match_refine_f16_ex(const void* Q1_rows_h, const void* Q2_cols_h, int n1, int n2,
+                                              const void* scratch, size_t scratch_bytes, int64_t* match_idx,
+                                              float* match_dist, const umereg_match_opts* opts, void* stream)
+{
+    return match_refine_f16(Q1_rows_h, Q2_cols_h, n1, n2, scratch, scratch_bytes, match_idx, match_dist, opts, nullptr, nullptr, stream);
 }
 UMEREG_API int umereg_ume_match_refine_f16(const void* Q1_rows_h, const void* Q2_cols_h, int n1, int n2,
                                            const void* scratch, size_t scratch_bytes, int64_t* match_idx,

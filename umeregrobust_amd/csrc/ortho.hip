@@ -9,15 +9,18 @@
 
 namespace umereg {
 
+// order (optional): slot i of Q holds the basis of matrix order[i] (targets: order[target_slot_pos(i, n)], qlayout.h) -- a gather
+// on the read side; null = slot i holds matrix i.
 __device__ __forceinline__ void orthobasis_body(const float* __restrict__ ume, int n, int n_pad, int layout,
-                                                float* __restrict__ Q)
+                                                float* __restrict__ Q, const int* __restrict__ order = nullptr, bool subsample_first = false)
 {
     const int row = threadIdx.x & 31;
     const int i = (blockIdx.x * blockDim.x + threadIdx.x) >> 5;
     if (i >= n_pad) return;  // uniform per 32-lane group
     double q[4] = {0.0, 0.0, 0.0, 0.0};
     if (i < n) {
-        const float4 f = reinterpret_cast<const float4*>(ume)[(size_t)i * 32 + row];
+        const int src = order ? order[subsample_first ? target_slot_pos(i, n) : i] : i;
+        const float4 f = reinterpret_cast<const float4*>(ume)[(size_t)src * 32 + row];
         const double a[4] = {f.x, f.y, f.z, f.w};
         householder_q_32x4(a, q, row);
     }
@@ -57,10 +60,11 @@ __global__ __launch_bounds__(256) void orthobasis_kernel(const float* __restrict
 // both sets of a matching problem in one launch (blockIdx.y: 0 = rows / source set, 1 = columns / target set)
 __global__ __launch_bounds__(256) void orthobasis_pair_kernel(const float* __restrict__ ume1, int n1, int n1_pad, int layout1,
                                                               float* __restrict__ Q1, const float* __restrict__ ume2, int n2,
-                                                              int n2_pad, int layout2, float* __restrict__ Q2)
+                                                              int n2_pad, int layout2, float* __restrict__ Q2,
+                                                              const int* __restrict__ order1, const int* __restrict__ order2)
 {
-    if (blockIdx.y == 0) orthobasis_body(ume1, n1, n1_pad, layout1, Q1);
-    else orthobasis_body(ume2, n2, n2_pad, layout2, Q2);
+    if (blockIdx.y == 0) orthobasis_body(ume1, n1, n1_pad, layout1, Q1, order1, false);
+    else orthobasis_body(ume2, n2, n2_pad, layout2, Q2, order2, true);
 }
 
 // singular values of each 32x4 UME (torch.linalg.svdvals at reference utils/eval_utils.py:31-32): one-sided
@@ -127,13 +131,13 @@ int launch_orthobasis(const float* ume, int n, int layout, float* Q, hipStream_t
 }
 
 int launch_orthobasis_pair(const float* ume1, int n1, int layout1, float* Q1, const float* ume2, int n2, int layout2,
-                           float* Q2, hipStream_t st)
+                           float* Q2, hipStream_t st, const int* order1, const int* order2)
 {
     const int n1_pad = (int)align_up((size_t)n1, qlayout_pad(layout1)), n2_pad = (int)align_up((size_t)n2, qlayout_pad(layout2));
     const int groups_per_wg = 256 / 32;
     const int gx = ((n1_pad > n2_pad ? n1_pad : n2_pad) + groups_per_wg - 1) / groups_per_wg;
     hipLaunchKernelGGL(orthobasis_pair_kernel, dim3(gx, 2), dim3(256), 0, st, ume1, n1, n1_pad, layout1, Q1, ume2, n2, n2_pad,
-                       layout2, Q2);
+                       layout2, Q2, order1, order2);
     UMEREG_CHECK_LAUNCH("orthobasis_pair_kernel");
     return UMEREG_OK;
 }

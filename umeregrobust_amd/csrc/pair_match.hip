@@ -86,8 +86,13 @@ static int pair_match_chain(const float* pts, const float* feat, const int64_t* 
     if (int rc = launch_moments(ws_mom, nullptr, kp_index, feat, 2, N, n_kp, K, radius, ordered ? UMEREG_MOMENTS_ORDERED : 0, F, nullptr,
                                 nullptr, st, desc))
         return rc;
-    if (int rc = umereg_ume_match_f16r_ex(F, F + (size_t)n_kp * 128, 1, n_kp, n_kp, match_idx, match_dist, ws_match,
-                                          need - 256 - mom_bytes, opts, stream))
+    // the matcher walks both clouds in the cell order the moment kernel just used (its early exit lives on neighbouring rows
+    // sharing their good targets, match_f16r.hip); the f16 bases it fills are private to this workspace, the results are
+    // keyed on the caller's keypoint indices either way
+    const int* order1 = ordered ? (const int*)(ws_mom + grid_ws(N).off_kperm) : nullptr;
+    const int* order2 = ordered ? (const int*)(ws_mom + grid_ws(N).total + grid_ws(N).off_kperm) : nullptr;
+    if (int rc = match_f16r_ordered(F, F + (size_t)n_kp * 128, n_kp, n_kp, order1, order2, match_idx, match_dist, ws_match,
+                                    need - 256 - mom_bytes, opts, stream))
         return rc;
     if (prob)
         if (int rc = umereg_match_prob_f32(match_dist, n_kp, tau, prob, stream)) return rc;

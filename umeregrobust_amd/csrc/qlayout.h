@@ -39,4 +39,22 @@ __device__ __forceinline__ size_t hoff_cols(int j, int b, int k, int plane)
     return ((((((size_t)(j >> 5) * 4 + b) * 2 + s) * 2 + plane) * 64) + h * 32 + (j & 31)) * 8 + e;
 }
 
+// ---- slot order of a matching problem whose keypoints come with a processing order (the pair chain, pair_match.hip) ----
+// order[p] = the keypoint at position p of the cell-sorted order (kp_order_kernel).  Source slot s holds keypoint order1[s].
+// Target slot s holds keypoint order2[target_slot_pos(s, n)]: the first ceil(n / kSubStride) slots are a spatially uniform
+// subsample (every kSubStride-th position), the other positions follow in order.  After the subsample's tiles every source
+// row has met a target from its own neighbourhood, so its limit is close to the final one when the bulk begins (the early
+// exit of ume_coarse_h_kernel lives on that).  A bijection of [0, n) onto itself for every n >= 1.
+#ifndef UMEREG_SUB_STRIDE
+#define UMEREG_SUB_STRIDE 8   // (16 for an A/B: half the subsample)
+#endif
+constexpr int kSubStride = UMEREG_SUB_STRIDE;
+__host__ __device__ inline int target_slot_pos(int s, int n)
+{
+    const int n_sub = (n + kSubStride - 1) / kSubStride;
+    if (s < n_sub) return s * kSubStride;
+    const int r = s - n_sub;
+    return r + r / (kSubStride - 1) + 1;
+}
+
 }  // namespace umereg
