@@ -2,9 +2,9 @@
 
 `MyInfoNCELossNoSeg` -- the point-wise contrastive loss of the reference's trainer (train_coloring.py:44-45; loss.py:10-46) --
 is plain torch on top of the feature network's differentiable output, with the reference's signature and the reference's
-order of operations, so that fp32 values agree to rounding.  `UMEContrastiveLoss` and `CubeRegistrationLoss` need
-differentiable UME moments, subspace distances and RTUME, which the HIP kernels of this library do not have yet:
-constructing them raises."""
+order of operations, so that fp32 values agree to rounding.  The working `UMEContrastiveLoss` lives in `ume_loss.py`, on the
+differentiable UME moments and subspace distances of `ume_grad.py`; the name here still refuses and points there.
+`CubeRegistrationLoss` needs a differentiable RTUME, which the HIP kernels of this library do not have yet."""
 import torch
 from torch import nn
 from torch.nn import functional as tnf
@@ -39,8 +39,8 @@ class MyInfoNCELossNoSeg(nn.Module):
 
 class UMEContrastiveLoss(nn.Module):
     def __init__(self, *args, **kwargs):
-        raise NotImplementedError("UMEContrastiveLoss needs differentiable UME moments and subspace distances; the HIP kernels "
-                                  "of this library are forward only (out of scope of the trainable feature network)")
+        raise NotImplementedError("loss.UMEContrastiveLoss is out of scope of this module: the working class is "
+                                  "umeregrobust_amd.ume_loss.UMEContrastiveLoss (same constructor, same return values)")
 
 
 class CubeRegistrationLoss(nn.Module):
