@@ -52,6 +52,64 @@ def test_no_cpu_fallback_without_device():
     assert lib.umereg_qbasis_bytes(10000, 3) == 10112 * 512
 
 
+# (Ns, Nt, M, flags, bytes): umereg_corr_workspace_bytes_ex of the library BEFORE the layout moved into corr_ws (corr.hip), on both
+# sides of every branch of the layout.  Flag values: include/umereg.h.
+_CORR_WS_BYTES = [
+    (100, 100, 10, 0x0, 255744), (5000, 6000, 300, 0x0, 84728576), (5000, 6000, 300, 0xa, 84728576), (5000, 6000, 300, 0x1a, 84728576),
+    (5000, 6000, 300, 0xa000a, 102078464), (5000, 6000, 300, 0x28000a, 102302976),
+    (10000, 10000, 2500, 0x0, 573977088), (10000, 10000, 2500, 0x1, 4399872), (10000, 10000, 2500, 0x200000, 808176640),
+    (30000, 30000, 5000, 0x0, 2548424704), (30000, 30000, 5000, 0x200000, 2567565568), (70000, 70000, 5000, 0x0, 40666880),
+    # M x Ns below and at 2^17, with and without FORCE_LATTICE (2), and with the consensus pass forced on top (8)
+    (1024, 2000, 127, 0x0, 579840), (1024, 2000, 127, 0x2, 12118016), (1024, 2000, 128, 0x0, 12166400), (1024, 2000, 128, 0x2, 12166400),
+    (1024, 2000, 127, 0xa, 12685312), (1024, 2000, 128, 0x8, 12737792),
+    # NO_LATTICE (1), whatever else is set
+    (5000, 6000, 300, 0x1, 1750272), (5000, 6000, 300, 0x20000b, 1750272),
+    # 16-bit list entries: Nt at 65471 and 65472
+    (5000, 65471, 300, 0x0, 95243008), (5000, 65472, 300, 0x0, 12264704), (5000, 65472, 300, 0x200002, 12264704),
+    # M at 255 and 256, FORCE_CONSENSUS (8) / NO_CONSENSUS (4)
+    (5000, 6000, 255, 0x0, 67538944), (5000, 6000, 256, 0x0, 73323520), (5000, 6000, 255, 0x8, 73065728), (5000, 6000, 256, 0x4, 67776000),
+    (5000, 6000, 256, 0x20000c, 67959552),
+    # M x Ns at 2^24 - 1, 2^24, 2^25 - 1, 2^25, without and with BOUND_OUTSIDE (1 << 21)
+    (4097, 6000, 4095, 0x0, 480761344), (4097, 6000, 4095, 0x200000, 482925056), (4096, 6000, 4096, 0x0, 480571136),
+    (4096, 6000, 4096, 0x200000, 647366400), (18631, 20000, 1801, 0x0, 672310016), (18631, 20000, 1801, 0x200000, 976628224),
+    (8192, 8000, 4096, 0x0, 968905984), (8192, 8000, 4096, 0x200000, 973182464),
+    # the cell block: CELL_PASS (1 << 19) on a small job; NO_CELL_PASS (1 << 20), LEFT_COOP (1 << 16), CONSENSUS_V1 (32) on big ones
+    (5000, 6000, 300, 0x80000, 102078464), (8192, 8000, 4096, 0x100000, 669007360), (8192, 8000, 4096, 0x10000, 669007360),
+    (8192, 8000, 4096, 0x20, 669007360), (8192, 8000, 4096, 0x180000, 669007360), (4096, 6000, 4096, 0x300000, 482734080),
+    (4096, 6000, 4096, 0x200020, 482734080),
+    # NO_FLAT (16) switches the bound block off
+    (8192, 8000, 4096, 0x200010, 968905984), (4096, 6000, 4096, 0x200010, 645203456), (10000, 10000, 2500, 0x200010, 804905728),
+    # Ns x M >= 2^32: no cell pass (32-bit entries)
+    (70000, 60000, 70000, 0x0, 55128904704), (70000, 60000, 70000, 0x200000, 55742665216), (65536, 60000, 65536, 0x80000, 48358834944),
+    # flags the layout ignores (SRC_ROWS, RECORD_STAGE, DEBUG_STATS, a far margin); nothing a multiple of 64
+    (10000, 10000, 2500, 0x414c0, 573977088), (513, 700, 257, 0x2, 12565248),
+]
+
+
+def test_corr_workspace_layout_is_the_one_python_and_the_tools_rely_on():
+    """umereg_corr_workspace_bytes_ex is pure host arithmetic (corr_ws, corr.hip) and must not move: the values below are those of the
+    library before the layout got its one function.  And the relation ops.corr_scores_profile, bench.py and the tools rely on: the call's 64
+    header words start at bytes_ex(Ns, Nt, M, NO_LATTICE) -- everything in front of the lattice exists for every flag set, everything from
+    the lattice on needs it.  So that offset does not depend on the other flags, a call without a lattice has nothing behind it, and a call
+    with one has at least the header."""
+    from umeregrobust_amd import _lib, ops
+    lib = _lib.load()
+    assert len(_CORR_WS_BYTES) >= 40 and len(set(_CORR_WS_BYTES)) == len(_CORR_WS_BYTES)
+    for Ns, Nt, M, flags, want in _CORR_WS_BYTES:
+        assert lib.umereg_corr_workspace_bytes_ex(Ns, Nt, M, flags) == want, (Ns, Nt, M, hex(flags))
+    assert lib.umereg_corr_workspace_bytes(10000, 10000, 2500) == 573977088
+    for bad in ((0, 5, 5), (5, 0, 5), (5, 5, 0), (-1, 5, 5)):
+        assert lib.umereg_corr_workspace_bytes_ex(*bad, 0) == 0
+    routes = (0, 2, 8, 2 | 8, 4, 16, 32, 128, 1 << 16, 1 << 17, 1 << 18, 1 << 19, 1 << 20, 1 << 21, 2 | 8 | 1 << 19 | 1 << 21, (1 << 21) | 16)
+    for (Ns, Nt, M), off in (((5000, 6000, 300), 1750272), ((10000, 10000, 2500), 4399872), ((1024, 2000, 127), 579840),
+                             ((5000, 65472, 300), 12264704), ((4096, 6000, 4096), 2614784), ((70000, 70000, 5000), 40666880)):
+        for f in routes:
+            assert lib.umereg_corr_workspace_bytes_ex(Ns, Nt, M, f | ops.CORR_NO_LATTICE) == off, (Ns, Nt, M, hex(f))
+            total = lib.umereg_corr_workspace_bytes_ex(Ns, Nt, M, f)
+            has_lattice = Nt <= 65471 and (M * Ns >= 1 << 17 or f & 2)
+            assert (total >= off + 256) if has_lattice else (total == off), (Ns, Nt, M, hex(f), total)
+
+
 def test_product_never_imports_the_oracle():
     """The oracle is test infrastructure: nothing under umeregrobust_amd/ may import or load it."""
     pkg = os.path.join(REPO, "umeregrobust_amd")

@@ -1149,47 +1149,16 @@ __device__ __forceinline__ void cons2_point(
 
 // The pass: one wavefront per source point, kC2BlockWaves (1) wavefronts per workgroup -- a finished wavefront's registers and LDS free at
 // once; with two per workgroup they stayed idle until the partner was done (1.175 -> 1.145 ms on a KITTI-test pair).
-// -DUMEREG_CONS2_PERSIST=1 (A/B builds, tools/r05_cons2_ab.sh; default 0): PERSISTENT wavefronts that take source points off a counter in the
-// call's header (word kCons2NextWord) -- three wavefronts per SIMD for the whole launch instead of 2.3 on average (a point costs between
-// a tenth and ten times the average), measured SLOWER: 1.21-1.22 ms (profiles/r05/cons2_schedule_ab.txt).  For that form the arguments come
-// as ONE struct and every point re-reads them from the kernel-argument segment: kept in registers across the loop they cost 40 scalar
-// registers more than the one-point kernel has, and the kernel no longer fits the 168 of three wavefronts per SIMD (it still spills 80 B).
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(UMEREG_CONS2_WAVES, UMEREG_CONS2_WAVES))) void corr_consensus2_kernel(Cons2Args args)
 {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = lane_id();
-    unsigned int* const next_slot = args.next_slot;
-    const int Ns = args.Ns;
-    auto take = [&]() __attribute__((always_inline)) {
-        unsigned int s = 0u;
-        if (lane == 0) s = atomicAdd(next_slot, 1u);
-        return (int)__builtin_amdgcn_readfirstlane(s);
-    };
-#if !UMEREG_CONS2_PERSIST
-    {
-        const int slot_n = (int)(blockIdx.x * (blockDim.x >> 6)) + wave;      // one wavefront per source point, no loop (A/B builds)
-        if (slot_n < Ns)
-            cons2_point(slot_n, lds + (size_t)wave * cons2_lds_per_wave(), lane, args.ws_tgt, args.ws_coop, args.ws_src, args.src_pts, args.vp4, args.vq4,
-                        args.T, args.Tmed, args.perm, args.Ns, args.Nt, args.M, args.K, args.sigma, args.far_margin_cells, args.val, args.served,
-                        args.stats, args.dbg, args.act_frac);
-        return;
-    }
-#endif
-    int slot_n = next_slot ? take() : (int)(blockIdx.x * (blockDim.x >> 6)) + wave;
-    while (slot_n < Ns) {                                                       // (one call site: the point's code exists once)
-        const Cons2Args* ap = (const Cons2Args*)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(ap));                                            // opaque: the loads below are this iteration's own
-        const Cons2Args a = *ap;
-        int lane_l = lane;
-        unsigned int my_off = (unsigned int)wave * (unsigned int)cons2_lds_per_wave();
-        asm volatile("" : "+v"(lane_l), "+s"(my_off));                           // (likewise: no per-lane address arithmetic carried across points)
-        cons2_point(slot_n, lds + my_off, lane_l, a.ws_tgt, a.ws_coop, a.ws_src, a.src_pts, a.vp4, a.vq4, a.T, a.Tmed, a.perm, a.Ns, a.Nt, a.M, a.K, a.sigma,
-                    a.far_margin_cells, a.val, a.served, a.stats, a.dbg, a.act_frac);
-        if (!next_slot) break;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");                // the next point reuses this wavefront's LDS region
-        slot_n = take();
-    }
+    const int slot_n = (int)(blockIdx.x * (blockDim.x >> 6)) + wave;
+    if (slot_n < args.Ns)
+        cons2_point(slot_n, lds + (size_t)wave * cons2_lds_per_wave(), lane, args.ws_tgt, args.ws_coop, args.ws_src, args.src_pts, args.vp4, args.vq4,
+                    args.T, args.Tmed, args.perm, args.Ns, args.Nt, args.M, args.K, args.sigma, args.far_margin_cells, args.val, args.served,
+                    args.stats, args.dbg, args.act_frac);
 }
 
 }  // namespace umereg
