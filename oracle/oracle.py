@@ -27,15 +27,38 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "libume_oracle.so")
+_POLAR_SO = os.path.join(_HERE, "libpolar_host.so")
+_POLAR_H = os.path.join(os.path.dirname(_HERE), "umeregrobust_amd", "csrc", "polar.h")
 _lib = None
+_polar_lib = None
+
+
+def _stale(so, *srcs):
+    return not os.path.exists(so) or any(os.path.getmtime(so) < os.path.getmtime(s) for s in srcs)
 
 
 def build(force=False):
-    """Compile oracle/ume_oracle.c with gcc (recipe: oracle/Makefile)."""
-    src = os.path.join(_HERE, "ume_oracle.c")
-    if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(src):
-        subprocess.check_call(["make", "-s", "-C", _HERE, "libume_oracle.so"])
+    """Compile oracle/ume_oracle.c with gcc and the host build of the library's polar.h with g++ (recipe: oracle/Makefile)."""
+    if force or _stale(_SO, os.path.join(_HERE, "ume_oracle.c")):
+        subprocess.check_call(["make", "-s", "-C", _HERE] + (["-B"] if force else []) + ["libume_oracle.so"])
+    if force or _stale(_POLAR_SO, os.path.join(_HERE, "polar_host.cpp"), _POLAR_H):
+        subprocess.check_call(["make", "-s", "-C", _HERE] + (["-B"] if force else []) + ["libpolar_host.so"])
     return _SO
+
+
+def polar_rotation_host(A):
+    """The LIBRARY's polar_rotation (umeregrobust_amd/csrc/polar.h, compiled for the host: oracle/polar_host.cpp) on fp64 [n,3,3]
+    -> fp64 [n,3,3].  The code under test, not a reference: tests/test_polar_cpu.py judges it against numpy's SVD."""
+    global _polar_lib
+    if _polar_lib is None:
+        build()
+        _polar_lib = ctypes.CDLL(_POLAR_SO)
+        _polar_lib.orc_polar_rotation_f64.restype = ctypes.c_int
+    A = np.ascontiguousarray(A, dtype=np.float64).reshape(-1, 3, 3)
+    R = np.empty_like(A)
+    rc = _polar_lib.orc_polar_rotation_f64(_p(A), ctypes.c_int(A.shape[0]), _p(R))
+    assert rc == 0
+    return R
 
 
 def lib():
@@ -379,7 +402,7 @@ def batch_estimate_transform_ume_old(G, H, with_dist=True):
     return T.astype(np.float32), D
 
 
-RtumeCond = namedtuple("RtumeCond", "s s3_s1 cos_mg_mh kappa_R kappa_t")
+RtumeCond = namedtuple("RtumeCond", "s s3_s1 cos_mg_mh kappa_R kappa_t kappa_R_problem kappa_R_normal kappa_t_problem")
 
 
 def batch_estimate_transform_ume_f64(G, H, g_index=None, h_index=None):
@@ -393,6 +416,10 @@ def batch_estimate_transform_ume_f64(G, H, g_index=None, h_index=None):
                  cross-moment's own rounding, |terms of A| / (s2 + det * s3) (polar factor sensitivity), and a solve through
                  the normal matrix A^T A, s1^2 / (s2 (s2 + det * s3));
       kappa_t    the same for t (in the units of t): the rounding of wrc (a quotient over mg.mh), of wlc, and wlc's share of dR.
+      kappa_R_problem, kappa_R_normal   the two terms of kappa_R apart.  Only the first belongs to the PROBLEM (any backward-stable fp64
+                 evaluation meets u * kappa_R_problem); the second is the price of one particular method, a solve through A^T A, which
+                 the fp32 reference's error is measured with and which no fp64 program is excused by;
+      kappa_t_problem   kappa_t with kappa_R_problem in the place of kappa_R.
     Two correct fp64 evaluations of these statements differ by a small multiple of 2^-53 * kappa."""
     G = np.asarray(G, np.float32).astype(np.float64)
     H = np.asarray(H, np.float32).astype(np.float64)
@@ -426,13 +453,16 @@ def batch_estimate_transform_ume_f64(G, H, g_index=None, h_index=None):
         cos = np.abs(mg_mh[:, 0, 0]) / (n_mg * n_mh)
         gap = S[:, 1] + det * S[:, 2]
         a_terms = (n_g + n_wlc * n_mg) * (n_h + n_wrc * n_mh)
-        kappa_R = a_terms / gap + S[:, 0] ** 2 / (S[:, 1] * gap)
+        kappa_R_problem, kappa_R_normal = a_terms / gap, S[:, 0] ** 2 / (S[:, 1] * gap)
+        kappa_R = kappa_R_problem + kappa_R_normal
         q_wrc = (n_h * n_mg + n_wrc * n_mg * n_mh) / np.abs(mg_mh[:, 0, 0])
         q_wlc = (n_g * n_mg + n_wlc * n_mg ** 2) / mg2[:, 0, 0]
         kappa_t = q_wrc + q_wlc + n_wlc * (1.0 + kappa_R)
+        kappa_t_problem = q_wrc + q_wlc + n_wlc * (1.0 + kappa_R_problem)
         s3_s1 = S[:, 2] / S[:, 0]
     bad = lambda x: np.where(np.isfinite(x), x, np.inf)                       # noqa: E731
-    return T, RtumeCond(S, np.nan_to_num(s3_s1, nan=0.0), np.nan_to_num(cos, nan=0.0), bad(kappa_R), bad(kappa_t))
+    return T, RtumeCond(S, np.nan_to_num(s3_s1, nan=0.0), np.nan_to_num(cos, nan=0.0), bad(kappa_R), bad(kappa_t),
+                        bad(kappa_R_problem), bad(kappa_R_normal), bad(kappa_t_problem))
 
 
 # ---------------------------------------------------------------------------------------------
