@@ -300,6 +300,36 @@ def encode_split_f16(hi, lo, layout):
     return out
 
 
+# fp32 fragment layouts (umeregrobust_amd/csrc/qlayout.h, qoff_rows / qoff_cols): the operand order of the exact-fp32 distance GEMM.
+QLAYOUT_ROWS, QLAYOUT_COLS = 1, 2
+
+
+def f32_fragment_floats(n, layout):
+    """Number of floats of an fp32 fragment buffer of n keypoints (umereg_qbasis_bytes / 4): ROWS pads n to 16, COLS to 32."""
+    pad = {QLAYOUT_ROWS: 16, QLAYOUT_COLS: 32}[layout]
+    return (n + pad - 1) // pad * pad * 128
+
+
+def f32_fragment_offsets(n, layout):
+    """Float offsets of entry (keypoint, channel k, basis column): int64 [n,32,4], restated from qoff_rows / qoff_cols."""
+    i = np.arange(n, dtype=np.int64)[:, None, None]
+    k = np.arange(32, dtype=np.int64)[None, :, None]
+    a = np.arange(4, dtype=np.int64)[None, None, :]
+    h, kk4, e = k >> 4, (k >> 2) & 3, k & 3
+    if layout == QLAYOUT_ROWS:
+        return ((((i >> 3) * 4 + kk4) * 64) + h * 32 + (i & 7) * 4 + a) * 4 + e
+    if layout == QLAYOUT_COLS:
+        return (((((i >> 5) * 4 + a) * 4 + kk4) * 64) + h * 32 + (i & 31)) * 4 + e
+    raise ValueError(f"not an fp32 fragment layout: {layout}")
+
+
+def decode_f32_fragments(buf, n, layout):
+    """fp32 fragment buffer (ops.ume_orthobasis(ume, layout) copied to the host) -> Q f32 [n,32,4]."""
+    f = np.ascontiguousarray(buf).reshape(-1).view(np.float32)
+    assert f.size >= f32_fragment_floats(n, layout), (f.size, f32_fragment_floats(n, layout))
+    return f[f32_fragment_offsets(n, layout)]
+
+
 SplitMatch = namedtuple("SplitMatch", "argmin key arg2 key2 d64 d64sec coarse_win coarse_max")
 
 # Bound on |computed - exact| of one fp64 evaluation of 4 - |Qa^T Qb|_F^2 from split bases, in ANY summation order (and with

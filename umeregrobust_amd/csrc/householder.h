@@ -1,7 +1,8 @@
 // householder.h -- 32x4 Householder orthonormal basis on a 32-lane group (lane = matrix row).
 // Restates torch.linalg.qr(mode='reduced').Q as used at reference utils/loc_utils.py:9,11,338,341
 // with LAPACK geqr2/org2r conventions (H_k = I - tau_k v_k v_k^T, v_k[k] = 1, tau_k = 0 when the
-// tail of column k is exactly zero), evaluated in fp64.  Cholesky-QR would be unsafe here:
+// tail of column k is exactly zero; beta = -sign(alpha) |x| with Fortran's SIGN, which takes alpha = -0.0 as negative),
+// evaluated in fp64.  Cholesky-QR would be unsafe here:
 // cond(F) reaches 1e4..1e8 because UME moments use absolute coordinates.
 #pragma once
 #include "common.h"
@@ -23,7 +24,7 @@ __device__ __forceinline__ void householder_q_32x4(const double a_in[4], double 
             continue;
         }
         const double nrm = sqrt(alpha * alpha + xn2);
-        const double beta = alpha >= 0.0 ? -nrm : nrm;
+        const double beta = -copysign(nrm, alpha);
         tau[k] = (beta - alpha) / beta;
         const double sc = 1.0 / (alpha - beta);
         if (row > k) a[k] *= sc;
