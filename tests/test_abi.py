@@ -173,3 +173,29 @@ def test_match_kernels_are_launched_where_they_are_defined():
     for f in sorted(os.listdir(csrc)):
         if f.endswith((".hip", ".h")) and f not in units:
             assert not (set(_kernels_of(os.path.join(csrc, f))) & want), f
+
+
+def test_grid_and_ball_kernels_are_launched_where_they_are_defined():
+    """The a1 / a2 sources, once one file, are cut by subject: grid.hip builds the search structure, ball_search.h is the device-inline
+    search, ball_query.hip and ume_moments.hip hold the two kernels that use it.  Each of the eight kernels is DEFINED in exactly
+    one unit and LAUNCHED only from that unit; every other unit of the library goes through the launchers that grid.h and
+    ball_search.h declare, and neither defines, declares nor launches one of these kernels."""
+    csrc = os.path.join(REPO, "umeregrobust_amd", "csrc")
+    want = {"grid.hip": {"pack_points_kernel", "grid_hist_kernel", "grid_scan_kernel", "grid_scatter_kernel", "kp_order_kernel",
+                         "zero_words_kernel"},
+            "ball_query.hip": {"ball_query_kernel"},
+            "ume_moments.hip": {"ume_moments_kernel"}}
+    every = set().union(*want.values())
+    assert len(every) == 8
+    assert not os.path.exists(os.path.join(csrc, "ball_moment.hip"))
+    launches = lambda f: set(re.findall(r"hipLaunchKernelGGL\(\(?(\w+)", open(os.path.join(csrc, f)).read()))
+    for f, names in want.items():
+        defined = _kernels_of(os.path.join(csrc, f))
+        assert sorted(defined) == sorted(names), f"{f} defines {sorted(defined)}"
+        assert launches(f) == names, f"{f} launches {sorted(launches(f))}"
+    assert _kernels_of(os.path.join(csrc, "ball_search.h")) == [] and launches("ball_search.h") == set()
+    assert _kernels_of(os.path.join(csrc, "grid.h")) == ["record_write_kernel"]
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h")) and f not in want:
+            assert not (set(_kernels_of(os.path.join(csrc, f))) & every), f"{f} defines or declares a kernel of another unit"
+            assert not (launches(f) & every), f"{f} launches a kernel of another unit"

@@ -1,7 +1,7 @@
 // pair_match.hip -- a1..a5 of one registration pair in one call, and the same chain as a hipGraph.  Host composition only:
-// every kernel belongs to the unit whose entry launches it (ball_moment.hip, ortho.hip, match*.hip).
+// every kernel belongs to the unit whose entry launches it (grid.hip, ume_moments.hip, ortho.hip, match*.hip).
 #include "common.h"
-#include "grid.h"
+#include "ball_search.h"
 #include "match_dev.h"
 
 using namespace umereg;
@@ -58,7 +58,7 @@ static int pair_match_chain(const float* pts, const float* feat, const int64_t* 
     UMEREG_REQUIRE(F && match_idx && match_dist, "%s: null output pointer", who);
     UMEREG_REQUIRE(ragged || (pts && feat && kp_index), "%s: null pointer", who);
     UMEREG_REQUIRE(N > 0 && n_kp > 0, "%s: N, n_kp must be positive (got %d, %d)", who, N, n_kp);
-    UMEREG_REQUIRE(K > 0 && K <= 7680, "%s: K must be in [1, 7680] (got %d)", who, K);
+    UMEREG_REQUIRE(K > 0 && K <= kMaxBallK, "%s: K must be in [1, 7680] (got %d)", who, K);
     UMEREG_REQUIRE(radius > 0.f, "%s: radius must be positive", who);
     UMEREG_REQUIRE(!prob || tau > 0.f, "%s: tau must be positive when prob is requested", who);
     UMEREG_REQUIRE(!ragged || n_kp <= grid_ws(N).Npad, "%s: n_kp (%d) exceeds the capacity's keypoint buffer (%d): the reference draws "
@@ -80,7 +80,7 @@ static int pair_match_chain(const float* pts, const float* feat, const int64_t* 
         if (int rc = write_pair_desc(desc_of(workspace, need), *desc_vals, st)) return rc;
     }
     if (int rc = launch_prep(pts, ws_mom, 2, N, radius, st, 0, desc)) return rc;
-    const int ordered = n_kp <= grid_ws(N).Npad && n_kp >= 64;
+    const bool ordered = keypoint_order_pays(N, n_kp);
     if (ordered)
         if (int rc = launch_query_order(ws_mom, nullptr, kp_index, 2, N, n_kp, radius, st, desc)) return rc;
     if (int rc = launch_moments(ws_mom, nullptr, kp_index, feat, 2, N, n_kp, K, radius, ordered ? UMEREG_MOMENTS_ORDERED : 0, F, nullptr,
