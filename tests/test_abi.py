@@ -128,23 +128,40 @@ def _kernels_of(path):
     return re.findall(r"__global__\s+void\s+(\w+)\s*\(", text)
 
 
-def test_corr_kernel_declarations_match_the_definitions():
-    """The hypothesis-selection sources are five translation units: every kernel is DEFINED in exactly one of
-    corr_knn / corr_consensus / corr_lattice / corr_leftover.hip and DECLARED exactly once in corr_kernels.h (what corr.hip,
-    the file with the one call, launches through); corr.hip and the two headers define none."""
+def test_corr_kernels_are_launched_where_they_are_defined():
+    """The hypothesis-selection sources are five translation units over corr_dev.h and corr_host.h: each of the 42 kernels is
+    DEFINED in exactly one of corr_knn / corr_consensus / corr_lattice / corr_leftover.hip and LAUNCHED only from that unit, by the host
+    launcher beside it (declared in corr_host.h) -- no kernel is declared across units, so there is no second copy of a signature that
+    could disagree with the first.  corr.hip (the one call, host only) and the two headers define, declare and launch none."""
     csrc = os.path.join(REPO, "umeregrobust_amd", "csrc")
-    defined = []
-    for f in ("corr_knn.hip", "corr_consensus.hip", "corr_lattice.hip", "corr_leftover.hip"):
-        names = [n for n in _kernels_of(os.path.join(csrc, f))]
-        defined += [n for n in dict.fromkeys(names)]          # (explicit instantiations repeat a template's name in its own file)
-    declared = _kernels_of(os.path.join(csrc, "corr_kernels.h"))
-    assert len(defined) == len(set(defined)) >= 40, "a kernel is defined in two files"      # (42 names, 51 instantiations)
-    assert len(declared) == len(set(declared)), "a kernel is declared twice"
-    assert set(defined) == set(declared), (sorted(set(defined) ^ set(declared)))
-    assert _kernels_of(os.path.join(csrc, "corr.hip")) == [] and _kernels_of(os.path.join(csrc, "corr_dev.h")) == []
-    # ... and every launch in corr.hip names a declared kernel
-    launched = set(re.findall(r"hipLaunchKernelGGL\(\(?(\w+)", open(os.path.join(csrc, "corr.hip")).read()))
-    assert launched and launched <= set(declared), sorted(launched - set(declared))
+    want = {"corr_knn.hip": {"knn_points_kernel", "nn1_points_kernel", "spatial_var_kernel", "colsum_partial_kernel", "feature_weight_kernel",
+                             "chunk_box_kernel", "spatial_var_coop_kernel"},
+            "corr_consensus.hip": {"mean_rotation_kernel", "rotate_points_kernel", "hyp_median_kernel", "hyp_err_kernel", "hyp_order_kernel",
+                                   "chunk_centroid_kernel", "hyp_order_chunk_kernel", "corr_consensus_kernel", "corr_consensus2_kernel"},
+            "corr_lattice.hip": {"leftover_decide_kernel", "lattice_mark_kernel", "lattice_far_table_kernel", "lattice_mark_order_kernel",
+                                 "lattice_compact_kernel", "lattice_posof_kernel", "lattice_list_kernel", "cell_apply_kernel",
+                                 "cell_blockscan_kernel", "cell_scatter_kernel", "bound_pass2_gate_kernel", "far_recompute_kernel",
+                                 "corr_cell_kernel"},
+            "corr_leftover.hip": {"corr_score_kernel", "leftover_queue_kernel", "corr_score_fallback_kernel", "leftover_flatten_kernel",
+                                  "row_norm_kernel", "flat_bound_kernel", "corr_score_flat_kernel", "bound_survivors_kernel",
+                                  "corr_score_record2_kernel", "leftover_sum_kernel", "corr_val_slices_kernel", "corr_reduce_kernel",
+                                  "corr_select_best_kernel"}}
+    every = set().union(*want.values())
+    assert len(every) == sum(len(v) for v in want.values()) == 42, "a kernel is listed for two units"
+    assert not os.path.exists(os.path.join(csrc, "corr_kernels.h"))
+    launches = lambda f: set(re.findall(r"hipLaunchKernelGGL\(\(?(\w+)", open(os.path.join(csrc, f)).read()))
+    for f, names in want.items():
+        defined = _kernels_of(os.path.join(csrc, f))                  # (a list: an explicit instantiation or a declaration would repeat a name)
+        assert sorted(defined) == sorted(names), f"{f} defines {sorted(defined)}"
+        assert launches(f) == names, f"{f} launches {sorted(launches(f))}"
+    others = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")) and f not in want]
+    assert {"corr.hip", "corr_dev.h", "corr_host.h"} <= set(others)
+    for f in others:
+        assert not (set(_kernels_of(os.path.join(csrc, f))) & every), f"{f} defines or declares a kernel of another unit"
+        assert not (launches(f) & every), f"{f} launches a kernel of another unit"
+    for f in ["corr.hip"] + [f for f in others if f.startswith("corr") and f.endswith(".h")]:
+        assert _kernels_of(os.path.join(csrc, f)) == [] and launches(f) == set(), f"{f} defines, declares or launches a kernel"
+    assert "hipLaunchKernelGGL" not in open(os.path.join(csrc, "corr.hip")).read()
 
 
 def test_match_kernels_are_launched_where_they_are_defined():

@@ -27,16 +27,18 @@
 // Squared distances use the reference's arithmetic: sum_d (p1-p2)^2 left to right in fp32, no FMA
 // contraction (-ffp-contract=off), ties resolved towards the lower index.
 //
-// Files (one translation unit each; corr_dev.h = shared inline device code, corr_kernels.h = kernel declarations):
-//   corr.hip            this file, host only: routing thresholds, the workspace layout (corr_ws: the one place that knows it), the stage functions and
-//                       umereg_corr_scores_ex_f32, the ONE call that enqueues them, its stage profile, umereg_corr_select_best_f32
-//   corr_knn.hip        knn_points / feature_spatial_var / weighted features + their entry points
+// Files (one translation unit each; corr_dev.h = shared inline device code, corr_host.h = CorrWs, CorrCtx and the launcher declarations).
+// A kernel is defined in exactly one unit and launched only there, by the host launcher that follows it (grid, block and LDS arithmetic
+// live with the kernel they describe); this file defines and launches none:
+//   corr.hip            this file, host only: routing thresholds, the workspace layout (corr_ws: the one place that knows it), the stage functions --
+//                       sequences of launcher calls and fills -- and umereg_corr_scores_ex_f32, the ONE call that enqueues them, its stage profile
+//   corr_knn.hip        knn_points / feature_spatial_var / weighted features + their entry points, chunk boxes
 //   corr_consensus.hip  orders + the consensus pass
 //   corr_lattice.hip    candidate lattice, cell pass, second pass of the arg-max mode
-//   corr_leftover.hip   per-lane grid walk, one wavefront per query (queue / flat / records), outside bound, reductions, pick
+//   corr_leftover.hip   per-lane grid walk, one wavefront per query (queue / flat / records), outside bound, reductions, pick + its entry point
 #include <assert.h>
 
-#include "corr_kernels.h"
+#include "corr_host.h"
 
 namespace umereg {
 #ifndef UMEREG_LAT_MAXCELLS
@@ -56,15 +58,20 @@ __host__ inline unsigned int lattice_cells_for(long queries, int Nt, int flags)
 
 // (consensus pass, second form: corr_consensus.hip; the far-point margin below is the caller's default)
 constexpr float kConsFarMarginCells = 2.5f;   // default margin of the far-point stage (see corr_consensus2_kernel), in grid cells
+// who takes what the consensus pass left (header word 8): 1 = the grid kernel (few leftovers: they sit in a few
+// thousand (hypothesis, chunk) wavefronts), 0 = the candidate lattice (many: hypotheses that do not agree, clouds that
+// barely overlap -- queries in empty parts of the target, where lists pay off).  Both sets of kernels are enqueued;
+// the ones not chosen return at once.
+#ifndef UMEREG_LEFT_MAX
+#define UMEREG_LEFT_MAX 3000000u
+#endif
+constexpr unsigned int kLeftMax = UMEREG_LEFT_MAX;      // (2^21 until the end of round 3: over 32 half-overlapping KITTI-test pairs, whose leftovers straddle
+                                                        // 2 M, f1 averages 7.5 ms with 2^21 and 6.4 with 3 M or 4.5 M -- the flat list holds half the job's queries now)   // (measured round 3, with the Hilbert-ordered copy: 0.26 M leftovers 2.2 ms through the queue against 3.2 through the lattice, 1.6 M 7.8 against 8.1)
 #ifndef UMEREG_LEFT_MAX_BOUND
 #define UMEREG_LEFT_MAX_BOUND 1000000u
 #endif
-constexpr unsigned int kLeftMaxBound = UMEREG_LEFT_MAX_BOUND;      // kLeftMax (corr_dev.h) where the cell pass rides in arg-max mode on a job below 2^25 queries
+constexpr unsigned int kLeftMaxBound = UMEREG_LEFT_MAX_BOUND;      // kLeftMax where the cell pass rides in arg-max mode on a job below 2^25 queries
 
-// ascending list of the marked cells (deterministic order): cids[0 .. header[3])
-// (kCompactBlocks workgroups, each with a contiguous range of 16-cell groups; a workgroup counts the marks of the ranges before its own
-// itself -- 512 KiB of marks, read from L2 -- instead of waiting for a scan: one launch, 0.15 -> 0.02 ms for 2^19 cells)
-constexpr int kCompactBlocks = 64;
 constexpr size_t kCellMaxEntries = (size_t)1 << 26; // queries the pass can list (512 MiB of entries)
 constexpr long kCellMinQueries = 1l << 25;          // jobs below this enqueue the pass in arg-max mode only, from 2^24 queries on (corr_ws: cell_pass; a KITTI-test pair: 2.5e7 queries)
 __host__ __device__ inline size_t cell_cap(long queries) { return (size_t)(queries < (long)kCellMaxEntries ? queries : (long)kCellMaxEntries); }
@@ -88,17 +95,9 @@ __host__ inline CellWs cell_ws(char* base, unsigned int c_max, long queries)
     w.cap = (unsigned int)cell_cap(queries);
     return w;
 }
-__host__ __device__ inline size_t cell_lds_per_wave(int K, bool lng)
-{
-    // tie list (16-bit index plane) | stage (256 or 512 slots x 16 B) | the lane's K keys (d2 plane -- the histogram lives there until
-    // the second sweep starts --, 16-bit index plane)
-    // (14.5 KiB: eleven wavefronts per CU; 128 bytes more are ten)
-    return (size_t)kCons2Tie * kWave * 6 + (size_t)(lng ? 512 : kCellStage) * 16 + cell_d2_plane(K, lng) + ((size_t)K * kWave * 2 + 255) / 256 * 256;
-}
 
 // (the flat list of leftover queries: corr_leftover.hip)
 constexpr unsigned int kFlatMaxQ = 1u << 21;
-constexpr int kFlatBlocks = 6144;   // workgroups of corr_score_flat_kernel (8 wavefronts each, visits of 4 queries dealt round-robin; 768 .. 16 384 measured: 1.17 .. 1.10 ms)
 // (capacity: 2^21 queries, or half of the job's if that is more -- a nuScenes-size job of 1.5e8 queries with outlier hypotheses
 // leaves tens of millions of far-off queries, and the record kernel costs 2.4x the flat one per query)
 __host__ __device__ inline size_t flat_slots(long n_queries)
@@ -122,25 +121,7 @@ __host__ __device__ inline FlatWs flat_ws(char* base, size_t n_records, long n_q
     return f;
 }
 
-// ---- the workspace of one corr_scores call: routing and layout, decided in ONE place (corr_ws) -------------------------------
-// Byte offsets of the regions in workspace order (sizes: the `take` lines of corr_ws; table: DESIGN 4.11).  A region that is switched off
-// has no bytes.  The host takes every pointer from here (CorrCtx).  Three things outside this function rely on an ADJACENCY:
-//   1. device code finds the queue records at lat + lat_ws(c_max).total (the lattice block's inside is lat_ws's): `queue` is that offset;
-//   2. Python and the tools read the 64 header words at `lat` as umereg_corr_workspace_bytes_ex(Ns, Nt, M, UMEREG_CORR_NO_LATTICE):
-//      everything in front of `lat` exists for every flag set, everything behind it needs the lattice;
-//   3. the cell block (cell_ws: its counters first) follows the bound block at once: ONE fill clears the block and the counters.
-// corr_ws asserts all three.
-struct CorrWs {
-    unsigned int c_max;                                                         // lattice cells (0: none, the per-lane grid walk does everything)
-    bool consensus, cell_pass, bound;                                           // WITHOUT T: a misaligned T skips both passes at launch, their regions stay
-    size_t n_chunks, n_records;                                                 // 64-query chunks of the source; records the queue can hold
-    size_t src, tgt, tgth, partial, colsum, rotated, rbar;                      // always
-    size_t lat, queue;                                                          // c_max != 0
-    size_t val, served, tmed, slices, gorder, perm, inv, chunk_of, centroid;    // consensus
-    size_t b_slack, b_surv, b_vpn, b_vqmax, b_farq, bound_head, bound_bytes;    // bound (bytes in front of b_farq; of the whole block)
-    size_t cell, flat, total;                                                   // cell_pass; c_max != 0
-};
-
+// ---- the workspace of one corr_scores call: routing and layout (CorrWs, corr_host.h: the regions and the three adjacencies asserted below) ----
 __host__ inline CorrWs corr_ws(int Ns, int Nt, int M, int flags)
 {
     CorrWs w = {};
@@ -213,16 +194,6 @@ static inline void corr_mark(int i, hipStream_t st)
     if (t_corr_marks) (void)hipEventRecord(t_corr_marks[i], st);
 }
 
-UMEREG_API int umereg_corr_select_best_f32(const float* scores, const float* T, int M, float* T_best, int64_t* best_index, void* stream)
-{
-    UMEREG_REQUIRE(scores && T && T_best, "corr_select_best: null pointer");
-    UMEREG_REQUIRE(M > 0, "corr_select_best: M must be positive (got %d)", M);
-    if (int rc = check_device()) return rc;
-    hipLaunchKernelGGL(corr_select_best_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, scores, T, M, T_best, best_index);
-    UMEREG_CHECK_LAUNCH("corr_select_best_kernel");
-    return UMEREG_OK;
-}
-
 UMEREG_API size_t umereg_corr_workspace_bytes(int Ns, int Nt, int M) { return umereg_corr_workspace_bytes_ex(Ns, Nt, M, 0); }
 UMEREG_API size_t umereg_corr_workspace_bytes_ex(int Ns, int Nt, int M, int flags) { return Ns <= 0 || Nt <= 0 || M <= 0 ? 0 : corr_ws(Ns, Nt, M, flags).total; }
 
@@ -234,36 +205,8 @@ UMEREG_API int umereg_corr_scores_f32(const float* src_pts, const float* tgt_pts
                                      workspace_bytes, stream);
 }
 
-// ---- one call: what every stage below works on -------------------------------------------------------------------------------
-struct CorrCtx {
-    const float *src_pts, *tgt_pts, *T;
-    const float4 *vp4, *vq4;             // the weighted features
-    int Ns, Nt, M, K, flags;
-    float sigma, *scores;
-    hipStream_t st; CorrWs ws;
-    bool consensus, cell_pass, bound;    // routing at launch: the layout's, minus what a misaligned T switches off
-    bool far_cells;                      // arg-max mode with a cell pass: queries in far lattice cells are bounded by the scatter (see cell_scatter_kernel)
-    bool coop_copy;                      // the Hilbert-ordered copy of the target exists (structures_and_orders)
-    long queries;                        // M x Ns
-    int n_chunks, n_words, dbg, cap, waves;      // (cap, waves, lds, idx16: knn_lds_plan)
-    size_t lds; bool idx16;
-    char *ws_src, *ws_tgt, *ws_tgth, *lat;       // the regions; nullptr / zero where the stage that owns them is off
-    const char* ws_coop;                 // what the one-wavefront-per-query searches prune with: ws_tgth, or ws_tgt without the copy
-    float *partial, *rotated, *Rbar, *val, *Tmed, *slices, *b_vpn;
-    unsigned long long *served, *b_slack, *b_farq;
-    int *perm, *inv, *chunk_of;          // the per-chunk orders
-    unsigned int *b_surv, *b_vqmax;
-    CellWs cw; FlatWs fw;
-    template <class P> P* at(bool on, size_t off) const { return on ? reinterpret_cast<P*>(ws_src + off) : nullptr; }
-};
-
 // bounding boxes of a target table's 64-point chunks (without the Hilbert-ordered copy, the SRC_ROWS route: ws_tgt's own, again in front of every kernel that prunes with them)
-static int chunk_boxes(const CorrCtx& c, char* ws)
-{
-    hipLaunchKernelGGL(chunk_box_kernel, dim3(((c.Nt + kWave - 1) / kWave + 3) / 4, 1), dim3(256), 0, c.st, ws, (size_t)0, c.Nt);
-    UMEREG_CHECK_LAUNCH("chunk_box_kernel");
-    return UMEREG_OK;
-}
+static int chunk_boxes(const CorrCtx& c, char* ws) { return launch_chunk_box(ws, 0, c.Nt, 1, c.st); }
 
 // target: the search structure; source: only a processing order (wavefronts of queries that stay row-aligned with the target grid
 // under the consensus rotation); and the hypothesis orders of the consensus pass
@@ -274,43 +217,34 @@ static int structures_and_orders(const CorrCtx& c)
     // ~40 m long; a far query's bound lets dozens of them through, compact blobs a handful.
     // (compact 64-point chunks of the source where the consensus pass runs; the per-lane grid walk of small jobs keeps the row-aligned strips)
     const int curve_src = c.consensus && !(c.flags & UMEREG_CORR_SRC_ROWS) ? 1 : 0;
-    const int Ns = c.Ns, Nt = c.Nt, M = c.M;
+    const int Ns = c.Ns, Nt = c.Nt;
     const float radius = -(float)c.K;
-    hipLaunchKernelGGL(mean_rotation_kernel, dim3(1), dim3(256), 0, c.st, c.T, M, c.Rbar);
-    UMEREG_CHECK_LAUNCH("mean_rotation_kernel");
+    if (int rc = launch_mean_rotation(c)) return rc;
     if (c.coop_copy && Ns == Nt) {
         // the three structures as one batch of three (their workspaces are consecutive and, the clouds being equally large, equally
         // long): [rotated source | target | target], Hilbert-curve order for the first (if the consensus pass runs) and the third
-        hipLaunchKernelGGL(rotate_points_kernel, dim3((Ns + 255) / 256), dim3(256), 0, c.st, c.src_pts, Ns, c.Rbar, c.rotated, c.tgt_pts, 2);
-        UMEREG_CHECK_LAUNCH("rotate_points_kernel");
+        if (int rc = launch_rotate_points(c, true)) return rc;
         if (int rc = launch_prep(c.rotated, c.ws_src, 3, Ns, radius, c.st, curve_src | 4)) return rc;
     } else {
         if (int rc = launch_prep(c.tgt_pts, c.ws_tgt, 1, Nt, radius, c.st)) return rc;
         if (c.coop_copy)
             if (int rc = launch_prep(c.tgt_pts, c.ws_tgth, 1, Nt, radius, c.st, 1)) return rc;
-        hipLaunchKernelGGL(rotate_points_kernel, dim3((Ns + 255) / 256), dim3(256), 0, c.st, c.src_pts, Ns, c.Rbar, c.rotated, nullptr, 0);
-        UMEREG_CHECK_LAUNCH("rotate_points_kernel");
+        if (int rc = launch_rotate_points(c, false)) return rc;
         if (int rc = launch_prep(c.rotated, c.ws_src, 1, Ns, radius, c.st, curve_src)) return rc;
     }
-    if (c.coop_copy && chunk_boxes(c, c.ws_tgth) != UMEREG_OK) return UMEREG_ELAUNCH;
+    if (c.coop_copy)
+        if (int rc = chunk_boxes(c, c.ws_tgth)) return rc;
     if (c.ws.c_max && hipMemsetAsync(c.lat, 0, 256, c.st) != hipSuccess) { set_error("hipMemsetAsync(lattice header) failed"); return UMEREG_ELAUNCH; }
     if (!c.consensus) return UMEREG_OK;
     // the orders the consensus pass takes the hypotheses in: the median hypothesis, and per 64-point chunk of the source the order around it
-    int* gperm = c.at<int>(true, c.ws.gorder);           // the global order: only the fallback of the chunk orders (M > kChunkOrderMax)
-    float* err = (float*)(gperm + 2 * M);
-    float4* centroid = c.at<float4>(true, c.ws.centroid);
-    hipLaunchKernelGGL(hyp_median_kernel, dim3(12), dim3(1024), 0, c.st, c.T, M, c.Tmed);
-    UMEREG_CHECK_LAUNCH("hyp_median_kernel");
-    if (M > kChunkOrderMax) {
-        hipLaunchKernelGGL(hyp_err_kernel, dim3((M + 255) / 256), dim3(256), 0, c.st, c.T, M, (const unsigned int*)(c.ws_src + grid_ws(c.Ns).off_bbox), c.Tmed, err);
-        UMEREG_CHECK_LAUNCH("hyp_err_kernel");
-        hipLaunchKernelGGL(hyp_order_kernel, dim3((M + kWave - 1) / kWave), dim3(256), 0, c.st, err, M, gperm, gperm + M);
-        UMEREG_CHECK_LAUNCH("hyp_order_kernel");
+    // (the global order: only the fallback of the chunk orders)
+    if (int rc = launch_hyp_median(c)) return rc;
+    if (c.M > kChunkOrderMax) {
+        if (int rc = launch_hyp_err(c)) return rc;
+        if (int rc = launch_hyp_order(c)) return rc;
     }
-    hipLaunchKernelGGL(chunk_centroid_kernel, dim3((c.n_chunks + 3) / 4), dim3(256), 0, c.st, c.ws_src, c.src_pts, c.Ns, c.chunk_of, centroid);
-    UMEREG_CHECK_LAUNCH("chunk_centroid_kernel");
-    hipLaunchKernelGGL(hyp_order_chunk_kernel, dim3(c.n_chunks), dim3(1024), 0, c.st, c.T, M, c.Tmed, centroid, gperm, c.perm, c.inv);
-    UMEREG_CHECK_LAUNCH("hyp_order_chunk_kernel");
+    if (int rc = launch_chunk_centroid(c)) return rc;
+    if (int rc = launch_hyp_order_chunk(c)) return rc;
     corr_mark(1, c.st);
     return UMEREG_OK;
 }
@@ -318,34 +252,23 @@ static int structures_and_orders(const CorrCtx& c)
 // consensus pass: scores every (source point, hypothesis) whose image lies near the consensus image of the point, and queues the rest
 static int consensus_pass(const CorrCtx& c)
 {
-    const int Ns = c.Ns, Nt = c.Nt, M = c.M, K = c.K, flags = c.flags;
-    unsigned int* header = (unsigned int*)c.lat;
+    const int flags = c.flags;
     if (flags & UMEREG_CORR_CONSENSUS_V1) {
-        hipLaunchKernelGGL(corr_consensus_kernel, dim3((Ns + 1) / 2), dim3(2 * kWave), 2 * cons_lds_per_wave(c.cap), c.st, c.ws_tgt, c.ws_src, c.src_pts, c.vp4, c.vq4,
-                           c.T, c.Tmed, c.perm, Ns, Nt, M, K, c.cap, c.sigma, c.val, c.served, header + 7);
-        UMEREG_CHECK_LAUNCH("corr_consensus_kernel");
+        if (int rc = launch_corr_consensus(c)) return rc;
     } else {
         // images in empty parts of the target stage the ball of radius d_K + margin (in grid cells; flags bits 8..15 in
         // eighths of a cell, 0 = default, 255 = such points give up as in the first form)
         const int mf = (flags >> UMEREG_CORR_FAR_MARGIN_SHIFT) & 0xff;
         const float far_margin = mf == 0 ? kConsFarMarginCells : (mf == 0xff ? 0.f : (float)mf * 0.125f);
-        if (!c.coop_copy && chunk_boxes(c, c.ws_tgt) != UMEREG_OK) return UMEREG_ELAUNCH;
+        if (!c.coop_copy)
+            if (int rc = chunk_boxes(c, c.ws_tgt)) return rc;
         const float act_frac = (c.cell_pass && c.queries >= kCellMinQueries) ? 0.8f : 1.0f;
-        const Cons2Args ca = {c.ws_tgt, c.ws_coop, c.ws_src, c.src_pts, c.vp4, c.vq4, c.T, c.Tmed, c.perm, c.val, c.served, header + 7, nullptr,
-                              Ns, Nt, M, K, c.sigma, far_margin, c.dbg, act_frac};
-        // one wavefront per source point, kC2BlockWaves per workgroup
-        hipLaunchKernelGGL(corr_consensus2_kernel, dim3((Ns + kC2BlockWaves - 1) / kC2BlockWaves), dim3(kC2BlockWaves * kWave), kC2BlockWaves * cons2_lds_per_wave(), c.st, ca);
-        UMEREG_CHECK_LAUNCH("corr_consensus2_kernel");
+        if (int rc = launch_corr_consensus2(c, far_margin, act_frac)) return rc;
     }
     // who takes its leftovers: the grid kernel (few) or the lattice (many); decided on the device, both enqueued
-    hipLaunchKernelGGL(leftover_decide_kernel, dim3(1), dim3(1), 0, c.st, header, c.queries,
-                       (flags & UMEREG_CORR_LEFT_COOP) ? 1 : ((flags & UMEREG_CORR_LEFT_LATTICE) ? 2 : 0), c.ws.c_max,
-                       (c.cell_pass && c.queries < kCellMinQueries && !(flags & UMEREG_CORR_CELL_PASS)) ? kLeftMaxBound : kLeftMax);
-    UMEREG_CHECK_LAUNCH("leftover_decide_kernel");
-    if (hipMemsetAsync(c.partial, 0, (size_t)M * c.ws.n_chunks * 4, c.st) != hipSuccess) { set_error("hipMemsetAsync(partial) failed"); return UMEREG_ELAUNCH; }
-    hipLaunchKernelGGL(leftover_queue_kernel, dim3((unsigned)(((long)c.n_chunks * c.n_words + 3) / 4)), dim3(256), 0, c.st, c.ws_src, Ns, M, c.n_chunks, c.served,
-                       c.n_words, c.perm, c.lat, c.ws.c_max);
-    UMEREG_CHECK_LAUNCH("leftover_queue_kernel");
+    if (int rc = launch_leftover_decide(c, (c.cell_pass && c.queries < kCellMinQueries && !(flags & UMEREG_CORR_CELL_PASS)) ? kLeftMaxBound : kLeftMax)) return rc;
+    if (hipMemsetAsync(c.partial, 0, (size_t)c.M * c.ws.n_chunks * 4, c.st) != hipSuccess) { set_error("hipMemsetAsync(partial) failed"); return UMEREG_ELAUNCH; }
+    if (int rc = launch_leftover_queue(c)) return rc;
     corr_mark(2, c.st);
     return UMEREG_OK;
 }
@@ -358,67 +281,37 @@ static int consensus_pass(const CorrCtx& c)
 //                   (see bound_pass2_gate_kernel); the values go to the consensus pass's plane.
 static int lattice_build_and_cell_pass(const CorrCtx& c, bool second)
 {
-    const int Ns = c.Ns, Nt = c.Nt, M = c.M, K = c.K;
     const unsigned int c_max = c.ws.c_max;
     const bool far = c.far_cells && !second;                          // this pass bounds the queries of far cells
-    unsigned long long* plane = second ? c.b_farq : c.served;         // the pass's queries (a clear bit in `served`, a set one in the far-query plane) ...
-    const unsigned int* only = second ? c.b_surv : nullptr;           // ... of these hypotheses
-    if (second) hipLaunchKernelGGL(bound_pass2_gate_kernel, dim3(1), dim3(1), 0, c.st, (unsigned int*)c.lat);
+    if (second)
+        if (int rc = launch_bound_pass2_gate(c)) return rc;
     if (hipMemsetAsync(c.lat + 256, 0, lat_ws(c_max).off_wave_tot - 256, c.st) != hipSuccess) { set_error("hipMemsetAsync(lattice marks) failed"); return UMEREG_ELAUNCH; }
     if (c.bound && !second) {
         // the bound's slack / survivor flags / norms / far-query plane, and what every bounding kernel needs before it runs
         // (one fill for the block -- slack, flags, norms, maximum, plane: the norms are written after it --, one launch for both sets of rows:
         // every launch of this chain is 4-5 us of a KITTI-test call whether it finds work or not; and the cell pass's counters right behind it: CorrWs, adjacency 3)
         if (hipMemsetAsync(c.b_slack, 0, far ? c.ws.bound_bytes + (size_t)c_max * 4 : c.ws.bound_head, c.st) != hipSuccess) { set_error("hipMemsetAsync(slack) failed"); return UMEREG_ELAUNCH; }
-        hipLaunchKernelGGL(row_norm_kernel, dim3((Ns + 255) / 256 + (Nt + 255) / 256), dim3(256), 0, c.st, c.vp4, Ns, c.b_vpn, c.vq4, Nt, c.b_vqmax);
-        UMEREG_CHECK_LAUNCH("row_norm_kernel");
+        if (int rc = launch_row_norm(c)) return rc;
     }
     if (c.cell_pass && !far && hipMemsetAsync(c.cw.cnt, 0, (size_t)c_max * 4, c.st) != hipSuccess) { set_error("hipMemsetAsync(cell counters) failed"); return UMEREG_ELAUNCH; }
-    const long order_items = (long)((Ns + 255) / 256) * c.n_words;
-    const dim3 order_grid((unsigned)(order_items < 16384 ? order_items : 16384));
+    // the pass's queries: a clear bit in `served`, a set one in the far-query plane; without a consensus pass there is no plane, and every query is marked
     if (far) {
-        if (!c.coop_copy && chunk_boxes(c, c.ws_tgt) != UMEREG_OK) return UMEREG_ELAUNCH;
-        hipLaunchKernelGGL(lattice_far_table_kernel, dim3((c_max + 255) / 256), dim3(256), 0, c.st, c.ws_coop, c.ws_tgt, c.lat, c_max, Nt, c.sigma);
-        hipLaunchKernelGGL(lattice_mark_order_kernel, order_grid, dim3(256), 0, c.st, c.ws_tgt, c.ws_src, c.src_pts, c.T, Ns, Nt, M, c.lat, c_max, plane, c.n_words, c.perm,
-                           c.cw.cnt, false, nullptr, K, c.sigma, c.b_vpn, c.b_vqmax, c.b_slack, c.b_farq, c.served);
-    } else if (plane)
-        hipLaunchKernelGGL(lattice_mark_order_kernel, order_grid, dim3(256), 0, c.st, c.ws_tgt, c.ws_src, c.src_pts, c.T, Ns, Nt, M, c.lat, c_max, plane, c.n_words, c.perm,
-                           c.cw.cnt, second, only);
-    else
-        hipLaunchKernelGGL(lattice_mark_kernel, dim3((Ns + 255) / 256, (M + 15) / 16), dim3(256), 0, c.st, c.ws_tgt, c.src_pts, c.T, Ns, Nt, M, 16 /* hypotheses per thread */,
-                           c.lat, c_max, c.served, c.n_words, c.inv, c.chunk_of, c.cw.cnt);
-    UMEREG_CHECK_LAUNCH("lattice_mark_kernel");
-    hipLaunchKernelGGL(lattice_compact_kernel, dim3(kCompactBlocks), dim3(1024), 0, c.st, c.ws_tgt, c.lat, c_max, Nt);
-    UMEREG_CHECK_LAUNCH("lattice_compact_kernel");
-    if (!second) {
-        if (!c.coop_copy && chunk_boxes(c, c.ws_tgt) != UMEREG_OK) return UMEREG_ELAUNCH;
-        hipLaunchKernelGGL(lattice_posof_kernel, dim3((Nt + 255) / 256), dim3(256), 0, c.st, c.ws_tgt, c.lat, c_max, Nt);
+        if (!c.coop_copy)
+            if (int rc = chunk_boxes(c, c.ws_tgt)) return rc;
+        if (int rc = launch_lattice_far_table(c)) return rc;
     }
-    // (grids of the kernels that usually find nothing to do -- the leftovers go to the queue up to 2 M -- are kept small: a
-    // workgroup that returns at once still costs its launch, 50 us for 1 024 x 512 threads with 33 KiB of LDS each)
-    // (idle on jobs whose leftovers go to the queue -- every KITTI-test pair --, where its launch alone was 60 us of a pair's 3.7 ms
-    // beside other streams' kernels: the full grid only where the lattice is the likely path)
-    hipLaunchKernelGGL(lattice_list_kernel, dim3(second || c.queries >= kCellMinQueries ? 512 : 256), dim3(8 * kWave), 0, c.st, c.ws_coop, c.ws_tgt, c.lat, c_max, Nt, K,
-                       c.sigma, far ? 1 : 0);
-    UMEREG_CHECK_LAUNCH("lattice_list_kernel");
+    if (int rc = second || c.served ? launch_lattice_mark_order(c, second) : launch_lattice_mark(c)) return rc;
+    if (int rc = launch_lattice_compact(c)) return rc;
+    if (!second) {
+        if (!c.coop_copy)
+            if (int rc = chunk_boxes(c, c.ws_tgt)) return rc;
+        if (int rc = launch_lattice_posof(c)) return rc;
+    }
+    if (int rc = launch_lattice_list(c, second, second || c.queries >= kCellMinQueries)) return rc;
     if (!c.cell_pass) return UMEREG_OK;
-    const unsigned int nb = (c_max + 1023u) / 1024u;
-    hipLaunchKernelGGL(cell_apply_kernel<0>, dim3(nb), dim3(1024), 0, c.st, c.lat, c_max, c.cw);
-    hipLaunchKernelGGL(cell_blockscan_kernel, dim3(1), dim3(1024), 0, c.st, c.lat, c_max, c.cw);
-    hipLaunchKernelGGL(cell_apply_kernel<1>, dim3(nb), dim3(1024), 0, c.st, c.lat, c_max, c.cw);
-    UMEREG_CHECK_LAUNCH("cell_apply_kernel");
-    // (the second pass bounds nothing: no norms, no slack, no plane to write)
-    hipLaunchKernelGGL(cell_scatter_kernel, order_grid, dim3(256), 0, c.st, c.ws_tgt, c.ws_src, c.src_pts, c.T, Ns, Nt, M, c.lat, c_max, plane, c.n_words, c.perm, c.cw, K,
-                       c.sigma, second ? nullptr : c.b_vpn, second ? nullptr : c.b_vqmax, far ? c.b_slack : nullptr, second ? nullptr : c.b_farq, second, only);
-    UMEREG_CHECK_LAUNCH("cell_scatter_kernel");
-    const int dbg = second ? 0 : c.dbg;
-    unsigned long long* farq_clear = second ? c.b_farq : nullptr;
-    hipLaunchKernelGGL(corr_cell_kernel<false>, dim3(2816), dim3(kWave), cell_lds_per_wave(K, false), c.st, c.ws_tgt, c.src_pts, c.vp4, c.vq4, c.T, Ns, Nt, M, K, c.sigma,
-                       c.lat, c_max, c.cw, c.val, c.served, dbg, farq_clear);
-    hipLaunchKernelGGL(corr_cell_kernel<true>, dim3(2048), dim3(kWave), cell_lds_per_wave(K, true), c.st, c.ws_tgt, c.src_pts, c.vp4, c.vq4, c.T, Ns, Nt, M, K, c.sigma,
-                       c.lat, c_max, c.cw, c.val, c.served, dbg, farq_clear);
-    UMEREG_CHECK_LAUNCH("corr_cell_kernel");
-    return UMEREG_OK;
+    if (int rc = launch_cell_offsets(c)) return rc;
+    if (int rc = launch_cell_scatter(c, second)) return rc;
+    return launch_corr_cell(c, second);
 }
 
 // the queries the passes above left.  One lane per query: through the lattice's lists where there is a lattice (queueing what it cannot serve), the
@@ -426,56 +319,22 @@ static int lattice_build_and_cell_pass(const CorrCtx& c, bool second)
 // ... as a flat list of queries when they fit (header word 12 marks that the flat path ran), record by record otherwise
 static int score_queries(const CorrCtx& c)
 {
-    const int Ns = c.Ns, Nt = c.Nt, M = c.M, K = c.K, flags = c.flags;
-    const unsigned int c_max = c.ws.c_max;
-    if (c_max) corr_mark(3, c.st);                                  // (the lattice build and cell pass end where this stage begins)
-    const int hyp_per_wave = 2;   // 1..4 measured equal (6.4 us per hypothesis), 8: 6.7, 16: 7.3 (balance at the tail, parallelism)
-    const long n_waves = (long)c.n_chunks * ((M + hyp_per_wave - 1) / hyp_per_wave);
-    const dim3 score_grid((unsigned)((n_waves + c.waves - 1) / c.waves)), score_block(c.waves * kWave);
-    if (c_max) {
-        const dim3 lat_grid(score_grid.x < 4096u ? score_grid.x : 4096u);
-        hipLaunchKernelGGL((corr_score_kernel<unsigned short, true>), lat_grid, score_block, c.lds, c.st, c.ws_tgt, c.ws_src, c.src_pts, c.vp4, c.vq4, c.T, Ns, Nt, M, K, c.cap,
-                           c.sigma, hyp_per_wave, c.n_chunks, c.partial, c.lat, c_max, c.served, c.n_words, c.inv, c.cell_pass ? 1 : 0, c.perm);
-    } else if (c.idx16)
-        hipLaunchKernelGGL((corr_score_kernel<unsigned short, false>), score_grid, score_block, c.lds, c.st, c.ws_tgt, c.ws_src, c.src_pts, c.vp4, c.vq4, c.T, Ns, Nt, M, K, c.cap,
-                           c.sigma, hyp_per_wave, c.n_chunks, c.partial, nullptr, 0u, nullptr, 0, nullptr);
-    else
-        hipLaunchKernelGGL((corr_score_kernel<unsigned int, false>), score_grid, score_block, c.lds, c.st, c.ws_tgt, c.ws_src, c.src_pts, c.vp4, c.vq4, c.T, Ns, Nt, M, K, c.cap,
-                           c.sigma, hyp_per_wave, c.n_chunks, c.partial, nullptr, 0u, nullptr, 0, nullptr);
-    UMEREG_CHECK_LAUNCH("corr_score_kernel");
-    if (!c_max) return UMEREG_OK;
+    const int flags = c.flags;
+    if (c.ws.c_max) corr_mark(3, c.st);                             // (the lattice build and cell pass end where this stage begins)
+    if (int rc = launch_corr_score(c)) return rc;
+    if (!c.ws.c_max) return UMEREG_OK;
     corr_mark(4, c.st);
-    if ((flags & UMEREG_CORR_RECORD_STAGE) && !(flags & UMEREG_CORR_NO_FLAT)) {
-        // first one wavefront per record (a staged set of the record's neighbours, one lane per query); the records keep the lanes it could not serve
-        if (c.idx16)
-            hipLaunchKernelGGL(corr_score_record2_kernel<unsigned short>, dim3(4096), dim3(2 * kWave), 2 * rec_lds_per_wave<unsigned short>(c.cap), c.st, c.ws_coop, c.ws_src,
-                               c.src_pts, c.vp4, c.vq4, c.T, Ns, Nt, K, c.cap, c.sigma, c.n_chunks, c.partial, c.lat, c_max, c.dbg);
-        else
-            hipLaunchKernelGGL(corr_score_record2_kernel<unsigned int>, dim3(4096), dim3(2 * kWave), 2 * rec_lds_per_wave<unsigned int>(c.cap), c.st, c.ws_coop, c.ws_src,
-                               c.src_pts, c.vp4, c.vq4, c.T, Ns, Nt, K, c.cap, c.sigma, c.n_chunks, c.partial, c.lat, c_max, c.dbg);
-        UMEREG_CHECK_LAUNCH("corr_score_record2_kernel");
-    }
+    // first one wavefront per record (a staged set of the record's neighbours, one lane per query); the records keep the lanes it could not serve
+    if ((flags & UMEREG_CORR_RECORD_STAGE) && !(flags & UMEREG_CORR_NO_FLAT))
+        if (int rc = launch_corr_score_record2(c)) return rc;
     if (!(flags & UMEREG_CORR_NO_FLAT)) {
-        hipLaunchKernelGGL(leftover_flatten_kernel, dim3(256), dim3(256), 0, c.st, c.lat, c_max, c.fw);
-        UMEREG_CHECK_LAUNCH("leftover_flatten_kernel");
-        if (c.bound) {
-            hipLaunchKernelGGL(flat_bound_kernel<1>, dim3(2048), dim3(256), 0, c.st, c.ws_tgt, c.ws_src, c.src_pts, c.T, Ns, Nt, K, c.sigma, c.lat, c_max, c.fw, c.b_vpn,
-                               c.b_vqmax, c.b_slack, c.b_surv);
-            UMEREG_CHECK_LAUNCH("flat_bound_kernel");
-            hipLaunchKernelGGL(corr_score_flat_kernel<3>, dim3(kFlatBlocks), dim3(kCoopWaves * kWave), 0, c.st, c.ws_coop, c.ws_src, c.src_pts, c.vp4, c.vq4, c.T, Ns, Nt, K,
-                               c.sigma, c.lat, c_max, c.fw, c.b_vpn, c.b_vqmax, c.b_slack);
-        } else
-            hipLaunchKernelGGL(corr_score_flat_kernel<0>, dim3(kFlatBlocks), dim3(kCoopWaves * kWave), 0, c.st, c.ws_coop, c.ws_src, c.src_pts, c.vp4, c.vq4, c.T, Ns, Nt, K,
-                               c.sigma, c.lat, c_max, c.fw);
-        UMEREG_CHECK_LAUNCH("corr_score_flat_kernel");
-        hipLaunchKernelGGL(leftover_sum_kernel, dim3(256), dim3(256), 0, c.st, c.lat, c_max, c.fw, c.n_chunks, c.partial, 0);
-        UMEREG_CHECK_LAUNCH("leftover_sum_kernel");
+        if (int rc = launch_leftover_flatten(c)) return rc;
+        if (c.bound)
+            if (int rc = launch_flat_bound(c, 1)) return rc;
+        if (int rc = c.bound ? launch_corr_score_flat(c, 3, true) : launch_corr_score_flat(c, 0, false)) return rc;
+        if (int rc = launch_leftover_sum(c, false)) return rc;
     }
-    // (with the flat list in front this kernel only has work when that list overflowed -- more leftovers than half the job's queries --:
-    // 128 workgroups, its idle launch was 70 us per end-to-end pair at 512)
-    hipLaunchKernelGGL(corr_score_fallback_kernel, dim3((flags & UMEREG_CORR_NO_FLAT) ? 4096 : 128), dim3(kCoopWaves * kWave), 0, c.st, c.ws_coop, c.ws_src, c.src_pts,
-                       c.vp4, c.vq4, c.T, Ns, Nt, K, c.sigma, c.n_chunks, c.partial, c.lat, c_max);
-    UMEREG_CHECK_LAUNCH("corr_score_fallback_kernel");
+    if (int rc = launch_corr_score_fallback(c)) return rc;
     corr_mark(5, c.st);
     return UMEREG_OK;
 }
@@ -484,14 +343,9 @@ static int score_queries(const CorrCtx& c)
 // in processing order and, in arg-max mode, for the surviving hypotheses only)
 static int reduce_scores(const CorrCtx& c, bool last)
 {
-    const int n_slices = c.val ? (c.Ns + kValSlice - 1) / kValSlice : 0;
-    if (c.val) {
-        hipLaunchKernelGGL(corr_val_slices_kernel, dim3((c.M + 255) / 256, n_slices), dim3(256), 0, c.st, c.val, c.M, c.Ns, c.ws_src, c.slices, last ? c.perm : nullptr,
-                           last ? c.b_surv : nullptr);
-        UMEREG_CHECK_LAUNCH("corr_val_slices_kernel");
-    }
-    hipLaunchKernelGGL(corr_reduce_kernel, dim3((c.M + 3) / 4), dim3(256), 0, c.st, c.partial, c.M, c.n_chunks, c.Ns, c.slices, n_slices, c.inv, c.scores);
-    UMEREG_CHECK_LAUNCH("corr_reduce_kernel");
+    if (c.val)
+        if (int rc = launch_corr_val_slices(c, last)) return rc;
+    if (int rc = launch_corr_reduce(c)) return rc;
     if (last) corr_mark(6, c.st);
     return UMEREG_OK;
 }
@@ -499,25 +353,15 @@ static int reduce_scores(const CorrCtx& c, bool last)
 // arg-max mode: the scores so far decide which hypotheses need their bounded queries; those queries, exactly; then (the caller) the sums once more
 static int bounded_recompute(const CorrCtx& c)
 {
-    const int Ns = c.Ns, Nt = c.Nt, M = c.M, K = c.K;
-    const unsigned int c_max = c.ws.c_max;
     if (int rc = reduce_scores(c, false)) return rc;
-    hipLaunchKernelGGL(bound_survivors_kernel, dim3(1), dim3(1024), 0, c.st, c.scores, c.b_slack, M, Ns, c.b_surv, (unsigned int*)c.lat);
-    UMEREG_CHECK_LAUNCH("bound_survivors_kernel");
-    hipLaunchKernelGGL(flat_bound_kernel<2>, dim3(2048), dim3(256), 0, c.st, c.ws_tgt, c.ws_src, c.src_pts, c.T, Ns, Nt, K, c.sigma, c.lat, c_max, c.fw, c.b_vpn, c.b_vqmax,
-                       c.b_slack, c.b_surv);
-    UMEREG_CHECK_LAUNCH("flat_bound_kernel");
-    hipLaunchKernelGGL(corr_score_flat_kernel<3>, dim3(kFlatBlocks), dim3(kCoopWaves * kWave), 0, c.st, c.ws_coop, c.ws_src, c.src_pts, c.vp4, c.vq4, c.T, Ns, Nt, K, c.sigma,
-                       c.lat, c_max, c.fw);
-    UMEREG_CHECK_LAUNCH("corr_score_flat_kernel");
-    hipLaunchKernelGGL(leftover_sum_kernel, dim3(256), dim3(256), 0, c.st, c.lat, c_max, c.fw, c.n_chunks, c.partial, 1);
-    UMEREG_CHECK_LAUNCH("leftover_sum_kernel");
+    if (int rc = launch_bound_survivors(c)) return rc;
+    if (int rc = launch_flat_bound(c, 2)) return rc;
+    if (int rc = launch_corr_score_flat(c, 3, false)) return rc;
+    if (int rc = launch_leftover_sum(c, true)) return rc;
     if (c.far_cells) {
         // ... and the queries bounded for lying in far lattice cells: through the lattice + cell pass once more, then one by one what that left
         if (int rc = lattice_build_and_cell_pass(c, true)) return rc;
-        hipLaunchKernelGGL(far_recompute_kernel, dim3(1024), dim3(kCoopWaves * kWave), 0, c.st, c.ws_coop, c.ws_src, c.src_pts, c.vp4, c.vq4, c.T, Ns, Nt, M, K, c.sigma,
-                           c.lat, c_max, c.b_farq, c.n_words, c.perm, c.b_surv, c.val);
-        UMEREG_CHECK_LAUNCH("far_recompute_kernel");
+        if (int rc = launch_far_recompute(c)) return rc;
     }
     return UMEREG_OK;
 }
@@ -549,6 +393,7 @@ UMEREG_API int umereg_corr_scores_ex_f32(const float* src_pts, const float* tgt_
     c.partial = c.at<float>(true, ws.partial); c.rotated = c.at<float>(true, ws.rotated); c.Rbar = c.at<float>(true, ws.rbar); c.lat = c.at<char>(true, ws.lat);
     c.val = c.at<float>(c.consensus, ws.val); c.served = c.at<unsigned long long>(c.consensus, ws.served); c.Tmed = c.at<float>(c.consensus, ws.tmed);
     c.slices = c.at<float>(c.consensus, ws.slices); c.perm = c.at<int>(c.consensus, ws.perm); c.inv = c.at<int>(c.consensus, ws.inv); c.chunk_of = c.at<int>(c.consensus, ws.chunk_of);
+    c.gorder = c.at<int>(c.consensus, ws.gorder); c.centroid = c.at<float4>(c.consensus, ws.centroid);
     c.b_slack = c.at<unsigned long long>(c.bound, ws.b_slack); c.b_surv = c.at<unsigned int>(c.bound, ws.b_surv); c.b_vpn = c.at<float>(c.bound, ws.b_vpn);
     c.b_vqmax = c.at<unsigned int>(c.bound, ws.b_vqmax); c.b_farq = c.at<unsigned long long>(c.bound, ws.b_farq);
     if (c.cell_pass) c.cw = cell_ws(c.at<char>(true, ws.cell), ws.c_max, c.queries);

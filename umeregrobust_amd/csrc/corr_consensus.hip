@@ -1,7 +1,8 @@
 // corr_consensus.hip -- SURVEY 8(f1), the consensus pass of the hypothesis scores (utils/loc_utils.py:592-637): the mean rotation
 // and the processing orders of source points and hypotheses, then one wavefront per SOURCE POINT with one lane per hypothesis
-// (corr_consensus_kernel, round 2; corr_consensus2_kernel, round 3: what runs).  Launched by umereg_corr_scores_ex_f32 (corr.hip).
-#include "corr_kernels.h"
+// (corr_consensus_kernel, round 2; corr_consensus2_kernel, round 3: what runs).  Each kernel is followed by its launcher, which
+// umereg_corr_scores_ex_f32 (corr.hip) calls.
+#include "corr_host.h"
 
 namespace umereg {
 // ---- processing order of the source points ---------------------------------------------------------
@@ -31,6 +32,12 @@ __global__ __launch_bounds__(256) void mean_rotation_kernel(const float* __restr
         __syncthreads();
     }
 }
+int launch_mean_rotation(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(mean_rotation_kernel, dim3(1), dim3(256), 0, c.st, c.T, c.M, c.Rbar);
+    UMEREG_CHECK_LAUNCH("mean_rotation_kernel");
+    return UMEREG_OK;
+}
 
 __global__ __launch_bounds__(256) void rotate_points_kernel(const float* __restrict__ pts, int N, const float* __restrict__ Rbar,
                                                             float* __restrict__ out, const float* __restrict__ tgt, int n_tgt_copies)
@@ -47,6 +54,14 @@ __global__ __launch_bounds__(256) void rotate_points_kernel(const float* __restr
         const float v = fmaf(Rbar[r * 3 + 2], z, fmaf(Rbar[r * 3 + 1], y, Rbar[r * 3] * x));
         out[(size_t)i * 3 + r] = v == v && fabsf(v) < 1e30f ? v : 0.f;
     }
+}
+// with_target_copies: the two copies of the target behind the rotated source (equal-sized clouds, see above)
+int launch_rotate_points(const CorrCtx& c, bool with_target_copies)
+{
+    hipLaunchKernelGGL(rotate_points_kernel, dim3((c.Ns + 255) / 256), dim3(256), 0, c.st, c.src_pts, c.Ns, c.Rbar, c.rotated, with_target_copies ? c.tgt_pts : nullptr,
+                       with_target_copies ? 2 : 0);
+    UMEREG_CHECK_LAUNCH("rotate_points_kernel");
+    return UMEREG_OK;
 }
 
 // ---- consensus pass: one wavefront per SOURCE POINT, one lane per hypothesis -----------------------------------------
@@ -105,6 +120,12 @@ __global__ __launch_bounds__(1024) void hyp_median_kernel(const float* __restric
         Tmed[e] = f == f && fabsf(f) < 1e30f ? f : ((e % 5 == 0) ? 1.f : 0.f);     // NaN / inf: identity entry
     }
 }
+int launch_hyp_median(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(hyp_median_kernel, dim3(12), dim3(1024), 0, c.st, c.T, c.M, c.Tmed);
+    UMEREG_CHECK_LAUNCH("hyp_median_kernel");
+    return UMEREG_OK;
+}
 
 // distance of every hypothesis from the median one (the source bounding box here is that of the consensus-ROTATED
 // copy the source order was built from: same radius, and the centre only matters roughly)
@@ -124,6 +145,14 @@ __global__ __launch_bounds__(256) void hyp_err_kernel(const float* __restrict__ 
     }
     const float e = sqrtf(dt2) + sqrtf(fro) * 2.0f * r0;
     err[h] = e == e ? e : 3.0e38f;                                                      // NaN hypotheses last
+}
+// (err: the third array of the global order's region, CorrCtx::gorder)
+int launch_hyp_err(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(hyp_err_kernel, dim3((c.M + 255) / 256), dim3(256), 0, c.st, c.T, c.M, (const unsigned int*)(c.ws_src + grid_ws(c.Ns).off_bbox), c.Tmed,
+                       (float*)(c.gorder + 2 * c.M));
+    UMEREG_CHECK_LAUNCH("hyp_err_kernel");
+    return UMEREG_OK;
 }
 
 // rank counting (ties by index) over the M distances: perm[rank] = h, inv[h] = rank.  64 hypotheses per workgroup, the
@@ -151,6 +180,12 @@ __global__ __launch_bounds__(256) void hyp_order_kernel(const float* __restrict_
         inv[h] = rk;
     }
 }
+int launch_hyp_order(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(hyp_order_kernel, dim3((c.M + kWave - 1) / kWave), dim3(256), 0, c.st, (const float*)(c.gorder + 2 * c.M), c.M, c.gorder, c.gorder + c.M);
+    UMEREG_CHECK_LAUNCH("hyp_order_kernel");
+    return UMEREG_OK;
+}
 
 // ---- per-neighbourhood hypothesis orders -----------------------------------------------------------------------------
 // How far a hypothesis moves a source point from its consensus image depends on where the point is (a rotation error of
@@ -176,6 +211,12 @@ __global__ __launch_bounds__(256) void chunk_centroid_kernel(const char* __restr
     x = wave_sum_f(x); y = wave_sum_f(y); z = wave_sum_f(z);
     const float inv_n = 1.0f / (float)min(kWave, Ns - chunk * kWave);
     if (lane == 0) centroid[chunk] = make_float4(x * inv_n, y * inv_n, z * inv_n, 0.f);
+}
+int launch_chunk_centroid(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(chunk_centroid_kernel, dim3((c.n_chunks + 3) / 4), dim3(256), 0, c.st, c.ws_src, c.src_pts, c.Ns, c.chunk_of, c.centroid);
+    UMEREG_CHECK_LAUNCH("chunk_centroid_kernel");
+    return UMEREG_OK;
 }
 
 // one workgroup per chunk: key = (displacement of the centroid, hypothesis), bitonic sort in LDS.  (The sort key keeps the
@@ -230,11 +271,28 @@ __global__ __launch_bounds__(1024) void hyp_order_chunk_kernel(const float* __re
         ic[h] = r;
     }
 }
+int launch_hyp_order_chunk(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(hyp_order_chunk_kernel, dim3(c.n_chunks), dim3(1024), 0, c.st, c.T, c.M, c.Tmed, c.centroid, c.gorder, c.perm, c.inv);
+    UMEREG_CHECK_LAUNCH("hyp_order_chunk_kernel");
+    return UMEREG_OK;
+}
 
 // (Images in empty parts of the target -- partly overlapping clouds -- are not served here: with D = d_K + margin the coverage
 // of a half-overlapping pair went 78 % -> 91 %, but their stages are full and the pass got slower than the lattice it relieves,
 // 15 ms vs 7.5 ms.  Such source points give up below and are left to the lattice.)
+constexpr int kConsCap = 256;            // staged target points per source point
 constexpr int kConsIdxBits = 9;          // low bits of a key's index word = position in the stage (kConsCap <= 512)
+// (the consensus pass's level-0 histogram has one more row than kBins: the overflow bin)
+__host__ __device__ constexpr size_t cons_list_bytes(int cap)
+{
+    return knn_lds_per_wave(cap, 4) > (size_t)(kBins + 1) * kWave * 4 ? knn_lds_per_wave(cap, 4) : (size_t)(kBins + 1) * kWave * 4;
+}
+__host__ __device__ constexpr size_t cons_lds_per_wave(int cap)
+{
+    // key list with a 32-bit index plane (original index << 9 | stage position) / histogram; stage; dot products; distances from the centre
+    return cons_list_bytes(cap) + (size_t)(kConsCap + 4) * 16 + (size_t)(kConsCap + 4) * 4 * 2;
+}
 
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 4))) void corr_consensus_kernel(
     const char* __restrict__ ws_tgt, const char* __restrict__ ws_src, const float* __restrict__ src_pts, const float4* __restrict__ vp4,
@@ -553,6 +611,14 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     }
     if (lane == 0 && stats) atomicAdd(stats, n_served);
 }
+// (one wavefront per source point, two per workgroup; header word 7 counts the queries served)
+int launch_corr_consensus(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(corr_consensus_kernel, dim3((c.Ns + 1) / 2), dim3(2 * kWave), 2 * cons_lds_per_wave(c.cap), c.st, c.ws_tgt, c.ws_src, c.src_pts, c.vp4, c.vq4,
+                       c.T, c.Tmed, c.perm, c.Ns, c.Nt, c.M, c.K, c.cap, c.sigma, c.val, c.served, (unsigned int*)c.lat + 7);
+    UMEREG_CHECK_LAUNCH("corr_consensus_kernel");
+    return UMEREG_OK;
+}
 
 // ---- consensus pass, second form (round 3) ----------------------------------------------------------------------------
 // Same contract as corr_consensus_kernel (val / served / stats, exact or left to the other structures), rebuilt around three
@@ -586,9 +652,35 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
 #ifndef UMEREG_CONS2_TIE_FAST
 #define UMEREG_CONS2_TIE_FAST 1
 #endif
-#ifndef UMEREG_C2_ABLATE
-#define UMEREG_C2_ABLATE 0   // timing experiments only (results wrong; tools/r05_cons2_ablate.sh): 1 no steps at all (set-up alone), 2 no rank-counting
-#endif                       // steps' work, 4 no histogram steps' sweeps, 8 no second sweep, 16 no sure-in prefix, 32 no first-sweep histogram adds, 256 no trimming of the tie list
+#ifndef UMEREG_CONS2_CAP
+#define UMEREG_CONS2_CAP 252
+#endif
+#ifndef UMEREG_CONS2_TIE
+#define UMEREG_CONS2_TIE 8
+#endif
+#ifndef UMEREG_CONS2_WAVES
+#define UMEREG_CONS2_WAVES 3
+#endif
+#ifndef UMEREG_CONS2_BLOCK_WAVES
+#define UMEREG_CONS2_BLOCK_WAVES 1
+#endif
+constexpr int kC2BlockWaves = UMEREG_CONS2_BLOCK_WAVES;   // wavefronts per workgroup of the consensus pass (1 or 2: __launch_bounds__(128))
+constexpr int kCons2Cap = UMEREG_CONS2_CAP;   // staged target points per source point (<= 252: byte counters, see (2) above)
+constexpr int kC2Tie = UMEREG_CONS2_TIE; // list entries per lane for the candidates of the K-th neighbour's bin (the cell pass's: kCons2Tie; here the LDS budget decides the wavefronts per SIMD)
+constexpr int kC2Slots = (kCons2Cap + 4 + 3) & ~3;   // stage slots: the points + one quad of far-point padding
+static_assert(kCons2Cap <= 252 && kCons2Cap % 4 == 0, "byte counters; quad-aligned cap");
+constexpr size_t kC2MinWork = (size_t)kCoopCap * 8 * 2 + 256 > (size_t)kCons2Cap * 16 ? (size_t)kCoopCap * 8 * 2 + 256 : (size_t)kCons2Cap * 16;
+constexpr size_t kC2ListWork = (size_t)kCons2HistWords * kWave * 4 + (size_t)kC2Tie * kWave * 8;
+// histogram + tie list; during set-up the same bytes hold the collected raw points and coop_knn's two key lists + histogram
+constexpr size_t kCons2WorkBytes = kC2ListWork > kC2MinWork ? kC2ListWork : kC2MinWork;
+__host__ __device__ constexpr size_t cons2_lds_per_wave() { return kCons2WorkBytes + (size_t)kC2Slots * 16 + (size_t)kC2Slots * 4 * 2; }
+static_assert(kC2BlockWaves * cons2_lds_per_wave() <= 64 * 1024, "a workgroup of the consensus pass must fit the LDS a workgroup can have");
+// (its arguments as one struct; `reserved` is always nullptr: it keeps the kernel-argument layout of the measured kernel)
+struct Cons2Args {
+    const char* ws_tgt; const char* ws_coop; const char* ws_src; const float* src_pts; const float4* vp4; const float4* vq4; const float* T;
+    const float* Tmed; const int* perm; float* val; unsigned long long* served; unsigned int* stats; unsigned int* reserved;
+    int Ns, Nt, M, K; float sigma, far_margin_cells; int dbg; float act_frac;
+};
 constexpr int kCons2Zone = UMEREG_CONS2_ZONE;           // zone size up to which the rank-counting path is taken (a multiple of 4)
 // (the path always ranks kCons2Zone slots; its zones hold 5 points on average: 12 -> 8 slots, 66 -> 28 comparisons per step: a KITTI-test call 1.84 -> 1.78 ms,
 // LoKITTI-size 11.9 -> 11.8; 4 / 16 slots: 1.89 / 1.91)
@@ -1159,6 +1251,16 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(UMEREG_CONS
         cons2_point(slot_n, lds + (size_t)wave * cons2_lds_per_wave(), lane, args.ws_tgt, args.ws_coop, args.ws_src, args.src_pts, args.vp4, args.vq4,
                     args.T, args.Tmed, args.perm, args.Ns, args.Nt, args.M, args.K, args.sigma, args.far_margin_cells, args.val, args.served,
                     args.stats, args.dbg, args.act_frac);
+}
+// far_margin_cells, act_frac: the caller's routing (consensus_pass, corr.hip); header word 7 counts the queries served
+int launch_corr_consensus2(const CorrCtx& c, float far_margin_cells, float act_frac)
+{
+    const Cons2Args ca = {c.ws_tgt, c.ws_coop, c.ws_src, c.src_pts, c.vp4, c.vq4, c.T, c.Tmed, c.perm, c.val, c.served, (unsigned int*)c.lat + 7, nullptr,
+                          c.Ns, c.Nt, c.M, c.K, c.sigma, far_margin_cells, c.dbg, act_frac};
+    // one wavefront per source point, kC2BlockWaves per workgroup
+    hipLaunchKernelGGL(corr_consensus2_kernel, dim3((c.Ns + kC2BlockWaves - 1) / kC2BlockWaves), dim3(kC2BlockWaves * kWave), kC2BlockWaves * cons2_lds_per_wave(), c.st, ca);
+    UMEREG_CHECK_LAUNCH("corr_consensus2_kernel");
+    return UMEREG_OK;
 }
 
 }  // namespace umereg

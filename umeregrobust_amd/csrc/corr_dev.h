@@ -1,7 +1,7 @@
 // corr_dev.h -- device-side building blocks shared by the translation units of SURVEY 8(f1), hypothesis selection
 // (corr.hip: the call and its file map).  Everything here is inline device code, plain structs or constants; the kernels
-// themselves live in corr_knn.hip, corr_consensus.hip, corr_lattice.hip and corr_leftover.hip and are declared in
-// corr_kernels.h.  What only ONE of those files needs stays in that file.
+// themselves live in corr_knn.hip, corr_consensus.hip, corr_lattice.hip and corr_leftover.hip, each beside the host function that
+// launches it (declared in corr_host.h).  What only ONE of those files needs stays in that file.
 #pragma once
 #include <type_traits>
 
@@ -11,6 +11,9 @@ namespace umereg {
 #ifndef UMEREG_F1_ABLATE
 #define UMEREG_F1_ABLATE 0   // timing experiments only (tools/exp_f1_ablate.sh): 1 skip epilogue, 2 skip append, 4 skip histogram, 8 skip grid fallback
 #endif
+#ifndef UMEREG_C2_ABLATE
+#define UMEREG_C2_ABLATE 0   // timing experiments only (results wrong; tools/r05_cons2_ablate.sh): 1 no steps at all (set-up alone), 2 no rank-counting
+#endif                       // steps' work, 4 no histogram steps' sweeps, 8 no second sweep, 16 no sure-in prefix, 32 no first-sweep histogram adds, 256 no trimming of the tie list
 constexpr int kBins = 32;
 constexpr float kKnnMaxCells = 6.0f;   // upper bound of the first search radius, in cells
 constexpr float kKnnTarget = 4.0f;     // expected points in the first search ball, in units of K
@@ -591,9 +594,6 @@ __device__ __forceinline__ float cauchy_weight_fast(float d2, float inv_sigma2)
     return __builtin_amdgcn_rcpf(fmaf(d2, inv_sigma2, 1.0f));
 }
 
-// (the consensus pass itself: corr_consensus.hip)
-constexpr int kConsCap = 256;            // staged target points per source point
-
 // (per-neighbourhood hypothesis orders: corr_consensus.hip)
 constexpr int kChunkOrderMax = 8192;        // hypotheses a chunk order can sort in LDS (beyond: the global order for every chunk)
 
@@ -820,41 +820,8 @@ __device__ __forceinline__ int coop_knn(const float4* __restrict__ P4s, const fl
     return cnt;
 }
 
-// (the consensus pass's level-0 histogram has one more row than kBins: the overflow bin)
-__host__ __device__ constexpr size_t cons_list_bytes(int cap)
-{
-    return knn_lds_per_wave(cap, 4) > (size_t)(kBins + 1) * kWave * 4 ? knn_lds_per_wave(cap, 4) : (size_t)(kBins + 1) * kWave * 4;
-}
-__host__ __device__ constexpr size_t cons_lds_per_wave(int cap)
-{
-    // key list with a 32-bit index plane (original index << 9 | stage position) / histogram; stage; dot products; distances from the centre
-    return cons_list_bytes(cap) + (size_t)(kConsCap + 4) * 16 + (size_t)(kConsCap + 4) * 4 * 2;
-}
-#ifndef UMEREG_CONS2_CAP
-#define UMEREG_CONS2_CAP 252
-#endif
-#ifndef UMEREG_CONS2_TIE
-#define UMEREG_CONS2_TIE 8
-#endif
-#ifndef UMEREG_CONS2_WAVES
-#define UMEREG_CONS2_WAVES 3
-#endif
-#ifndef UMEREG_CONS2_BLOCK_WAVES
-#define UMEREG_CONS2_BLOCK_WAVES 1
-#endif
-constexpr int kC2BlockWaves = UMEREG_CONS2_BLOCK_WAVES;   // wavefronts per workgroup of the consensus pass (1 or 2: __launch_bounds__(128))
-constexpr int kCons2Cap = UMEREG_CONS2_CAP;   // staged target points per source point (<= 252: byte counters, see above)
 constexpr int kCons2Tie = 8;             // list entries per lane for the candidates of the K-th neighbour's bin (cell pass)
-constexpr int kC2Tie = UMEREG_CONS2_TIE; // the same in the consensus pass (its LDS budget decides the wavefronts per SIMD)
-constexpr int kC2Slots = (kCons2Cap + 4 + 3) & ~3;   // stage slots: the points + one quad of far-point padding
-static_assert(kCons2Cap <= 252 && kCons2Cap % 4 == 0, "byte counters; quad-aligned cap");
 constexpr int kCons2HistWords = 9;       // 36 byte counters per lane: bin t = 0 below the range, 1..32, 33 at or beyond it
-constexpr size_t kC2MinWork = (size_t)kCoopCap * 8 * 2 + 256 > (size_t)kCons2Cap * 16 ? (size_t)kCoopCap * 8 * 2 + 256 : (size_t)kCons2Cap * 16;
-constexpr size_t kC2ListWork = (size_t)kCons2HistWords * kWave * 4 + (size_t)kC2Tie * kWave * 8;
-// histogram + tie list; during set-up the same bytes hold the collected raw points and coop_knn's two key lists + histogram
-constexpr size_t kCons2WorkBytes = kC2ListWork > kC2MinWork ? kC2ListWork : kC2MinWork;
-__host__ __device__ constexpr size_t cons2_lds_per_wave() { return kCons2WorkBytes + (size_t)kC2Slots * 16 + (size_t)kC2Slots * 4 * 2; }
-
 __device__ __forceinline__ int cons2_bin(float d2, float lo, float sc)
 {
     // (d2 - lo) * sc + 1 truncated: 0 <=> below lo (then certainly d2 < lo), 1..32 the bins, >= 33 at or beyond the range
@@ -884,8 +851,9 @@ __device__ __forceinline__ float cons2_edge(int b, float lo, float sc, float wid
 }
 __device__ __forceinline__ void cons2_hist_add(unsigned int* hist, int lane, int t)
 {
-#ifdef UMEREG_C2_ABLATE
-    if (UMEREG_C2_ABLATE & 32) { asm volatile("" :: "v"(t)); return; }       // (timing experiment: the bin is computed, the counter not touched)
+#if UMEREG_C2_ABLATE & 32
+    asm volatile("" :: "v"(t));                                            // (timing experiment: the bin is computed, the counter not touched)
+    return;
 #endif
     atomicAdd(&hist[(t >> 2) * kWave + lane], 1u << ((t & 3) * 8));       // lane-private byte counter (ds_add_u32)
 }
@@ -927,22 +895,6 @@ __device__ __forceinline__ void cons2_scan(const unsigned int* hist, int lane, i
     inbin = any ? inb : 0;
 }
 
-// the same with 16-bit counters (two per word, 18 words per lane): stages of up to 65 535 points (the cell pass's long lists)
-constexpr int kHist16Words = 18;
-
-// who takes what the consensus pass left (header word 8): 1 = the grid kernel (few leftovers: they sit in a few
-// thousand (hypothesis, chunk) wavefronts), 0 = the candidate lattice (many: hypotheses that do not agree, clouds that
-// barely overlap -- queries in empty parts of the target, where lists pay off).  Both sets of kernels are enqueued;
-// the ones not chosen return at once.
-#ifndef UMEREG_LEFT_MAX
-#define UMEREG_LEFT_MAX 3000000u
-#endif
-constexpr unsigned int kLeftMax = UMEREG_LEFT_MAX;      // (2^21 until the end of round 3: over 32 half-overlapping KITTI-test pairs, whose leftovers straddle
-                                                        // 2 M, f1 averages 7.5 ms with 2^21 and 6.4 with 3 M or 4.5 M -- the flat list holds half the job's queries now)   // (measured round 3, with the Hilbert-ordered copy: 0.26 M leftovers 2.2 ms through the queue against 3.2 through the lattice, 1.6 M 7.8 against 8.1)
-#ifndef UMEREG_CELL_STAGE
-#define UMEREG_CELL_STAGE 256
-#endif
-constexpr int kCellStage = UMEREG_CELL_STAGE;       // stage slots of the short-list instance (a group of cells shares them)
 #ifndef UMEREG_CELL_CHUNK
 #define UMEREG_CELL_CHUNK 512
 #endif
@@ -966,11 +918,6 @@ struct CellWs {
 constexpr unsigned int kCellChunkLong = UMEREG_CELL_CHUNK_LONG;   // the same for the long-list instance: its steps cost three times a short one's, its cells hold thousands of
                                                                   // queries, and its items are few -- with 512 per item the kernel lasted as long as its slowest two items
 
-__host__ __device__ inline size_t cell_d2_plane(int K, bool lng)
-{
-    const size_t hw = (size_t)(lng ? kHist16Words : kCons2HistWords) * kWave * 4;
-    return (size_t)K * kWave * 4 > hw ? (size_t)K * kWave * 4 : hw;
-}
 struct FlatWs {
     unsigned int* rbase;   // [records] first query slot of the record
     unsigned int* qlist;   // [slots] record << 6 | lane
@@ -979,17 +926,6 @@ struct FlatWs {
     unsigned char* qfar;   // [slots] 1 = the search bounded this entry instead (nothing within kBoundBoxSigmas sigma of its image: see corr_score_flat_kernel)
     unsigned int slots;
 };
-
-// (one wavefront per record: corr_leftover.hip)
-constexpr int kRecStage = 768;           // staged target points per record
-
-template <class IdxT>
-__host__ __device__ constexpr size_t rec_lds_per_wave(int cap)
-{
-    // list / histogram region (also coop_knn's two key lists + its histogram: 4 352 B) + the record's queries + the stage
-    return (knn_lds_per_wave(cap, sizeof(IdxT)) > (size_t)(2 * kCoopCap * 8 + kWave * 4) ? knn_lds_per_wave(cap, sizeof(IdxT)) : (size_t)(2 * kCoopCap * 8 + kWave * 4)) +
-           (size_t)kWave * 16 + (size_t)(kRecStage + 4) * 16;
-}
 
 // sums of the consensus pass's terms over slices of kValSlice source points (fixed order inside a slice)
 constexpr int kValSlice = 64;

@@ -1,9 +1,10 @@
 // corr_knn.hip -- SURVEY 8(f1), the feature side: pytorch3d.ops.knn_points as used at reference utils/loc_utils.py:580,623 and
 // evaluate.py:272,274 (one lane per query on the uniform grid; K = 1 by sub-wavefront groups), feature_spatial_var
 // (utils/loc_utils.py:579-585), the weighted features (utils/loc_utils.py:661,664-665) and the bounding boxes of a sorted table's
-// 64-point chunks.  Kernels + the C entry points that launch only them.  The search itself (knn_wave and its selection of the K
-// smallest keys) is in corr_dev.h: the per-hypothesis score kernel of corr_leftover.hip runs the same code.
-#include "corr_kernels.h"
+// 64-point chunks.  Kernels + the C entry points that launch only them; the chunk boxes, which the score call (corr.hip) needs too,
+// go through launch_chunk_box here and there.  The search itself (knn_wave and its selection of the K smallest keys) is in corr_dev.h:
+// the per-hypothesis score kernel of corr_leftover.hip runs the same code.
+#include "corr_host.h"
 
 namespace umereg {
 // sort this lane's keys ascending (selection sort in LDS; K is small)
@@ -59,12 +60,6 @@ __global__ __launch_bounds__(256) void knn_points_kernel(const char* __restrict_
         }
     }
 }
-template __global__ __launch_bounds__(256) void knn_points_kernel<unsigned short>(const char* __restrict__ ws, size_t ws_stride,
-                                                         const float* __restrict__ p1, int n1, int n2, int K, int cap,
-                                                         int ordered, float* __restrict__ dists, int64_t* __restrict__ idx);
-template __global__ __launch_bounds__(256) void knn_points_kernel<unsigned int>(const char* __restrict__ ws, size_t ws_stride,
-                                                         const float* __restrict__ p1, int n1, int n2, int K, int cap,
-                                                         int ordered, float* __restrict__ dists, int64_t* __restrict__ idx);
 
 // K = 1 (evaluate.py:272,274: every raw point takes the feature of its nearest network point): eight lanes per query walk the rows
 // of the cells a box of half-width rho around the query touches (consecutive table entries per row), the nearest candidate is the minimum
@@ -187,12 +182,6 @@ __global__ __launch_bounds__(256) void spatial_var_kernel(const char* __restrict
     }
     if (valid) out[(size_t)b * N + me] = acc / (float)(K - 1);
 }
-template __global__ __launch_bounds__(256) void spatial_var_kernel<unsigned short>(const char* __restrict__ ws, size_t ws_stride,
-                                                          const float4* __restrict__ feat4, int N, int K, int cap,
-                                                          int lanes_used, float* __restrict__ out);
-template __global__ __launch_bounds__(256) void spatial_var_kernel<unsigned int>(const char* __restrict__ ws, size_t ws_stride,
-                                                          const float4* __restrict__ feat4, int N, int K, int cap,
-                                                          int lanes_used, float* __restrict__ out);
 
 // ---- weighted features: (feat - m) * w,  m = mean over BOTH clouds' points (utils/loc_utils.py:661,664-665)
 __global__ __launch_bounds__(256) void colsum_partial_kernel(const float* __restrict__ a, int na, const float* __restrict__ b,
@@ -256,6 +245,13 @@ __global__ __launch_bounds__(256) void chunk_box_kernel(char* __restrict__ ws, s
         box[2 * c] = make_float4(lo[0], lo[1], lo[2], 0.f);
         box[2 * c + 1] = make_float4(hi[0], hi[1], hi[2], 0.f);
     }
+}
+// (one wavefront per chunk, four per workgroup; `batch` tables ws_stride bytes apart)
+int launch_chunk_box(char* ws, size_t ws_stride, int N, int batch, hipStream_t st)
+{
+    hipLaunchKernelGGL(chunk_box_kernel, dim3(((N + kWave - 1) / kWave + 3) / 4, batch), dim3(256), 0, st, ws, ws_stride, N);
+    UMEREG_CHECK_LAUNCH("chunk_box_kernel");
+    return UMEREG_OK;
 }
 
 // ---- feature_spatial_var for clouds that do not fill the chip with one query per lane: one wavefront per query ----
@@ -412,8 +408,7 @@ UMEREG_API int umereg_feature_spatial_var_f32(const float* pts, const float* fea
     knn_lds_plan(knn, N, &cap, &waves, &lds, 4, &idx16);
     if (N <= 32768) {
         // small clouds: one wavefront per query
-        hipLaunchKernelGGL(chunk_box_kernel, dim3(((N + kWave - 1) / kWave + 3) / 4, B), dim3(256), 0, st, (char*)workspace, grid_ws(N).total, N);
-        UMEREG_CHECK_LAUNCH("chunk_box_kernel");
+        if (int rc = launch_chunk_box((char*)workspace, grid_ws(N).total, N, B, st)) return rc;
         hipLaunchKernelGGL(spatial_var_coop_kernel, dim3(min((N + 7) / 8, 4096), B), dim3(8 * kWave), 0, st, (const char*)workspace,
                            grid_ws(N).total, (const float4*)feat, N, knn, out);
         UMEREG_CHECK_LAUNCH("spatial_var_coop_kernel");

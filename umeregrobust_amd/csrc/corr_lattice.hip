@@ -1,8 +1,8 @@
 // corr_lattice.hip -- SURVEY 8(f1), what the consensus pass leaves when it leaves MANY queries: the candidate lattice on the
 // target (mark, compact, lists, far table), the cell pass that serves the leftover queries grouped by the cell their image falls
-// in, and the arg-max mode's second pass over the far-query plane (utils/loc_utils.py:592-637, 676-680).  Launched by
-// umereg_corr_scores_ex_f32 (corr.hip).
-#include "corr_kernels.h"
+// in, and the arg-max mode's second pass over the far-query plane (utils/loc_utils.py:592-637, 676-680).  Each kernel is followed by
+// its launcher, which umereg_corr_scores_ex_f32 (corr.hip) calls.
+#include "corr_host.h"
 
 namespace umereg {
 // ---- candidate lattice on the target (hypothesis selection) -----------------------------------------------------
@@ -47,6 +47,8 @@ constexpr float kBoundCellSigmas = UMEREG_BOUND_CELL_SIGMAS;  // the same for a 
 // half-overlapping 17.3 / 13.70 / 13.67 / 13.74 / 14.27 / 14.38 with 21 / 2 / 2 / 2 / 2 / 2 hypotheses recomputed)
 constexpr float kBoundNearSigmas = UMEREG_BOUND_NEAR_SIGMAS;
 constexpr float kBoundNearFrom = UMEREG_BOUND_NEAR_FROM;
+// cons2_hist_add / cons2_scan (corr_dev.h) with 16-bit counters (two per word, 18 words per lane): stages of up to 65 535 points (the cell pass's long lists)
+constexpr int kHist16Words = 18;
 __device__ __forceinline__ void hist16_add(unsigned int* hist, int lane, int t)
 {
     atomicAdd(&hist[(t >> 1) * kWave + lane], 1u << ((t & 1) * 16));
@@ -92,6 +94,14 @@ __global__ void leftover_decide_kernel(unsigned int* __restrict__ header, long n
     }
     header[8] = force == 1 ? 1u : (force == 2 ? 0u : (left <= (long)left_max ? 1u : 0u));   // force: UMEREG_CORR_LEFT_COOP / _LATTICE (tuning)
 }
+// left_max: the leftovers up to which the grid kernel takes them (the caller's routing: consensus_pass, corr.hip)
+int launch_leftover_decide(const CorrCtx& c, unsigned int left_max)
+{
+    hipLaunchKernelGGL(leftover_decide_kernel, dim3(1), dim3(1), 0, c.st, (unsigned int*)c.lat, c.queries,
+                       (c.flags & UMEREG_CORR_LEFT_COOP) ? 1 : ((c.flags & UMEREG_CORR_LEFT_LATTICE) ? 2 : 0), c.ws.c_max, left_max);
+    UMEREG_CHECK_LAUNCH("leftover_decide_kernel");
+    return UMEREG_OK;
+}
 
 // ---- lattice build ---------------------------------------------------------------------------------------------------
 // (1) lattice_mark_kernel: marks[cell] = 1 for every cell some (hypothesis, source point) query lands in (~1/4 of them);
@@ -128,6 +138,13 @@ __global__ __launch_bounds__(256) void lattice_mark_kernel(const char* __restric
             if (cell_cnt) atomicAdd(&cell_cnt[cell], 1u);       // (the cell pass's counting sort: see corr_cell_kernel)
         }
     }
+}
+int launch_lattice_mark(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(lattice_mark_kernel, dim3((c.Ns + 255) / 256, (c.M + 15) / 16), dim3(256), 0, c.st, c.ws_tgt, c.src_pts, c.T, c.Ns, c.Nt, c.M,
+                       16 /* hypotheses per thread */, c.lat, c.ws.c_max, c.served, c.n_words, c.inv, c.chunk_of, c.cw.cnt);
+    UMEREG_CHECK_LAUNCH("lattice_mark_kernel");
+    return UMEREG_OK;
 }
 
 // The unserved queries of a pair, walked in the consensus pass's order: lane = one slot of the source's processing order (a wavefront
@@ -217,6 +234,12 @@ __global__ __launch_bounds__(256) void lattice_far_table_kernel(const char* __re
     const unsigned long long fb = __ballot(far);
     if (fb != 0ull && lane_id() == 0) atomicAdd(reinterpret_cast<unsigned int*>(lat + lw.off_header) + 45, (unsigned int)__popcll(fb));      // (statistics: far cells)
 }
+int launch_lattice_far_table(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(lattice_far_table_kernel, dim3((c.ws.c_max + 255) / 256), dim3(256), 0, c.st, c.ws_coop, c.ws_tgt, c.lat, c.ws.c_max, c.Nt, c.sigma);
+    UMEREG_CHECK_LAUNCH("lattice_far_table_kernel");
+    return UMEREG_OK;
+}
 
 __global__ __launch_bounds__(256) void lattice_mark_order_kernel(const char* __restrict__ ws_tgt, const char* __restrict__ ws_src, const float* __restrict__ src_pts,
                                                                  const float* __restrict__ T, int Ns, int Nt, int M, char* __restrict__ lat, unsigned int c_max,
@@ -283,6 +306,25 @@ __global__ __launch_bounds__(256) void lattice_mark_order_kernel(const char* __r
         }
     }, todo_plane, only);
 }
+// grid of the two kernels that deal (256 source points, 64 hypotheses) items: this one and cell_scatter_kernel
+static dim3 order_grid(const CorrCtx& c)
+{
+    const long order_items = (long)((c.Ns + 255) / 256) * c.n_words;
+    return dim3((unsigned)(order_items < 16384 ? order_items : 16384));
+}
+// the call's pass over the queries the consensus pass left (bounding those of far cells in arg-max mode with a cell pass), or the second pass over
+// the far-query plane and the surviving hypotheses
+int launch_lattice_mark_order(const CorrCtx& c, bool second)
+{
+    if (c.far_cells && !second)
+        hipLaunchKernelGGL(lattice_mark_order_kernel, order_grid(c), dim3(256), 0, c.st, c.ws_tgt, c.ws_src, c.src_pts, c.T, c.Ns, c.Nt, c.M, c.lat, c.ws.c_max, c.served, c.n_words,
+                           c.perm, c.cw.cnt, false, nullptr, c.K, c.sigma, c.b_vpn, c.b_vqmax, c.b_slack, c.b_farq, c.served);
+    else
+        hipLaunchKernelGGL(lattice_mark_order_kernel, order_grid(c), dim3(256), 0, c.st, c.ws_tgt, c.ws_src, c.src_pts, c.T, c.Ns, c.Nt, c.M, c.lat, c.ws.c_max,
+                           second ? c.b_farq : c.served, c.n_words, c.perm, c.cw.cnt, second, second ? c.b_surv : nullptr, 0, 1.f, nullptr, nullptr, nullptr, nullptr, nullptr);
+    UMEREG_CHECK_LAUNCH("lattice_mark_order_kernel");
+    return UMEREG_OK;
+}
 __global__ __launch_bounds__(1024) void lattice_compact_kernel(const char* __restrict__ ws_tgt, char* __restrict__ lat, unsigned int c_max, int Nt)
 {
     __shared__ unsigned int part[1024];
@@ -339,7 +381,15 @@ __global__ __launch_bounds__(1024) void lattice_compact_kernel(const char* __res
     }
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 1023) { header[3] = before + part[1023]; header[1] = (unsigned int)L.n_cells; }
 }
-
+// (kCompactBlocks workgroups, each with a contiguous range of 16-cell groups; a workgroup counts the marks of the ranges before its own
+// itself -- 512 KiB of marks, read from L2 -- instead of waiting for a scan: one launch, 0.15 -> 0.02 ms for 2^19 cells)
+constexpr int kCompactBlocks = 64;
+int launch_lattice_compact(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(lattice_compact_kernel, dim3(kCompactBlocks), dim3(1024), 0, c.st, c.ws_tgt, c.lat, c.ws.c_max, c.Nt);
+    UMEREG_CHECK_LAUNCH("lattice_compact_kernel");
+    return UMEREG_OK;
+}
 
 // is target point p a candidate of the cell (centre cc, list radius^2 r2)?  dist(p, cell box) <= r
 __device__ __forceinline__ bool lattice_in_list(const Lattice& L, const float4& p, float ccx, float ccy, float ccz, float r2)
@@ -366,6 +416,12 @@ __global__ __launch_bounds__(256) void lattice_posof_kernel(const char* __restri
     unsigned short* posof = reinterpret_cast<unsigned short*>(lat + lat_ws(c_max).off_posof);
     const unsigned int orig = (unsigned int)__float_as_int(P4s[pos].w);
     if (orig < 65536u) posof[orig] = (unsigned short)pos;
+}
+int launch_lattice_posof(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(lattice_posof_kernel, dim3((c.Nt + 255) / 256), dim3(256), 0, c.st, c.ws_tgt, c.lat, c.ws.c_max, c.Nt);
+    UMEREG_CHECK_LAUNCH("lattice_posof_kernel");
+    return UMEREG_OK;
 }
 
 constexpr int kLatListCap = 4 * kLatMaxQuads;            // entries of the longest list
@@ -524,6 +580,17 @@ __global__ __launch_bounds__(8 * 64) void lattice_list_kernel(const char* __rest
         if (n_far) atomicAdd(&header[45], n_far);               // (statistics: far cells)
     }
 }
+// (grids of the kernels that usually find nothing to do -- the leftovers go to the queue up to 2 M -- are kept small: a
+// workgroup that returns at once still costs its launch, 50 us for 1 024 x 512 threads with 33 KiB of LDS each)
+// (idle on jobs whose leftovers go to the queue -- every KITTI-test pair --, where its launch alone was 60 us of a pair's 3.7 ms
+// beside other streams' kernels: full_grid only where the lattice is the likely path)
+int launch_lattice_list(const CorrCtx& c, bool second, bool full_grid)
+{
+    hipLaunchKernelGGL(lattice_list_kernel, dim3(full_grid ? 512 : 256), dim3(8 * kWave), 0, c.st, c.ws_coop, c.ws_tgt, c.lat, c.ws.c_max, c.Nt, c.K, c.sigma,
+                       c.far_cells && !second ? 1 : 0);
+    UMEREG_CHECK_LAUNCH("lattice_list_kernel");
+    return UMEREG_OK;
+}
 
 // ---- cell pass: the consensus pass's leftovers, when they are MANY, grouped by the lattice cell they land in ---------------------
 // The list kernel below works (hypothesis, chunk) record by record: 64 lanes with 64 different cells, every lane streaming ITS cell's
@@ -548,6 +615,10 @@ __global__ __launch_bounds__(8 * 64) void lattice_list_kernel(const char* __rest
 // Measured (MI355X, 5 000 hypotheses x 30 000 points, sigma 1): list kernel 27.7 -> 2.2 ms + this pass 10.6 + 3.2 (scatter) on a plain
 // pair (24.8 M leftovers, 22.2 M of them served here); on a half-overlapping one 68 -> 21 + 19.7 + 4.9.
 constexpr int kCellCap = 252;                       // list entries (byte counters: see corr_consensus2_kernel)
+#ifndef UMEREG_CELL_STAGE
+#define UMEREG_CELL_STAGE 256
+#endif
+constexpr int kCellStage = UMEREG_CELL_STAGE;       // stage slots of the short-list instance (a group of cells shares them)
 #ifndef UMEREG_CELL_FETCH
 #define UMEREG_CELL_FETCH 4
 #endif
@@ -620,8 +691,6 @@ __global__ __launch_bounds__(1024) void cell_apply_kernel(char* __restrict__ lat
         for (unsigned int k = 0; k < mine; ++k) dst[k] = make_uint2(i, k);
     }
 }
-template __global__ __launch_bounds__(1024) void cell_apply_kernel<0>(char* __restrict__ lat, unsigned int c_max, CellWs cw);
-template __global__ __launch_bounds__(1024) void cell_apply_kernel<1>(char* __restrict__ lat, unsigned int c_max, CellWs cw);
 __global__ __launch_bounds__(1024) void cell_blockscan_kernel(char* __restrict__ lat, unsigned int c_max, CellWs cw)
 {
     __shared__ unsigned int part[1024 / 64];
@@ -638,6 +707,16 @@ __global__ __launch_bounds__(1024) void cell_blockscan_kernel(char* __restrict__
     __syncthreads();
     if (threadIdx.x < nb) cw.bsum[threadIdx.x] = base + (unsigned int)incl - v;
     if (threadIdx.x == 0) header[32] = tot;
+}
+// the three short launches over the marked list: per-block sums, their offsets, the cells' first entries and records
+int launch_cell_offsets(const CorrCtx& c)
+{
+    const unsigned int nb = (c.ws.c_max + 1023u) / 1024u;
+    hipLaunchKernelGGL(cell_apply_kernel<0>, dim3(nb), dim3(1024), 0, c.st, c.lat, c.ws.c_max, c.cw);
+    hipLaunchKernelGGL(cell_blockscan_kernel, dim3(1), dim3(1024), 0, c.st, c.lat, c.ws.c_max, c.cw);
+    hipLaunchKernelGGL(cell_apply_kernel<1>, dim3(nb), dim3(1024), 0, c.st, c.lat, c.ws.c_max, c.cw);
+    UMEREG_CHECK_LAUNCH("cell_apply_kernel");
+    return UMEREG_OK;
 }
 
 // the entries: every unserved query whose cell has a usable list, at cnt[cell] (= first) + cur[cell]++
@@ -726,6 +805,16 @@ __global__ __launch_bounds__(256) void cell_scatter_kernel(const char* __restric
         listed = 0ull;
     });
 }
+// (the second pass bounds nothing: no norms, no slack, no plane to write)
+int launch_cell_scatter(const CorrCtx& c, bool second)
+{
+    const bool far = c.far_cells && !second;
+    hipLaunchKernelGGL(cell_scatter_kernel, order_grid(c), dim3(256), 0, c.st, c.ws_tgt, c.ws_src, c.src_pts, c.T, c.Ns, c.Nt, c.M, c.lat, c.ws.c_max,
+                       second ? c.b_farq : c.served, c.n_words, c.perm, c.cw, c.K, c.sigma, second ? nullptr : c.b_vpn, second ? nullptr : c.b_vqmax,
+                       far ? c.b_slack : nullptr, second ? nullptr : c.b_farq, second, second ? c.b_surv : nullptr);
+    UMEREG_CHECK_LAUNCH("cell_scatter_kernel");
+    return UMEREG_OK;
+}
 
 // The second pass of the bounded mode re-runs the lattice + cell pass on the far-cell queries of the surviving hypotheses (a list for
 // every cell they lie in, the same kernels: one wavefront per query, which it used to be, cost a pair with 200 survivors 13 ms).  Its
@@ -735,6 +824,12 @@ __global__ void bound_pass2_gate_kernel(unsigned int* __restrict__ header)
 {
     if (header[40] == 0u) { header[8] = header[8] == 1u ? 3u : 2u; return; }      // (2 / 3: the first pass's leftovers had gone to the lattice / the queue)
     header[3] = 0u; header[33] = 0u; header[37] = 0u; header[38] = 0u; header[39] = 0u; header[43] = 0u;
+}
+int launch_bound_pass2_gate(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(bound_pass2_gate_kernel, dim3(1), dim3(1), 0, c.st, (unsigned int*)c.lat);
+    UMEREG_CHECK_LAUNCH("bound_pass2_gate_kernel");
+    return UMEREG_OK;
 }
 
 // ... and what that leaves (cells whose list would be too long, ties by the dozen): the queries cell_scatter_kernel bounded for lying in far cells, for the hypotheses that survived
@@ -806,7 +901,27 @@ __global__ __launch_bounds__(kCoopWaves * 64) __attribute__((amdgpu_waves_per_eu
         }
     }
 }
+int launch_far_recompute(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(far_recompute_kernel, dim3(1024), dim3(kCoopWaves * kWave), 0, c.st, c.ws_coop, c.ws_src, c.src_pts, c.vp4, c.vq4, c.T, c.Ns, c.Nt, c.M, c.K, c.sigma,
+                       c.lat, c.ws.c_max, c.b_farq, c.n_words, c.perm, c.b_surv, c.val);
+    UMEREG_CHECK_LAUNCH("far_recompute_kernel");
+    return UMEREG_OK;
+}
 
+// LDS of one wavefront (= one workgroup) of corr_cell_kernel, in the order the kernel carves it: the d2 plane holds the histogram until the second sweep starts
+__host__ __device__ inline size_t cell_d2_plane(int K, bool lng)
+{
+    const size_t hw = (size_t)(lng ? kHist16Words : kCons2HistWords) * kWave * 4;
+    return (size_t)K * kWave * 4 > hw ? (size_t)K * kWave * 4 : hw;
+}
+__host__ __device__ inline size_t cell_lds_per_wave(int K, bool lng)
+{
+    // tie list (16-bit index plane) | stage (256 or 512 slots x 16 B) | the lane's K keys (d2 plane -- the histogram lives there until
+    // the second sweep starts --, 16-bit index plane)
+    // (14.5 KiB: eleven wavefronts per CU; 128 bytes more are ten)
+    return (size_t)kCons2Tie * kWave * 6 + (size_t)(lng ? 512 : kCellStage) * 16 + cell_d2_plane(K, lng) + ((size_t)K * kWave * 2 + 255) / 256 * 256;
+}
 // kLong = false: the cells whose list has <= kCellCap entries (byte counters, 256 stage slots: 14.5 KiB of LDS per wavefront);
 // kLong = true: the longer ones, up to kCellCapLong (16-bit counters, 512 slots: 18.5 KiB) -- dense spots, 3 % of the queries of a
 // nuScenes-size half-overlapping pair, which cost 9 ns each in the list kernel (21 of that pair's 85 ms)
@@ -1129,15 +1244,17 @@ __global__ __launch_bounds__(64) void corr_cell_kernel(const char* __restrict__ 
         if (dbg && n_batches) atomicAdd(&header[36], n_batches);
     }
 }
-template __global__ __launch_bounds__(64) void corr_cell_kernel<false>(const char* __restrict__ ws_tgt, const float* __restrict__ src_pts,
-                                                       const float4* __restrict__ vp4, const float4* __restrict__ vq4, const float* __restrict__ T,
-                                                       int Ns, int Nt, int M, int K, float sigma, char* __restrict__ lat, unsigned int c_max, CellWs cw,
-                                                       float* __restrict__ val, unsigned long long* __restrict__ served, int dbg,
-                                                       unsigned long long* __restrict__ farq_clear);
-template __global__ __launch_bounds__(64) void corr_cell_kernel<true>(const char* __restrict__ ws_tgt, const float* __restrict__ src_pts,
-                                                       const float4* __restrict__ vp4, const float4* __restrict__ vq4, const float* __restrict__ T,
-                                                       int Ns, int Nt, int M, int K, float sigma, char* __restrict__ lat, unsigned int c_max, CellWs cw,
-                                                       float* __restrict__ val, unsigned long long* __restrict__ served, int dbg,
-                                                       unsigned long long* __restrict__ farq_clear);
+// both instances, one wavefront per workgroup; the second pass (arg-max mode) takes no statistics and clears the far-query bits it serves
+int launch_corr_cell(const CorrCtx& c, bool second)
+{
+    const int dbg = second ? 0 : c.dbg;
+    unsigned long long* farq_clear = second ? c.b_farq : nullptr;
+    hipLaunchKernelGGL(corr_cell_kernel<false>, dim3(2816), dim3(kWave), cell_lds_per_wave(c.K, false), c.st, c.ws_tgt, c.src_pts, c.vp4, c.vq4, c.T, c.Ns, c.Nt, c.M, c.K,
+                       c.sigma, c.lat, c.ws.c_max, c.cw, c.val, c.served, dbg, farq_clear);
+    hipLaunchKernelGGL(corr_cell_kernel<true>, dim3(2048), dim3(kWave), cell_lds_per_wave(c.K, true), c.st, c.ws_tgt, c.src_pts, c.vp4, c.vq4, c.T, c.Ns, c.Nt, c.M, c.K,
+                       c.sigma, c.lat, c.ws.c_max, c.cw, c.val, c.served, dbg, farq_clear);
+    UMEREG_CHECK_LAUNCH("corr_cell_kernel");
+    return UMEREG_OK;
+}
 
 }  // namespace umereg

@@ -1,8 +1,9 @@
 // corr_leftover.hip -- SURVEY 8(f1), the remaining routes of a (hypothesis, query) to its exact K nearest: one lane per query on
 // the grid (corr_score_kernel: small jobs, and every job's fallback), one wavefront per query over the Hilbert-ordered chunks
 // (queue, flat list, records), the bound of the queries outside the lattice, and the fixed-order reductions down to the scores and
-// FeatureCorrelator's pick (utils/loc_utils.py:592-637, 676-680).  Launched by umereg_corr_scores_ex_f32 (corr.hip).
-#include "corr_kernels.h"
+// FeatureCorrelator's pick (utils/loc_utils.py:592-637, 676-680).  Each kernel is followed by its launcher, which
+// umereg_corr_scores_ex_f32 (corr.hip) calls; the pick has its entry point here.
+#include "corr_host.h"
 
 namespace umereg {
 // ---- score epilogue ---------------------------------------------------------------------------------------------
@@ -257,27 +258,28 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
 #endif
 }
-template __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 4))) void corr_score_kernel<unsigned short, false>(const char* __restrict__ ws_tgt, const char* __restrict__ ws_src,
-                                                         const float* __restrict__ src_pts, const float4* __restrict__ vp4, const float4* __restrict__ vq4,
-                                                         const float* __restrict__ T, int Ns, int Nt, int M, int K, int cap,
-                                                         float sigma, int hyp_per_wave, int n_chunks,
-                                                         float* __restrict__ partial, char* __restrict__ lat, unsigned int c_max,
-                                                         const unsigned long long* __restrict__ served, int n_words,
-                                                         const int* __restrict__ inv, int after_cell_pass, const int* __restrict__ perm_o);
-template __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 4))) void corr_score_kernel<unsigned short, true>(const char* __restrict__ ws_tgt, const char* __restrict__ ws_src,
-                                                         const float* __restrict__ src_pts, const float4* __restrict__ vp4, const float4* __restrict__ vq4,
-                                                         const float* __restrict__ T, int Ns, int Nt, int M, int K, int cap,
-                                                         float sigma, int hyp_per_wave, int n_chunks,
-                                                         float* __restrict__ partial, char* __restrict__ lat, unsigned int c_max,
-                                                         const unsigned long long* __restrict__ served, int n_words,
-                                                         const int* __restrict__ inv, int after_cell_pass, const int* __restrict__ perm_o);
-template __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 4))) void corr_score_kernel<unsigned int, false>(const char* __restrict__ ws_tgt, const char* __restrict__ ws_src,
-                                                         const float* __restrict__ src_pts, const float4* __restrict__ vp4, const float4* __restrict__ vq4,
-                                                         const float* __restrict__ T, int Ns, int Nt, int M, int K, int cap,
-                                                         float sigma, int hyp_per_wave, int n_chunks,
-                                                         float* __restrict__ partial, char* __restrict__ lat, unsigned int c_max,
-                                                         const unsigned long long* __restrict__ served, int n_words,
-                                                         const int* __restrict__ inv, int after_cell_pass, const int* __restrict__ perm_o);
+// One lane per query: through the lattice's lists where there is a lattice (queueing what it cannot serve), the per-lane grid walk otherwise.
+int launch_corr_score(const CorrCtx& c)
+{
+    const unsigned int c_max = c.ws.c_max;
+    const int hyp_per_wave = 2;   // 1..4 measured equal (6.4 us per hypothesis), 8: 6.7, 16: 7.3 (balance at the tail, parallelism)
+    const long n_waves = (long)c.n_chunks * ((c.M + hyp_per_wave - 1) / hyp_per_wave);
+    const dim3 score_grid((unsigned)((n_waves + c.waves - 1) / c.waves)), score_block(c.waves * kWave);
+    const dim3 lat_grid(score_grid.x < 4096u ? score_grid.x : 4096u);
+    // (the instances are named in this order on purpose: the compiler instantiates them, and inlines knn_wave into them, in order of first mention, and
+    // <unsigned short, false> comes out as the measured code -- 40 B of scratch, not 68 -- only when it is the first: tools/isa_identity.py shows it)
+    if (!c_max && c.idx16)
+        hipLaunchKernelGGL((corr_score_kernel<unsigned short, false>), score_grid, score_block, c.lds, c.st, c.ws_tgt, c.ws_src, c.src_pts, c.vp4, c.vq4, c.T, c.Ns, c.Nt, c.M, c.K,
+                           c.cap, c.sigma, hyp_per_wave, c.n_chunks, c.partial, nullptr, 0u, nullptr, 0, nullptr, 0, nullptr);
+    else if (c_max)
+        hipLaunchKernelGGL((corr_score_kernel<unsigned short, true>), lat_grid, score_block, c.lds, c.st, c.ws_tgt, c.ws_src, c.src_pts, c.vp4, c.vq4, c.T, c.Ns, c.Nt, c.M, c.K,
+                           c.cap, c.sigma, hyp_per_wave, c.n_chunks, c.partial, c.lat, c_max, c.served, c.n_words, c.inv, c.cell_pass ? 1 : 0, c.perm);
+    else
+        hipLaunchKernelGGL((corr_score_kernel<unsigned int, false>), score_grid, score_block, c.lds, c.st, c.ws_tgt, c.ws_src, c.src_pts, c.vp4, c.vq4, c.T, c.Ns, c.Nt, c.M, c.K,
+                           c.cap, c.sigma, hyp_per_wave, c.n_chunks, c.partial, nullptr, 0u, nullptr, 0, nullptr, 0, nullptr);
+    UMEREG_CHECK_LAUNCH("corr_score_kernel");
+    return UMEREG_OK;
+}
 
 // ---- the consensus pass's leftovers, when they are few (header word 8 = 1): queued for corr_score_fallback_kernel ----
 // They are ~1 % of the queries, scattered over the (hypothesis, chunk) records with a dozen live lanes each.  A
@@ -319,6 +321,13 @@ __global__ __launch_bounds__(256) void leftover_queue_kernel(const char* __restr
         queue[base + (unsigned int)mbcnt(recs)] = make_uint4((unsigned int)perm[(size_t)chunk * M + pos], (unsigned int)chunk, (unsigned int)mine, (unsigned int)(mine >> 32));
         atomicAdd(&header[6], (unsigned int)__popcll(mine));
     }
+}
+int launch_leftover_queue(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(leftover_queue_kernel, dim3((unsigned)(((long)c.n_chunks * c.n_words + 3) / 4)), dim3(256), 0, c.st, c.ws_src, c.Ns, c.M, c.n_chunks, c.served,
+                       c.n_words, c.perm, c.lat, c.ws.c_max);
+    UMEREG_CHECK_LAUNCH("leftover_queue_kernel");
+    return UMEREG_OK;
 }
 
 // ---- the queries the lattice could not serve: one WAVEFRONT per query -----------------------------------------------
@@ -402,6 +411,15 @@ __global__ __launch_bounds__(kCoopWaves * 64) void corr_score_fallback_kernel(co
         __syncthreads();
     }
 }
+// (with the flat list in front this kernel only has work when that list overflowed -- more leftovers than half the job's queries --:
+// 128 workgroups, its idle launch was 70 us per end-to-end pair at 512)
+int launch_corr_score_fallback(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(corr_score_fallback_kernel, dim3((c.flags & UMEREG_CORR_NO_FLAT) ? 4096 : 128), dim3(kCoopWaves * kWave), 0, c.st, c.ws_coop, c.ws_src, c.src_pts,
+                       c.vp4, c.vq4, c.T, c.Ns, c.Nt, c.K, c.sigma, c.n_chunks, c.partial, c.lat, c.ws.c_max);
+    UMEREG_CHECK_LAUNCH("corr_score_fallback_kernel");
+    return UMEREG_OK;
+}
 
 // ---- the same queries as a FLAT list ---------------------------------------------------------------------------------
 // A record holds a dozen queries on average, and the eight wavefronts of corr_score_fallback_kernel meet at two barriers
@@ -427,6 +445,12 @@ __global__ __launch_bounds__(256) void leftover_flatten_kernel(char* __restrict_
         for (unsigned int j = 0; mask != 0ull; mask &= mask - 1ull, ++j)
             f.qlist[base + j] = (r << 6) | (unsigned int)(__ffsll((long long)mask) - 1);
     }
+}
+int launch_leftover_flatten(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(leftover_flatten_kernel, dim3(256), dim3(256), 0, c.st, c.lat, c.ws.c_max, c.fw);
+    UMEREG_CHECK_LAUNCH("leftover_flatten_kernel");
+    return UMEREG_OK;
 }
 
 // ---- bounding the queries OUTSIDE the lattice (UMEREG_CORR_BOUND_OUTSIDE) ----------------------------------------------------
@@ -467,6 +491,13 @@ __global__ __launch_bounds__(256) void row_norm_kernel(const float4* __restrict_
         const float m = wave_max_nonneg_f(r == r ? r : 3.0e38f);          // (a NaN row: no bound)
         if (lane_id() == 0) atomicMax(max_bits, __float_as_uint(m));
     }
+}
+// (one launch for both sets of rows: |vp_n| of the source's, the maximum of |vq_j| over the target's)
+int launch_row_norm(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(row_norm_kernel, dim3((c.Ns + 255) / 256 + (c.Nt + 255) / 256), dim3(256), 0, c.st, c.vp4, c.Ns, c.b_vpn, c.vq4, c.Nt, c.b_vqmax);
+    UMEREG_CHECK_LAUNCH("row_norm_kernel");
+    return UMEREG_OK;
 }
 
 // The bookkeeping of the bounded mode, one listed query per LANE (it used to sit in corr_score_flat_kernel's visits of four queries per
@@ -563,14 +594,18 @@ __global__ __launch_bounds__(256) void flat_bound_kernel(const char* __restrict_
         }
     }
 }
-template __global__ __launch_bounds__(256) void flat_bound_kernel<1>(const char* __restrict__ ws_tgt, const char* __restrict__ ws_src, const float* __restrict__ src_pts,
-                                                         const float* __restrict__ T, int Ns, int Nt, int K, float sigma, char* __restrict__ lat, unsigned int c_max,
-                                                         FlatWs f, const float* __restrict__ vpn, const unsigned int* __restrict__ vq_max_bits,
-                                                         unsigned long long* __restrict__ slack, const unsigned int* __restrict__ surv);
-template __global__ __launch_bounds__(256) void flat_bound_kernel<2>(const char* __restrict__ ws_tgt, const char* __restrict__ ws_src, const float* __restrict__ src_pts,
-                                                         const float* __restrict__ T, int Ns, int Nt, int K, float sigma, char* __restrict__ lat, unsigned int c_max,
-                                                         FlatWs f, const float* __restrict__ vpn, const unsigned int* __restrict__ vq_max_bits,
-                                                         unsigned long long* __restrict__ slack, const unsigned int* __restrict__ surv);
+// mode 1: the call's pass; mode 2: once more for the surviving hypotheses (bounded_recompute, corr.hip)
+int launch_flat_bound(const CorrCtx& c, int mode)
+{
+    if (mode == 1)
+        hipLaunchKernelGGL(flat_bound_kernel<1>, dim3(2048), dim3(256), 0, c.st, c.ws_tgt, c.ws_src, c.src_pts, c.T, c.Ns, c.Nt, c.K, c.sigma, c.lat, c.ws.c_max, c.fw, c.b_vpn,
+                           c.b_vqmax, c.b_slack, c.b_surv);
+    else
+        hipLaunchKernelGGL(flat_bound_kernel<2>, dim3(2048), dim3(256), 0, c.st, c.ws_tgt, c.ws_src, c.src_pts, c.T, c.Ns, c.Nt, c.K, c.sigma, c.lat, c.ws.c_max, c.fw, c.b_vpn,
+                           c.b_vqmax, c.b_slack, c.b_surv);
+    UMEREG_CHECK_LAUNCH("flat_bound_kernel");
+    return UMEREG_OK;
+}
 
 // kMode 0: every entry of the flat list; kMode 3: the entries flat_bound_kernel left to the search (f.qsel, header word 44)
 template <int kMode>
@@ -710,18 +745,22 @@ __global__ __launch_bounds__(kCoopWaves * 64) __attribute__((amdgpu_waves_per_eu
         }
     }
 }
-template __global__ __launch_bounds__(kCoopWaves * 64) __attribute__((amdgpu_waves_per_eu(8, 8))) void corr_score_flat_kernel<0>(const char* __restrict__ ws_tgt, const char* __restrict__ ws_src,
-                                                                       const float* __restrict__ src_pts, const float4* __restrict__ vp4,
-                                                                       const float4* __restrict__ vq4, const float* __restrict__ T, int Ns, int Nt,
-                                                                       int K, float sigma, const char* __restrict__ lat, unsigned int c_max, FlatWs f,
-                                                                       const float* __restrict__ vpn, const unsigned int* __restrict__ vq_max_bits,
-                                                                       unsigned long long* __restrict__ slack);
-template __global__ __launch_bounds__(kCoopWaves * 64) __attribute__((amdgpu_waves_per_eu(8, 8))) void corr_score_flat_kernel<3>(const char* __restrict__ ws_tgt, const char* __restrict__ ws_src,
-                                                                       const float* __restrict__ src_pts, const float4* __restrict__ vp4,
-                                                                       const float4* __restrict__ vq4, const float* __restrict__ T, int Ns, int Nt,
-                                                                       int K, float sigma, const char* __restrict__ lat, unsigned int c_max, FlatWs f,
-                                                                       const float* __restrict__ vpn, const unsigned int* __restrict__ vq_max_bits,
-                                                                       unsigned long long* __restrict__ slack);
+constexpr int kFlatBlocks = 6144;   // workgroups (8 wavefronts each, visits of 4 queries dealt round-robin; 768 .. 16 384 measured: 1.17 .. 1.10 ms)
+// mode 0: the whole list; mode 3: what flat_bound_kernel selected -- bounding the far ones itself (the call's pass) or not (the recompute)
+int launch_corr_score_flat(const CorrCtx& c, int mode, bool bounding)
+{
+    const float* vpn = bounding ? c.b_vpn : nullptr;
+    const unsigned int* vq_max_bits = bounding ? c.b_vqmax : nullptr;
+    unsigned long long* slack = bounding ? c.b_slack : nullptr;
+    if (mode == 0)
+        hipLaunchKernelGGL(corr_score_flat_kernel<0>, dim3(kFlatBlocks), dim3(kCoopWaves * kWave), 0, c.st, c.ws_coop, c.ws_src, c.src_pts, c.vp4, c.vq4, c.T, c.Ns, c.Nt, c.K,
+                           c.sigma, c.lat, c.ws.c_max, c.fw, vpn, vq_max_bits, slack);
+    else
+        hipLaunchKernelGGL(corr_score_flat_kernel<3>, dim3(kFlatBlocks), dim3(kCoopWaves * kWave), 0, c.st, c.ws_coop, c.ws_src, c.src_pts, c.vp4, c.vq4, c.T, c.Ns, c.Nt, c.K,
+                           c.sigma, c.lat, c.ws.c_max, c.fw, vpn, vq_max_bits, slack);
+    UMEREG_CHECK_LAUNCH("corr_score_flat_kernel");
+    return UMEREG_OK;
+}
 
 // which hypotheses need their bounded queries after all (see above): surv[h], header word 40 = how many, 41 = hypotheses with slack
 __global__ __launch_bounds__(1024) void bound_survivors_kernel(const float* __restrict__ scores, const unsigned long long* __restrict__ slack, int M, int Ns,
@@ -758,6 +797,12 @@ __global__ __launch_bounds__(1024) void bound_survivors_kernel(const float* __re
     __syncthreads();
     if (threadIdx.x == 0) { header[40] = cnt[0]; header[41] = cnt[1]; header[44] = 0u; }      // (44: flat_bound_kernel's selection starts over)
 }
+int launch_bound_survivors(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(bound_survivors_kernel, dim3(1), dim3(1024), 0, c.st, c.scores, c.b_slack, c.M, c.Ns, c.b_surv, (unsigned int*)c.lat);
+    UMEREG_CHECK_LAUNCH("bound_survivors_kernel");
+    return UMEREG_OK;
+}
 
 // ---- the same queries, first one wavefront per RECORD (round 3) --------------------------------------------------------
 // A record = the queries of one 64-slot chunk of the source order under one hypothesis that nothing else served.  With the
@@ -774,6 +819,16 @@ __global__ __launch_bounds__(1024) void bound_survivors_kernel(const float* __re
 // Lanes that pass are summed into the record's partial sum here; the record's mask is REWRITTEN to the lanes that did not
 // (sparser spot, stage overflow, degenerate image) and the flat one-wavefront-per-query path that follows serves exactly
 // those -- one search per record instead of one per query for the rest (the flat kernel alone: 4 ns per query, 1.1 ms per pair).
+constexpr int kRecStage = 768;           // staged target points per record
+
+// LDS of one wavefront of corr_score_record2_kernel, in the order the kernel carves it
+template <class IdxT>
+__host__ __device__ constexpr size_t rec_lds_per_wave(int cap)
+{
+    // list / histogram region (also coop_knn's two key lists + its histogram: 4 352 B) + the record's queries + the stage
+    return (knn_lds_per_wave(cap, sizeof(IdxT)) > (size_t)(2 * kCoopCap * 8 + kWave * 4) ? knn_lds_per_wave(cap, sizeof(IdxT)) : (size_t)(2 * kCoopCap * 8 + kWave * 4)) +
+           (size_t)kWave * 16 + (size_t)(kRecStage + 4) * 16;
+}
 template <class IdxT>
 __global__ __launch_bounds__(128) void corr_score_record2_kernel(const char* __restrict__ ws_tgt, const char* __restrict__ ws_src,
                                                                  const float* __restrict__ src_pts, const float4* __restrict__ vp4,
@@ -932,16 +987,18 @@ __global__ __launch_bounds__(128) void corr_score_record2_kernel(const char* __r
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
 }
-template __global__ __launch_bounds__(128) void corr_score_record2_kernel<unsigned short>(const char* __restrict__ ws_tgt, const char* __restrict__ ws_src,
-                                                                 const float* __restrict__ src_pts, const float4* __restrict__ vp4,
-                                                                 const float4* __restrict__ vq4, const float* __restrict__ T, int Ns, int Nt,
-                                                                 int K, int cap, float sigma, int n_chunks, float* __restrict__ partial,
-                                                                 char* __restrict__ lat, unsigned int c_max, int dbg);
-template __global__ __launch_bounds__(128) void corr_score_record2_kernel<unsigned int>(const char* __restrict__ ws_tgt, const char* __restrict__ ws_src,
-                                                                 const float* __restrict__ src_pts, const float4* __restrict__ vp4,
-                                                                 const float4* __restrict__ vq4, const float* __restrict__ T, int Ns, int Nt,
-                                                                 int K, int cap, float sigma, int n_chunks, float* __restrict__ partial,
-                                                                 char* __restrict__ lat, unsigned int c_max, int dbg);
+// (two wavefronts per workgroup; the records are dealt statically over 4 096 workgroups)
+int launch_corr_score_record2(const CorrCtx& c)
+{
+    if (c.idx16)
+        hipLaunchKernelGGL(corr_score_record2_kernel<unsigned short>, dim3(4096), dim3(2 * kWave), 2 * rec_lds_per_wave<unsigned short>(c.cap), c.st, c.ws_coop, c.ws_src,
+                           c.src_pts, c.vp4, c.vq4, c.T, c.Ns, c.Nt, c.K, c.cap, c.sigma, c.n_chunks, c.partial, c.lat, c.ws.c_max, c.dbg);
+    else
+        hipLaunchKernelGGL(corr_score_record2_kernel<unsigned int>, dim3(4096), dim3(2 * kWave), 2 * rec_lds_per_wave<unsigned int>(c.cap), c.st, c.ws_coop, c.ws_src,
+                           c.src_pts, c.vp4, c.vq4, c.T, c.Ns, c.Nt, c.K, c.cap, c.sigma, c.n_chunks, c.partial, c.lat, c.ws.c_max, c.dbg);
+    UMEREG_CHECK_LAUNCH("corr_score_record2_kernel");
+    return UMEREG_OK;
+}
 
 __global__ __launch_bounds__(256) void leftover_sum_kernel(const char* __restrict__ lat, unsigned int c_max, FlatWs f, int n_chunks,
                                                            float* __restrict__ partial, int second_pass)
@@ -960,6 +1017,12 @@ __global__ __launch_bounds__(256) void leftover_sum_kernel(const char* __restric
         partial[(size_t)rec.x * n_chunks + rec.y] += total;              // every record has one writer
     }
 }
+int launch_leftover_sum(const CorrCtx& c, bool second_pass)
+{
+    hipLaunchKernelGGL(leftover_sum_kernel, dim3(256), dim3(256), 0, c.st, c.lat, c.ws.c_max, c.fw, c.n_chunks, c.partial, second_pass ? 1 : 0);
+    UMEREG_CHECK_LAUNCH("leftover_sum_kernel");
+    return UMEREG_OK;
+}
 __global__ __launch_bounds__(256) void corr_val_slices_kernel(const float* __restrict__ val, int M, int Ns, const char* __restrict__ ws_src,
                                                               float* __restrict__ slices, const int* __restrict__ perm,
                                                               const unsigned int* __restrict__ only)
@@ -977,6 +1040,14 @@ __global__ __launch_bounds__(256) void corr_val_slices_kernel(const float* __res
     for (int sl = s0; sl < s1; ++sl) s += val[(size_t)__float_as_int(S4s[sl].w) * M + pos];   // coalesced over pos; fixed order
     slices[(size_t)blockIdx.y * M + pos] = s;
 }
+// last: the call's final reduction (the plane summed in processing order and, in arg-max mode, for the surviving hypotheses only)
+int launch_corr_val_slices(const CorrCtx& c, bool last)
+{
+    hipLaunchKernelGGL(corr_val_slices_kernel, dim3((c.M + 255) / 256, (c.Ns + kValSlice - 1) / kValSlice), dim3(256), 0, c.st, c.val, c.M, c.Ns, c.ws_src, c.slices,
+                       last ? c.perm : nullptr, last ? c.b_surv : nullptr);
+    UMEREG_CHECK_LAUNCH("corr_val_slices_kernel");
+    return UMEREG_OK;
+}
 
 // one wavefront per hypothesis: lanes stride over the slices / chunks, then a fixed butterfly: deterministic
 __global__ __launch_bounds__(256) void corr_reduce_kernel(const float* __restrict__ partial, int M, int n_chunks, int Ns,
@@ -991,6 +1062,14 @@ __global__ __launch_bounds__(256) void corr_reduce_kernel(const float* __restric
     for (int k = lane; k < n_chunks; k += kWave) s += partial[(size_t)h * n_chunks + k];
     s = wave_sum_f(s);
     if (lane == 0) scores[h] = s / (float)Ns;                                        // utils/loc_utils.py:610
+}
+// (without a consensus pass there is no plane and there are no slices)
+int launch_corr_reduce(const CorrCtx& c)
+{
+    hipLaunchKernelGGL(corr_reduce_kernel, dim3((c.M + 3) / 4), dim3(256), 0, c.st, c.partial, c.M, c.n_chunks, c.Ns, c.slices, c.val ? (c.Ns + kValSlice - 1) / kValSlice : 0,
+                       c.inv, c.scores);
+    UMEREG_CHECK_LAUNCH("corr_reduce_kernel");
+    return UMEREG_OK;
 }
 
 // ---- FeatureCorrelator's pick (utils/loc_utils.py:676-680): the hypothesis with the highest score -------------------------
@@ -1029,6 +1108,17 @@ __global__ __launch_bounds__(1024) void corr_select_best_kernel(const float* __r
 }
 
 }  // namespace umereg
+
+UMEREG_API int umereg_corr_select_best_f32(const float* scores, const float* T, int M, float* T_best, int64_t* best_index, void* stream)
+{
+    using namespace umereg;
+    UMEREG_REQUIRE(scores && T && T_best, "corr_select_best: null pointer");
+    UMEREG_REQUIRE(M > 0, "corr_select_best: M must be positive (got %d)", M);
+    if (int rc = check_device()) return rc;
+    hipLaunchKernelGGL(corr_select_best_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, scores, T, M, T_best, best_index);
+    UMEREG_CHECK_LAUNCH("corr_select_best_kernel");
+    return UMEREG_OK;
+}
 
 #ifdef UMEREG_KNN_DEBUG
 UMEREG_API int umereg_knn_debug_counters(unsigned long long* out16, int reset)
