@@ -1,0 +1,257 @@
+"""GPU: the backward pass of include/umereg_rtume_grad.h and `cube_loss.CubeRegistrationLoss` on top of it -- both gradients of the
+RTUME solve gated at sizes on every side of the launch's edges, on thin neighbourhoods with reflections, one side at a time,
+across the convention at the rotation's singularity, twice between guard bands, the loss against the reference's own class
+(tests/golden/g15_cube_registration.npz) and the trainer's `ume + reg` through the whole graph.
+
+Yardsticks: tests/cube_loss_ref.py in fp64 is the truth; the SAME helper in fp32 on the CPU sets every gate
+(max |gpu - fp64| <= 4 max |fp32 helper - fp64| per tensor, ume_grad_ref.gate); never the GPU's own output."""
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import cube_loss_ref as cref
+import ume_grad_ref as uref
+from test_abi_guard import Guard
+
+pytestmark = pytest.mark.gpu
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+SIZES = [1, 2, 15, 257, 4096]       # one hypothesis, both halves of a wavefront, a partly filled workgroup, no multiple of 8, many workgroups
+
+
+@functools.lru_cache(maxsize=None)
+def solve_case(n, thin):
+    """(G, H, dT) fp32, fp64 autograd (T, dG, dH), the fp32 helper's (T, dG, dH), and the case's distance to the singularity"""
+    G, H, dT = cref.ume_pairs(n, 1000 * int(thin) + n, thin=thin)
+    truth = cref.solve_grads(G.double(), H.double(), dT.double())
+    yard = cref.solve_grads(G, H, dT)
+    return (G, H, dT), truth, yard, cref.conditioning(G, H)
+
+
+def run_solve(gpu, G, H, dT):
+    from umeregrobust_amd import rtume_grad
+    a, b = G.to(gpu).requires_grad_(), H.to(gpu).requires_grad_()
+    T = rtume_grad.rtume_solve(a, b)
+    (T * dT.to(gpu)).sum().backward()
+    return T.detach(), a.grad, b.grad
+
+
+def check_solve(gpu, n, thin):
+    from umeregrobust_amd import ops
+    (G, H, dT), truth, yard, (cond, s1_s3, flips) = solve_case(n, thin)
+    print(f"[case] n={n} thin={thin}: max s1 / (s2 + d s3) {cond:.2f}  max s1 / s3 {s1_s3:.3g}  d = -1: {flips}")
+    assert cond <= 20, "the case must not stand on the convention"
+    T, dG, dH = run_solve(gpu, G, H, dT)
+    assert torch.equal(T, ops.rtume_solve(G.to(gpu), H.to(gpu))[0])
+    assert float((T.cpu().double() - truth[0]).abs().max()) <= 4 * float((yard[0].double() - truth[0]).abs().max())
+    uref.gate(dG, truth[1], yard[1], f"dG n={n} thin={thin}")
+    uref.gate(dH, truth[2], yard[2], f"dH n={n} thin={thin}")
+    return s1_s3, flips
+
+
+# ---- 1 / 2: the backward against the truth -----------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n", SIZES)
+def test_backward_against_truth(gpu, n):
+    """1: normalised moment matrices of 200-point neighbourhoods, the target the source under a rotation of 0.7 rad plus noise,
+    random dT"""
+    check_solve(gpu, n, thin=False)
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_backward_on_thin_neighbourhoods(gpu, n):
+    """2: the same with the neighbourhood's third axis scaled by 0.005: s1 / s3 up to 1e8, and about one pair in a hundred with
+    det(U V^T) = -1 (so the reflections are asserted where there are a hundred pairs).  A backward through A^T A, or one that
+    loses the sign of the third value, fails here."""
+    s1_s3, flips = check_solve(gpu, n, thin=True)
+    assert s1_s3 >= 1e4
+    if n >= 257:
+        assert flips > 0 and s1_s3 >= 1e6
+
+
+# ---- 3: one side only --------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("side", [0, 1])
+def test_backward_one_side_only(gpu, side):
+    from umeregrobust_amd import rtume_grad
+    (G, H, dT), truth, yard, _ = solve_case(15, False)
+    _, dG, dH = run_solve(gpu, G, H, dT)
+    both = rtume_grad.rtume_bwd_raw(G.to(gpu), H.to(gpu), dT.to(gpu))
+    one = rtume_grad.rtume_bwd_raw(G.to(gpu), H.to(gpu), dT.to(gpu), need_g=side == 0, need_h=side == 1)
+    assert one[1 - side] is None and torch.equal(one[side], both[side]) and torch.equal(both[side], (dG, dH)[side])
+    t = [G.to(gpu), H.to(gpu)]
+    t[side].requires_grad_()
+    (rtume_grad.rtume_solve(*t) * dT.to(gpu)).sum().backward()
+    assert t[1 - side].grad is None and torch.equal(t[side].grad, both[side])
+    uref.gate(t[side].grad, truth[1 + side], yard[1 + side], ("dG", "dH")[side] + " alone")
+
+
+def test_no_hypothesis_no_launch(gpu):
+    from umeregrobust_amd import rtume_grad
+    a, b = torch.zeros(0, 32, 4, device=gpu, requires_grad=True), torch.zeros(0, 32, 4, device=gpu, requires_grad=True)
+    T = rtume_grad.rtume_solve(a, b)
+    T.sum().backward()
+    assert T.shape == (0, 4, 4) and a.grad.shape == (0, 32, 4) and b.grad.shape == (0, 32, 4)
+
+
+# ---- 4: the convention ---------------------------------------------------------------------------------------------------------
+
+def degenerate_pairs():
+    """three pairs at the rotation's singularity: A = 0 (all coordinates zero), rank 1 (all points on one line), and
+    A = diag(1, 0.5, -0.5) (s2 + d s3 = 0, up to the fp32 rounding of the orthonormal columns)"""
+    g = torch.Generator().manual_seed(4)
+    G, H = torch.zeros(3, 32, 4), torch.zeros(3, 32, 4)
+    G[:2, :, 0], H[:2, :, 0] = torch.rand(2, 32, generator=g) + 0.1, torch.rand(2, 32, generator=g) + 0.1
+    line = torch.tensor([1.0, 2.0, -1.0])
+    G[1, :, 1:], H[1, :, 1:] = torch.randn(32, 1, generator=g) * line, torch.randn(32, 1, generator=g) * line
+    q = torch.linalg.qr(torch.cat([torch.ones(32, 1, dtype=torch.float64), torch.randn(32, 3, generator=g, dtype=torch.float64)], dim=1)).Q
+    G[2, :, 0] = H[2, :, 0] = 1.0
+    G[2, :, 1:] = q[:, 1:].float()
+    H[2, :, 1:] = G[2, :, 1:] * torch.tensor([1.0, 0.5, -0.5])
+    return G, H
+
+
+def test_convention_at_the_singularity(gpu):
+    """4: well-conditioned pairs and the three degenerate ones in one launch, the degenerate ones in the first, an odd and the last
+    position (each shares its wavefront with a well-conditioned pair): everything finite, and the well-conditioned rows bit-equal
+    to a launch without the degenerate ones"""
+    from umeregrobust_amd import rtume_grad
+    (G, H, dT), _, _, _ = solve_case(15, False)
+    Gd, Hd = degenerate_pairs()
+    S, d = cref.spectrum(Gd.double(), Hd.double())
+    print(f"[convention] singular values of the degenerate pairs: {S.tolist()}  d: {d.tolist()}")
+    assert float(S[0].max()) == 0 and float(S[1, 1]) <= 1e-12 * float(S[1, 0]) and float((S[2, 1] - S[2, 2]).abs()) <= 1e-6 and float(d[2]) == -1
+    where = [0, 5, 17]                                      # positions of the degenerate pairs among 18
+    good = [i for i in range(18) if i not in where]
+    Gm, Hm, dTm = torch.zeros(18, 32, 4), torch.zeros(18, 32, 4), torch.randn(18, 4, 4, generator=torch.Generator().manual_seed(5))
+    Gm[good], Hm[good], dTm[good] = G, H, dT
+    Gm[where], Hm[where] = Gd, Hd
+    T, dG, dH = run_solve(gpu, Gm, Hm, dTm)
+    assert torch.isfinite(T).all() and torch.isfinite(dG).all() and torch.isfinite(dH).all()
+    _, dG0, dH0 = run_solve(gpu, G, H, dT)
+    assert torch.equal(dG[good], dG0) and torch.equal(dH[good], dH0)
+    # the raw entry: the same bits
+    raw = rtume_grad.rtume_bwd_raw(Gm.to(gpu), Hm.to(gpu), dTm.to(gpu))
+    assert torch.equal(raw[0], dG) and torch.equal(raw[1], dH)
+
+
+# ---- 5: determinism and bounds -------------------------------------------------------------------------------------------------
+
+def test_entry_is_deterministic_between_guard_bands(gpu):
+    """5: the entry twice between 4 KiB canary bands, with both outputs and with each alone: bands intact, an output that was not asked
+    for untouched, outputs byte-equal between the runs and between the three forms"""
+    from umeregrobust_amd import rtume_grad
+    rtume_grad.load_native()
+    (G, H, dT), _, _, _ = solve_case(257, True)
+    n = G.shape[0]
+    outs = []
+    for run in range(2):
+        gd = Guard(gpu, run)
+        p_G, _ = gd.inp(G.numpy(), "G")
+        p_H, _ = gd.inp(H.numpy(), "H")
+        p_dT, _ = gd.inp(dT.numpy(), "dT")
+        res = []
+        for want_g, want_h in ((1, 1), (1, 0), (0, 1)):
+            p_dG, t_dG = gd.out((n, 32, 4), torch.float32, "dG")
+            p_dH, t_dH = gd.out((n, 32, 4), torch.float32, "dH")
+            gd.call("umereg_rtume_solve_bwd_f32", p_G, p_H, p_dT, n, p_dG if want_g else None, p_dH if want_h else None, gd.stream)
+            gd.check()
+            for t, w in ((t_dG, want_g), (t_dH, want_h)):
+                if w:
+                    res.append(t)
+                else:
+                    assert bool((t.view(torch.uint8) == gd.poison).all()), "an output that was not asked for was written"
+        assert gd.called == {"umereg_rtume_solve_bwd_f32"}
+        outs.append([t.clone() for t in res])
+    assert len(outs[0]) == 4
+    for a, b in zip(*outs):
+        assert torch.isfinite(a).all() and torch.equal(a.view(torch.int32), b.view(torch.int32))
+    assert torch.equal(outs[0][0], outs[0][2]) and torch.equal(outs[0][1], outs[0][3])
+
+
+# ---- 6: the loss against the reference's own class -----------------------------------------------------------------------------
+
+def _g(name):
+    return np.load(os.path.join(GOLDEN, name))
+
+
+def check_loss(gpu, name, extra_batch_entry):
+    from umeregrobust_amd.cube_loss import CubeRegistrationLoss
+    g14, g15 = _g("g14_ume_contrastive.npz"), _g("g15_cube_registration.npz")
+    thr, scale = float(g15[f"{name}_thr"]), float(g15["cfg_cube_scale"])
+    t = lambda k, dt=None: torch.from_numpy(g14[k]) if dt is None else torch.from_numpy(g14[k]).to(dt)      # noqa: E731
+    gt, valid = t("gt_tform"), t("with_kpts")
+    if extra_batch_entry:       # a batch element without keypoints in the middle: its gt_tform must not be read
+        gt = torch.stack([gt[0], torch.full((4, 4), float("nan")), gt[1]])
+        valid = torch.tensor([True, False, True])
+    fn = CubeRegistrationLoss(int(g15["cfg_rtume_max_nn"]), float(g15["cfg_rtume_r_nn"]), cube_scale=scale, nn_inter_ratio_thr=thr)
+    a, b = t("velo_ume").to(gpu).requires_grad_(), t("ref_ume").to(gpu).requires_grad_()
+    loss, rre, rte = fn(t("velo_kp").to(gpu), a, t("ref_kp").to(gpu), b, gt.to(gpu), t("ratio").to(gpu), valid.to(gpu))
+    loss.backward()
+    assert rre.shape == rte.shape == (2, 48) and not rre.requires_grad and not rte.requires_grad
+    truth = cref.loss_and_grads(t("velo_ume", torch.float64), t("ref_ume", torch.float64), gt.double(), t("ratio"), valid, scale, thr)
+    yard = cref.loss_and_grads(t("velo_ume"), t("ref_ume"), gt, t("ratio"), valid, scale, thr)
+    for got, t64, y32, key in zip((loss, rre, rte, a.grad, b.grad), truth, yard, ("loss", "rre", "rte", "grad_src_ume", "grad_tgt_ume")):
+        e_gpu = float((got.detach().cpu().double() - t64).abs().max())
+        e_ref = float((torch.from_numpy(g15[f"{name}_{key}"]).double() - t64).abs().max())
+        e_cpu = float((y32.double() - t64).abs().max())
+        print(f"[loss {name}] {key}: max|gpu - fp64| {e_gpu:.3e}  max|reference - fp64| {e_ref:.3e}  max|fp32 helper - fp64| {e_cpu:.3e}  "
+              f"ratio {e_gpu / max(e_ref, e_cpu):.3f}  (max|truth| {float(t64.abs().max()):.3e})")
+        assert torch.isfinite(got).all() and e_gpu <= 4 * max(e_ref, e_cpu), key
+
+
+@pytest.mark.parametrize("name", ["main", "median"])
+def test_loss_equals_the_reference_s(gpu, name):
+    """6: the fixture, on the threshold's main branch and on the fall-back to the per-row median: loss, rre, rte and both UME
+    gradients within 4 x max(|reference - fp64|, |fp32 helper - fp64|)"""
+    check_loss(gpu, name, extra_batch_entry=False)
+
+
+def test_loss_with_a_dropped_batch_element(gpu):
+    """6: `valid_batch_entries` drops an element of gt_tform (all NaN here: it must not reach the loss)"""
+    check_loss(gpu, "main", extra_batch_entry=True)
+
+
+# ---- 7: through the whole graph ------------------------------------------------------------------------------------------------
+
+def test_ume_plus_reg_through_the_whole_graph(gpu):
+    """7: the trainer's line 58 on the clouds of g14: `UMEContrastiveLoss`, then `CubeRegistrationLoss` on what it returned,
+    backward() of their sum; the gradients with respect to both feature tensors against ume_grad_ref + cube_loss_ref on the
+    fixture's neighbour lists"""
+    from umeregrobust_amd.cube_loss import CubeRegistrationLoss
+    from umeregrobust_amd.ume_loss import UMEContrastiveLoss
+    g = _g("g14_ume_contrastive.npz")
+    cfg = {k: float(g[f"cfg_{k}"]) for k in ("nn_r", "tau", "tau_neg", "nn_intersection_r", "svd_thr")}
+    thr = 0.76      # (several of the fixture's ratios ARE 0.75; none is within 1e-3 of this one, and the GPU's ratio agrees to 1e-6)
+    assert float(np.abs(g["ratio"] - thr).min()) > 1e-3 and int((g["ratio"] >= thr).sum()) >= 48 and bool(g["with_kpts"].all())
+    ume_fn = UMEContrastiveLoss(num_samples=int(g["cfg_num_samples"]), max_nn=int(g["cfg_max_nn"]), min_nn=int(g["cfg_min_nn"]),
+                                flat_labels=[int(v) for v in g["cfg_flat_labels"]], **cfg)
+    reg_fn = CubeRegistrationLoss(int(g["cfg_max_nn"]), cfg["nn_r"], nn_inter_ratio_thr=thr)
+    t = lambda k: torch.from_numpy(g[k]).to(gpu)          # noqa: E731
+    vf, rf = t("velo_feat").requires_grad_(), t("ref_feat").requires_grad_()
+    gt = t("gt_tform")
+    l_ume, velo_kp, ref_kp, velo_ume, ref_ume, ratio, with_kpts = ume_fn(t("velo_pts"), t("velo_seg"), vf, t("ref_pts"), rf, gt)
+    l_reg, rre, rte = reg_fn(velo_kp, velo_ume, ref_kp, ref_ume, gt, ratio, with_kpts)
+    (l_ume + l_reg).backward()
+    assert velo_ume.shape == (2, 48, 32, 4) and np.abs(ratio.cpu().numpy() - g["ratio"]).max() < 1e-6
+
+    def total(dt):
+        c = lambda k: torch.from_numpy(g[k]).to(dt)          # noqa: E731
+        a, b = c("velo_feat").requires_grad_(), c("ref_feat").requires_grad_()
+        vu = uref.moments(c("velo_pts"), a, torch.from_numpy(g["velo_nn_idx"]).long(), True)
+        ru = uref.moments(c("ref_pts"), b, torch.from_numpy(g["ref_nn_idx"]).long(), True)
+        l1 = uref.contrastive(vu, ru, cfg["tau"], cfg["tau_neg"])
+        l2, _, _ = cref.cube_loss(vu, ru, c("gt_tform"), torch.from_numpy(g["ratio"]), torch.from_numpy(g["with_kpts"]), 1.0, thr)
+        (l1 + l2).backward()
+        return (l1 + l2).detach(), l2.detach(), a.grad, b.grad
+
+    l64, reg64, gv64, gr64 = total(torch.float64)
+    l32, reg32, gv32, gr32 = total(torch.float32)
+    print(f"[ume + reg] gpu {float((l_ume + l_reg).detach()):.7f} (reg {float(l_reg.detach()):.7f})  fp64 {float(l64):.7f} (reg {float(reg64):.7f})  "
+          f"fp32 helper {float(l32):.7f}")
+    assert float(reg64) > 0.05 * float(l64), "the registration term must weigh in the sum"
+    uref.gate(vf.grad, gv64, gv32, "d(ume + reg) / d velo_feat")
+    uref.gate(rf.grad, gr64, gr32, "d(ume + reg) / d ref_feat")

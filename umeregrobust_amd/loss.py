@@ -3,8 +3,8 @@
 `MyInfoNCELossNoSeg` -- the point-wise contrastive loss of the reference's trainer (train_coloring.py:44-45; loss.py:10-46) --
 is plain torch on top of the feature network's differentiable output, with the reference's signature and the reference's
 order of operations, so that fp32 values agree to rounding.  The working `UMEContrastiveLoss` lives in `ume_loss.py`, on the
-differentiable UME moments and subspace distances of `ume_grad.py`; the name here still refuses and points there.
-`CubeRegistrationLoss` needs a differentiable RTUME, which the HIP kernels of this library do not have yet."""
+differentiable UME moments and subspace distances of `ume_grad.py`, and the working `CubeRegistrationLoss` in `cube_loss.py`, on the
+differentiable RTUME solve of `rtume_grad.py`; the two names here still refuse and point there."""
 import torch
 from torch import nn
 from torch.nn import functional as tnf
@@ -45,5 +45,5 @@ class UMEContrastiveLoss(nn.Module):
 
 class CubeRegistrationLoss(nn.Module):
     def __init__(self, *args, **kwargs):
-        raise NotImplementedError("CubeRegistrationLoss needs a differentiable RTUME; the HIP kernels of this library are "
-                                  "forward only (out of scope of the trainable feature network)")
+        raise NotImplementedError("loss.CubeRegistrationLoss is out of scope of this module: the working class is "
+                                  "umeregrobust_amd.cube_loss.CubeRegistrationLoss (same constructor, same return values)")
