@@ -63,16 +63,106 @@ def write_cached_pair(path, item, src_feat=None, tgt_feat=None):
         pickle.dump(d, handle, protocol=pickle.HIGHEST_PROTOCOL)
 
 
+def z_rotation_matrix(deg):
+    """`scipy.spatial.transform.Rotation.from_euler('z', deg, degrees=True).as_matrix()` (kitti_dataset.py:473-474) in own
+    code: fp64 [[c, -s, 0], [s, c, 0], [0, 0, 1]] with c, s the cosine and sine of the angle in radians."""
+    a = np.deg2rad(np.float64(deg))
+    c, s = np.cos(a), np.sin(a)
+    return np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]], dtype=np.float64)
+
+
+def rotate_rows(pts, rot):
+    """`pts @ rot` (kitti_dataset.py:476-477) for pts f32 [n,3] and rot f32 [3,3] on the device of `pts`, in a stated order:
+    column k = (x rot[0,k] + y rot[1,k]) + z rot[2,k], every product and sum rounded to fp32 on its own (a BLAS matmul may
+    fuse or reorder them; the result differs from it in the last bit at most)."""
+    x, y, z = pts[:, 0:1], pts[:, 1:2], pts[:, 2:3]
+    return (x * rot[0][None, :] + y * rot[1][None, :]) + z * rot[2][None, :]
+
+
+def quantize_on_device(pts, voxel_size):
+    """`ME.utils.sparse_quantize(coordinates=pts, return_index=True, quantization_size=voxel_size)` (kitti_dataset.py:416-419,
+    :480-487) on the device: (coords int32 [m,3] = floor(p / voxel) of the first point of every occupied voxel, inds int64 [m]
+    ascending).  `ops.voxel_first_index` restates MinkowskiEngine's choice of representative (parity unpinned, as everywhere).
+    The division is a true fp32 division, like the kernel's (torch turns a division by a Python number into a multiplication
+    by its reciprocal on the device, which can land on the other side of a voxel boundary)."""
+    from .. import ops
+    inds = ops.voxel_first_index(pts.contiguous(), float(voxel_size))
+    coords = torch.floor(pts[inds] / torch.tensor(float(voxel_size), dtype=torch.float32, device=pts.device)).to(torch.int32)
+    return coords, inds
+
+
+def _refuse_gpu_in_worker(what):
+    if torch.utils.data.get_worker_info() is not None:
+        raise RuntimeError(f"{what} runs on the GPU and was asked for inside a DataLoader worker process: a forked worker must "
+                           "not open the GPU.  Use num_workers=0 (the item's work is a few kernel launches)")
+
+
+def augmented_gt_tform(gt_tform, rot_src, rot_tgt):
+    """The ground truth between the two rotated clouds, by the reference's expressions (kitti_dataset.py:492-499), on the host
+    in fp32 as there: R' = (rot_src^T R^T rot_tgt)^T, t' = t rot_tgt."""
+    T = torch.as_tensor(gt_tform).float()
+    out = torch.zeros_like(T)
+    out[:3, :3] = ((rot_src.T @ T[:3, :3].T) @ rot_tgt).T
+    out[:3, 3] = T[:3, 3] @ rot_tgt
+    out[3, 3] = 1
+    return out
+
+
+def augmented_item(item, voxel_size, rng, device, phase=None):
+    """`cached_getitem_augmented` (kitti_dataset.py:460-509; the same in nuscenes_dataset.py:467-516) on the device: two
+    rotations about z drawn as `rng.uniform(-180, 180)` (source first, then target), both clouds rotated (rotate_rows),
+    re-quantised (quantize_on_device) and turned into grid points, the ground truth re-expressed in the rotated frames
+    (augmented_gt_tform), and new one-side matches at voxel_size / 2.  -> the 9-tuple, on the host.
+    phase: optional `phase(name)` -> context manager entered around each part ("to_device", "thinning", "grid_points", "matches",
+    "to_host"): how tools/train_step_time.py times the parts of exactly this code."""
+    from contextlib import nullcontext
+
+    from ..utils.general_utils import convert_coords_to_grid_pts, one_side_ball_query_matches
+    phase = phase or (lambda name: nullcontext())
+    dev = torch.device(device)
+    rots = [torch.from_numpy(z_rotation_matrix(rng.uniform(low=-180, high=180))).float() for _ in ("src", "tgt")]
+    sides = []
+    for first, rot in ((0, rots[0]), (3, rots[1])):
+        with phase("to_device"):
+            pts, seg, rot_dev = torch.as_tensor(item[first]).float().to(dev), torch.as_tensor(item[first + 1]).to(dev), rot.to(dev)
+        with phase("thinning"):
+            pts = rotate_rows(pts, rot_dev)
+            coords, inds = quantize_on_device(pts, voxel_size)
+            seg = seg[inds]
+        with phase("grid_points"):
+            grid = convert_coords_to_grid_pts(pts, coords, voxel_size)
+        sides.append((grid, seg, coords))
+    gt_tform = augmented_gt_tform(item[7], rots[0], rots[1])
+    with phase("matches"):
+        T_dev = gt_tform.to(dev)
+        src_grid, tgt_grid = sides[0][0], sides[1][0]
+        moved = rotate_rows(src_grid, T_dev[:3, :3].T.contiguous()) + T_dev[:3, 3]
+        matches = one_side_ball_query_matches(src_grid, tgt_grid, T_dev, voxel_size / 2).long()
+    with phase("to_host"):
+        out = tuple(t.cpu() for t in (*sides[0], *sides[1], moved)) + (gt_tform, matches.cpu())
+    return out
+
+
 class CachedPairDataset(torch.utils.data.Dataset):
     """The cache-backed half of the reference's SemanticKITTIDataset / NuscenesDataset (`cache_data_path != ""`,
     kitti_dataset.py:380-385): item i = the pickle of pair i.  The reference takes its pair list from the raw dataset's
     pose files; here it is the sorted content of `<cache_data_path>/<split>/*/` (or an explicit list of
-    (seq_id, frame0_id, frame1_id))."""
+    (seq_id, frame0_id, frame1_id)).
 
-    def __init__(self, cache_data_path, split="test", files=None, with_features=False, dataset="kitti"):
+    use_augmentations: every item goes through `augmented_item` (the reference's `cached_getitem_augmented`) on `device`
+    (default: the current HIP device) with angles from `rng` (default: the global numpy stream, like the reference).  The
+    reference hides that work -- two KDTree builds' worth per item -- behind loader workers; here it is a few kernel launches
+    in the loading process, and asking for it inside a worker raises: use num_workers=0, with which the host RNG is also
+    consumed in the reference's order (item draws, then the collate's)."""
+
+    def __init__(self, cache_data_path, split="test", files=None, with_features=False, dataset="kitti", use_augmentations=False,
+                 voxel_size=0.3, device=None, rng=np.random):
         """dataset: "kitti" -- sequence ids are integers, directories `%02d` (kitti_dataset.py:444); "nuscenes" -- sequence
         ids are the directory names themselves (nuscenes_dataset.py:452)."""
         self.cache_data_path, self.split, self.with_features, self.dataset = cache_data_path, split, with_features, dataset
+        self.use_augmentations, self.voxel_size, self.device, self.rng = bool(use_augmentations), voxel_size, device, rng
+        if self.use_augmentations and with_features:
+            raise ValueError("CachedPairDataset: cached features belong to the cached points; an augmented item has other points")
         if files is None:
             files = []
             for p in sorted(glob.glob(os.path.join(cache_data_path, split, "*", "*.pickle"))):
@@ -90,7 +180,14 @@ class CachedPairDataset(torch.utils.data.Dataset):
         return len(self.files)
 
     def __getitem__(self, idx):
-        return read_cached_pair(self.path(idx), self.with_features)
+        item = read_cached_pair(self.path(idx), self.with_features)
+        if not self.use_augmentations:
+            return item
+        _refuse_gpu_in_worker("CachedPairDataset(use_augmentations=True)")
+        if not torch.cuda.is_available():
+            raise RuntimeError("CachedPairDataset(use_augmentations=True) needs a HIP device; there is no CPU fallback")
+        device = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+        return augmented_item(item, self.voxel_size, self.rng, device)
 
 
 def sparse_collate(coords, feats):

@@ -222,3 +222,57 @@ def ragged_sizes(seed, lo=35000, hi=50000):
     pair to pair and between the two clouds of a pair (kitti_dataset.py:568-569)."""
     r = np.random.RandomState(1_000_003 + seed)
     return int(r.randint(lo, hi + 1)), int(r.randint(lo, hi + 1))
+
+
+FLAT_LABEL = 9      # the class the UME loss treats as flat ground (its `flat_labels` default; SemanticKITTI's remapped road)
+
+
+def synth_train_item(seed, N=3000, voxel=0.3, kind="test", keep=0.8, device=None):
+    """One TRAINING item -- the 9-tuple of a pair-cache file, as `preprocess_getitem` builds it from two labelled scans
+    (reference datasets/kitti/kitti_dataset.py:388-439) -- from `synth_scene`, so that the training driver and its tests need
+    no dataset:
+
+      * a scene of N / keep lattice points (moved to the voxel centres, so that no point sits on a voxel boundary); source and
+        target each keep a random N of them (a point has a twin where both kept it), the target rigidly moved (`kind` as in
+        synth_pair);
+      * seg labels: FLAT_LABEL (9) on the ground (z below -1.4 m in the scene frame), 1..8 on walls, by wall patch;
+      * both clouds quantised on the device (coords = floor(p / voxel) of every voxel's first point), grid points by
+        `convert_coords_to_grid_pts`, `matches` from `mutual_ball_query_matches` at voxel / 2 (:433), src_pts_tform (:437).
+
+    -> (src_pts f32 [n,3], src_seg i64 [n], src_coords i32 [n,3], tgt_pts, tgt_seg, tgt_coords, src_pts_tform f32 [n,3],
+        gt_tform f32 [4,4], matches i64 [m,2]), torch tensors on the host.  The quantisation and the matches run on the GPU
+    (`device`, default the current HIP device): this is the one function of this module that needs one."""
+    import torch
+
+    from .datasets.kitti_dataset import _refuse_gpu_in_worker, quantize_on_device, rotate_rows
+    from .utils.general_utils import convert_coords_to_grid_pts, mutual_ball_query_matches
+    _refuse_gpu_in_worker("synth_train_item")
+    if not torch.cuda.is_available():
+        raise RuntimeError("synth_train_item quantises and matches on the GPU; there is no HIP device and no CPU fallback")
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    rng = np.random.RandomState(seed)
+    n_all = int(np.ceil(N / keep))
+    scene = synth_scene(rng, n_all, voxel)
+    ground = scene[:, 2] < -1.4
+    patch = (np.round(scene[:, 0] / 8.0) * 3 + np.round(scene[:, 1] / 8.0) * 5).astype(np.int64)
+    seg = np.where(ground, FLAT_LABEL, 1 + patch % 8).astype(np.int64)
+    scene = scene + 0.5 * voxel
+    deg = np.pi / 180.0
+    yaw = (rng.uniform(30.0, 180.0) * rng.choice([-1.0, 1.0]) if kind == "rot" else rng.normal(0.0, 5.0)) * deg
+    R = _rot(rng.normal(0, 1.0) * deg, rng.normal(0, 1.0) * deg, yaw)
+    tdir = rng.standard_normal(3) * np.array([1.0, 1.0, 0.05])
+    t = tdir / np.linalg.norm(tdir) * rng.uniform(1.0, 5.0)
+    si, ti = rng.permutation(n_all)[:N], rng.permutation(n_all)[:N]
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = R, t
+    gt_tform = torch.from_numpy(T.astype(np.float32))
+    sides = []
+    for pts, labels in ((scene[si], seg[si]), ((scene @ R.T + t)[ti], seg[ti])):
+        pts = torch.from_numpy(pts.astype(np.float32)).to(dev)
+        coords, inds = quantize_on_device(pts, voxel)
+        sides.append((convert_coords_to_grid_pts(pts, coords, voxel), torch.from_numpy(labels).to(dev)[inds], coords))
+    (src_grid, src_seg, src_coords), (tgt_grid, tgt_seg, tgt_coords) = sides
+    T_dev = gt_tform.to(dev)
+    matches = mutual_ball_query_matches(src_grid, tgt_grid, gt_tform, voxel / 2).long()
+    src_pts_tform = rotate_rows(src_grid, T_dev[:3, :3].T.contiguous()) + T_dev[:3, 3]
+    return tuple(x.cpu() for x in (src_grid, src_seg, src_coords, tgt_grid, tgt_seg, tgt_coords, src_pts_tform, gt_tform, matches))

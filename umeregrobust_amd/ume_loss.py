@@ -62,7 +62,12 @@ class UMEContrastiveLoss(nn.Module):
         velo_ume = velo_ume[:, keep_kp]
         ref_ume = ref_ume[:, keep_kp]
         matched_nn_intersection_ratio = matched_nn_intersection_ratio[:, keep_kp]
-        D_ume = ume_grad.ume_cdist(velo_ume, ref_ume)                                   # (bs, n_samples, n_samples)
+        if velo_ume.shape[1] == 0:
+            # no keypoint column survived: the reference's distance matrix of two empty sets is empty and its loss the mean of nothing
+            # (NaN); the trainer tests `src_ume.shape[1] == 0` on what is returned here and skips the batch (train_coloring.py:50-52)
+            D_ume = velo_ume.new_zeros(velo_ume.shape[0], 0, 0)
+        else:
+            D_ume = ume_grad.ume_cdist(velo_ume, ref_ume)                               # (bs, n_samples, n_samples)
         ume_rank = velo_ume.shape[-1]
 
         sim_ume = (np.sqrt(ume_rank) - 2 * D_ume) / (np.sqrt(ume_rank))
