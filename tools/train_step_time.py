@@ -2,8 +2,9 @@
 r = 5, 256 UME samples, 512 point-wise samples.
 
     python tools/train_step_time.py [--points 50000] [--steps 7] [--warmup 3] [--out profiles/train/train_step_time.jsonl]
+    python tools/train_step_time.py --device-collate          # only the "device_collate" lines below
 
-Two kinds of lines (JSON, appended to --out):
+Three kinds of lines (JSON, appended to --out):
   * "phases": per-phase medians of one training step.  Device phases are timed with events on the stream after warm-up
     (the elapsed time between two events recorded around the phase, read after the step's final synchronisation); host phases
     (item read = unpickling a cache file, collate) with the host clock.  The augmentation is split into its parts: rotation +
@@ -14,7 +15,16 @@ Two kinds of lines (JSON, appended to --out):
     times each after a warm-up, and the medians reported; both include the one device -> host read of the row count.
     `nn1_pair` serves two clouds per call: its second one is given 64 points, so that it builds one 50 000-point structure,
     like the new call.  The same line carries the host cost of the reference's way: scipy's KDTree build + query + mask on
-    the same points (host clock, median of 3)."""
+    the same points (host clock, median of 3).
+  * "device_collate" (--device-collate): the trainer's loop on the same cached items in three forms, in one process --
+    "host" (items back to the host, `batch_collate_fn_dset`, batch up again, scalars read at once: the loop as it is without the
+    flag), "device" (items stay on the device, `collate.batch_collate_fn_dset_device`, scalars read at once) and "device_late" (the
+    same with the scalars read after the next batch has been fetched and collated: `--device-collate` of the driver).  The forms
+    take turns, --rounds times each, warmup + steps consecutive steps per turn; per turn the medians (host clock) of the step's
+    wall time from one `optimizer.step()` to the next, of the whole fetch (item read + augmentation + collate) and of the
+    collate call alone.  The difference between the "host" turns is the run-to-run spread against which the others are read.
+    "draws_ms" is the time of the collate's numpy draws alone (the same `choice` calls on the batch's sizes; the match draw on
+    the item's match count, an upper bound of its survivor count)."""
 import argparse
 import json
 import os
@@ -174,6 +184,83 @@ def match_compare(points, reps, warmup, dev, hard):
             "host_kdtree": {"median_ms": round(statistics.median(host), 3), "rows": int(host_rows.shape[0])}}
 
 
+def device_collate_compare(points, batch, steps, warmup, rounds, dev):
+    from umeregrobust_amd import train_coloring as tc
+    from umeregrobust_amd.collate import batch_collate_fn_dset_device
+    from umeregrobust_amd.datasets.kitti_dataset import augmented_item, batch_collate_fn_dset, read_cached_pair, write_cached_pair
+    from umeregrobust_amd.loss import MyInfoNCELossNoSeg
+    from umeregrobust_amd.models import ResUNetSmall2
+    from umeregrobust_amd.synth import synth_train_item
+    args = tc.make_config("kitti", batch_size=batch, device=str(dev))
+    tmp = tempfile.mkdtemp()
+    paths = []
+    for i in range(batch):
+        paths.append(os.path.join(tmp, f"{i}.pickle"))
+        write_cached_pair(paths[-1], synth_train_item(500 + i, N=points, device=dev))
+    torch.manual_seed(0)
+    rng = np.random.RandomState(0)
+    model = ResUNetSmall2(in_channels=1, out_channels=32, trainable=True).to(dev).train()
+    pw = MyInfoNCELossNoSeg(num_samples=args.num_pw_samples, tau=args.tau, neg_euclid_dist=tc.NEG_EUCLID_DIST)
+    opt = torch.optim.Adam(model.parameters(), lr=args.lr, weight_decay=0.0)
+    ctx = tc.TrainContext(args)
+    sizes = {}
+
+    def fetch(on_device, t_fetch, t_collate):
+        t0 = time.perf_counter()
+        items = [augmented_item(read_cached_pair(p), 0.3, rng, dev, to_host=not on_device) for p in paths]
+        t1 = time.perf_counter()
+        collate = batch_collate_fn_dset_device if on_device else batch_collate_fn_dset
+        data = collate(items, num_matches=args.num_pw_samples, max_pc_size=args.max_pc_size, rng=rng)
+        t2 = time.perf_counter()
+        t_fetch.append((t2 - t0) * 1e3)
+        t_collate.append((t2 - t1) * 1e3)
+        sizes.update(clouds=[(len(it[0]), len(it[3]), len(it[8])) for it in items], n_src=data[0].shape[1], n_tgt=data[4].shape[1],
+                     k=data[10].shape[1])
+        return data
+
+    def turn(on_device, late):
+        t_fetch, t_collate, stamps = [], [], []
+        data = fetch(on_device, t_fetch, t_collate)
+        for _ in range(warmup + steps + 1):
+            b = tc.Batch(data, dev)
+            terms, _ = tc.objective(b, tc.network_features(model, b.src), tc.network_features(model, b.tgt), pw, ctx)
+            opt.zero_grad()
+            terms["total"].backward()
+            opt.step()
+            stamps.append(time.perf_counter())
+            if late:
+                data = fetch(on_device, t_fetch, t_collate)
+                values = {k: float(v.detach()) for k, v in terms.items()}
+            else:
+                values = {k: float(v.detach()) for k, v in terms.items()}
+                data = fetch(on_device, t_fetch, t_collate)
+            assert np.isfinite(values["total"])
+        torch.cuda.synchronize()
+        wall = [(b - a) * 1e3 for a, b in zip(stamps, stamps[1:])]
+        med = lambda v: round(statistics.median(v[warmup:]), 4)                                             # noqa: E731
+        return {"step_wall_ms": med(wall), "step_wall_min_ms": round(min(wall[warmup:]), 4), "fetch_ms": med(t_fetch[1:]),
+                "collate_ms": med(t_collate[1:])}
+
+    forms = (("host", False, False), ("device", True, False), ("device_late", True, True))
+    res = {name: [] for name, _, _ in forms}
+    for _ in range(rounds):
+        for name, on_device, late in forms:
+            res[name].append(turn(on_device, late))
+    # the collate's draws alone, on the sizes of the last batch (a generator of their own: the loop's stream is not touched)
+    own, draws = np.random.RandomState(1), []
+    for _ in range(warmup + steps):
+        t0 = time.perf_counter()
+        for ns, nt, _ in sizes["clouds"]:
+            own.choice(ns, sizes["n_src"], replace=False)
+            own.choice(nt, sizes["n_tgt"], replace=False)
+        for _, _, m in sizes["clouds"]:
+            own.choice(max(m, sizes["k"]), sizes["k"], replace=False)          # (the item's match count stands in for its survivor count)
+        draws.append((time.perf_counter() - t0) * 1e3)
+    return {"kind": "device_collate", "points": points, "batch": batch, "steps": steps, "warmup": warmup, "rounds": rounds,
+            "collated_src_tgt_matches": (sizes["n_src"], sizes["n_tgt"], sizes["k"]), "draws_ms": round(statistics.median(draws[warmup:]), 4),
+            **res}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", type=int, default=50000)
@@ -182,10 +269,19 @@ def main():
     ap.add_argument("--match-reps", type=int, default=200)
     ap.add_argument("--batches", type=int, nargs="*", default=[2, 8])
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "train", "train_step_time.jsonl"))
+    ap.add_argument("--device-collate", action="store_true", help="only the host / device / device_late comparison of the collate")
+    ap.add_argument("--rounds", type=int, default=2, help="turns per form of the --device-collate comparison")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a") as f:
+        if a.device_collate:
+            for batch in a.batches:
+                line = device_collate_compare(a.points, batch, a.steps, a.warmup, a.rounds, dev)
+                print(json.dumps(line), flush=True)
+                f.write(json.dumps(line) + "\n")
+                f.flush()
+            return
         for hard in (False, True):
             line = match_compare(a.points, a.match_reps, 10, dev, hard)
             print(json.dumps(line), flush=True)

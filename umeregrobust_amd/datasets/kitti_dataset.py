@@ -108,11 +108,12 @@ def augmented_gt_tform(gt_tform, rot_src, rot_tgt):
     return out
 
 
-def augmented_item(item, voxel_size, rng, device, phase=None):
+def augmented_item(item, voxel_size, rng, device, phase=None, to_host=True):
     """`cached_getitem_augmented` (kitti_dataset.py:460-509; the same in nuscenes_dataset.py:467-516) on the device: two
     rotations about z drawn as `rng.uniform(-180, 180)` (source first, then target), both clouds rotated (rotate_rows),
     re-quantised (quantize_on_device) and turned into grid points, the ground truth re-expressed in the rotated frames
-    (augmented_gt_tform), and new one-side matches at voxel_size / 2.  -> the 9-tuple, on the host.
+    (augmented_gt_tform), and new one-side matches at voxel_size / 2.  -> the 9-tuple, on the host; with to_host=False on the device,
+    where it was made (the "to_host" phase is skipped): what `collate.batch_collate_fn_dset_device` takes without a round trip.
     phase: optional `phase(name)` -> context manager entered around each part ("to_device", "thinning", "grid_points", "matches",
     "to_host"): how tools/train_step_time.py times the parts of exactly this code."""
     from contextlib import nullcontext
@@ -132,12 +133,14 @@ def augmented_item(item, voxel_size, rng, device, phase=None):
         with phase("grid_points"):
             grid = convert_coords_to_grid_pts(pts, coords, voxel_size)
         sides.append((grid, seg, coords))
-    gt_tform = augmented_gt_tform(item[7], rots[0], rots[1])
+    gt_tform = augmented_gt_tform(torch.as_tensor(item[7]).cpu(), rots[0], rots[1])
     with phase("matches"):
         T_dev = gt_tform.to(dev)
         src_grid, tgt_grid = sides[0][0], sides[1][0]
         moved = rotate_rows(src_grid, T_dev[:3, :3].T.contiguous()) + T_dev[:3, 3]
         matches = one_side_ball_query_matches(src_grid, tgt_grid, T_dev, voxel_size / 2).long()
+    if not to_host:
+        return (*sides[0], *sides[1], moved, T_dev, matches)
     with phase("to_host"):
         out = tuple(t.cpu() for t in (*sides[0], *sides[1], moved)) + (gt_tform, matches.cpu())
     return out
@@ -156,10 +159,12 @@ class CachedPairDataset(torch.utils.data.Dataset):
     consumed in the reference's order (item draws, then the collate's)."""
 
     def __init__(self, cache_data_path, split="test", files=None, with_features=False, dataset="kitti", use_augmentations=False,
-                 voxel_size=0.3, device=None, rng=np.random):
+                 voxel_size=0.3, device=None, rng=np.random, items_on_device=False):
         """dataset: "kitti" -- sequence ids are integers, directories `%02d` (kitti_dataset.py:444); "nuscenes" -- sequence
-        ids are the directory names themselves (nuscenes_dataset.py:452)."""
+        ids are the directory names themselves (nuscenes_dataset.py:452).  items_on_device: an augmented item stays on the device
+        (`augmented_item(..., to_host=False)`), for the device-side collate; a plain item is the cache file's either way."""
         self.cache_data_path, self.split, self.with_features, self.dataset = cache_data_path, split, with_features, dataset
+        self.items_on_device = bool(items_on_device)
         self.use_augmentations, self.voxel_size, self.device, self.rng = bool(use_augmentations), voxel_size, device, rng
         if self.use_augmentations and with_features:
             raise ValueError("CachedPairDataset: cached features belong to the cached points; an augmented item has other points")
@@ -187,7 +192,7 @@ class CachedPairDataset(torch.utils.data.Dataset):
         if not torch.cuda.is_available():
             raise RuntimeError("CachedPairDataset(use_augmentations=True) needs a HIP device; there is no CPU fallback")
         device = self.device if self.device is not None else torch.device("cuda", torch.cuda.current_device())
-        return augmented_item(item, self.voxel_size, self.rng, device)
+        return augmented_item(item, self.voxel_size, self.rng, device, to_host=not self.items_on_device)
 
 
 def sparse_collate(coords, feats):

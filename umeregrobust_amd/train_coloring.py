@@ -23,7 +23,14 @@ The reference's behaviour is mirrored, quirks included; each is named where it h
   * without the registration loss the reference's `eval_one_epoch` raises on its return statement (`valid_reg_acc` is never
     bound); here `reg_acc` is 0.0 then.
 Loader workers: the augmented item opens the GPU, which a forked worker must not do -- `num_workers` of the config is
-overridden to 0 whenever items are made on the GPU (and the dataset raises if asked inside a worker anyway)."""
+overridden to 0 whenever items are made or collated on the GPU (and the dataset and the device collate raise if asked inside a
+worker anyway).
+
+`--device-collate` (`run(..., device_collate=True)`; not a config key: those are the reference's) keeps a training batch on the GPU
+end to end: items stay where the augmentation made them, `collate.batch_collate_fn_dset_device` gathers them there, and
+`train_one_epoch` reads a step's scalars one batch late, after it has fetched and collated the next batch, so that the host's share
+of the data side (item read, augmentation launches, the numpy draws, collate launches) runs under the device's backward pass.  What
+is computed, the order in which the host RNG is consumed and everything that is logged are the same as without the flag."""
 import argparse
 import json
 import os
@@ -36,6 +43,7 @@ import torch
 import torch.optim as optim
 
 from .cube_loss import CubeRegistrationLoss
+from .collate import batch_collate_fn_dset_device
 from .datasets.kitti_dataset import CachedPairDataset, batch_collate_fn_dset
 from .loss import MyInfoNCELossNoSeg
 from .models import ResUNetSmall2
@@ -169,11 +177,14 @@ class RunningSums:
         return self.v.get(k, 0.0)
 
 
-def train_one_epoch(epoch, data_loader, model, loss_func, optimizer, summary_writer, ctx):
+def train_one_epoch(epoch, data_loader, model, loss_func, optimizer, summary_writer, ctx, late_read=False):
     """The reference's train_one_epoch (train_coloring.py:20-93) with its globals in `ctx`.  Quirks kept: a batch without matches is
     dropped before the forward pass and one without UME keypoints after it (so batch-norm statistics have seen it), both before
     `zero_grad`: model parameters and optimizer stay untouched, and the batch still counts in the step numbering; without the UME
-    loss the total is the unweighted point-wise loss; every tenth iteration prints the mean of the last ten."""
+    loss the total is the unweighted point-wise loss; every tenth iteration prints the mean of the last ten.
+    late_read: the loop of `train_one_epoch_late_read` instead (same steps, same log; the scalars are read one batch late)."""
+    if late_read:
+        return train_one_epoch_late_read(epoch, data_loader, model, loss_func, optimizer, summary_writer, ctx)
     sums = RunningSums()
     n_batches = len(data_loader)
     for i, data in enumerate(data_loader):
@@ -198,6 +209,47 @@ def train_one_epoch(epoch, data_loader, model, loss_func, optimizer, summary_wri
         if (i + 1) % 10 == 0:
             print(" | ".join(f"{k} {sums.get(k) / 10:.4f}" for k in ("total", "pointwise", "ume", "reg")))
             sums = RunningSums()
+    print(f"train epoch {epoch + 1} done")
+
+
+def train_one_epoch_late_read(epoch, data_loader, model, loss_func, optimizer, summary_writer, ctx):
+    """`train_one_epoch` with the host reads of a step deferred: once `optimizer.step()` of batch i is enqueued, the NEXT batch is
+    fetched and collated first (the host work of the data side then runs while the device is still in the backward pass of batch
+    i), and only then are the scalars of batch i read, logged and printed.  Batches are fetched in the same order and between the
+    same two steps as in the plain loop, so the host RNG is consumed identically; `add_scalar` sees the same (tag, value, step) rows
+    in the same order; the two skip rules are the plain loop's.  The last batch is read before the function returns."""
+    sums = RunningSums()
+    n_batches = len(data_loader)
+    batches = iter(data_loader)
+    data = next(batches, None)
+    i = 0
+    while data is not None:
+        launched = None
+        if not has_matches(data):
+            print("no matches in this batch: skipped")
+            ctx.skipped["no_matches"] += 1
+        else:
+            batch = Batch(data, ctx.device)
+            terms, _ = objective(batch, network_features(model, batch.src), network_features(model, batch.tgt), loss_func, ctx)
+            if terms is None:
+                print("no UME keypoints in this batch: skipped")
+                ctx.skipped["no_keypoints"] += 1
+            else:
+                optimizer.zero_grad()
+                terms["total"].backward()
+                optimizer.step()
+                launched = {k: v.detach() for k, v in terms.items()}
+        data = next(batches, None)                        # item read, augmentation, draws, collate: under the step just enqueued
+        if launched is not None:
+            values = {k: float(v) for k, v in launched.items()}
+            sums.add(**values)
+            for k in ("total", "pointwise", "ume", "reg"):
+                if k in values:
+                    summary_writer.add_scalar(f"train/{k}_loss", values[k], epoch * n_batches + i)
+            if (i + 1) % 10 == 0:
+                print(" | ".join(f"{k} {sums.get(k) / 10:.4f}" for k in ("total", "pointwise", "ume", "reg")))
+                sums = RunningSums()
+        i += 1
     print(f"train epoch {epoch + 1} done")
 
 
@@ -303,10 +355,20 @@ def create_params_dict(args, run_name, out_path, model):
 class SyntheticPairs(torch.utils.data.Dataset):
     """`n_items` items of `synth.synth_train_item` (made once, on the GPU, in the constructor), optionally augmented like a cache item."""
 
-    def __init__(self, n_items, n_points=3000, seed=0, use_augmentations=False, voxel_size=0.3, device=None, rng=np.random):
+    def __init__(self, n_items, n_points=3000, seed=0, use_augmentations=False, voxel_size=0.3, device=None, rng=np.random,
+                 items_on_device=False):
+        """items_on_device: the stored items live on the device (all but gt_tform, which the augmentation reads on the host), and an
+        augmented item stays there: for the device-side collate."""
         from .synth import synth_train_item
         self.items = [synth_train_item(seed + i, N=n_points, voxel=voxel_size, device=device) for i in range(n_items)]
         self.use_augmentations, self.voxel_size, self.device, self.rng = use_augmentations, voxel_size, device, rng
+        self.items_on_device = bool(items_on_device)
+        if self.items_on_device:
+            dev = self._device()
+            self.items = [tuple(t if k == 7 else t.to(dev) for k, t in enumerate(item)) for item in self.items]
+
+    def _device(self):
+        return torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
 
     def __len__(self):
         return len(self.items)
@@ -316,38 +378,45 @@ class SyntheticPairs(torch.utils.data.Dataset):
             return self.items[idx]
         from .datasets.kitti_dataset import _refuse_gpu_in_worker, augmented_item
         _refuse_gpu_in_worker("SyntheticPairs(use_augmentations=True)")
-        return augmented_item(self.items[idx], self.voxel_size, self.rng, self.device or torch.device("cuda", torch.cuda.current_device()))
+        return augmented_item(self.items[idx], self.voxel_size, self.rng, self._device(), to_host=not self.items_on_device)
 
 
-def make_loaders(args, synthetic=0, synthetic_points=3000):
+def make_loaders(args, synthetic=0, synthetic_points=3000, device_collate=False):
     """train_coloring.py:324-363.  The train loader shuffles (torch's RNG), the validation loader does not; both collate with
-    `batch_collate_fn_dset(num_matches=num_pw_samples, max_pc_size=max_pc_size)`."""
+    `batch_collate_fn_dset(num_matches=num_pw_samples, max_pc_size=max_pc_size)`.  device_collate: items stay on the device and both
+    loaders collate there (`collate.batch_collate_fn_dset_device`: the same batches), without pinning (torch refuses to pin device
+    tensors)."""
     collate_fn = partial(batch_collate_fn_dset, num_matches=args.num_pw_samples, max_pc_size=args.max_pc_size)
+    if device_collate:
+        collate_fn = partial(batch_collate_fn_dset_device, num_matches=args.num_pw_samples, max_pc_size=args.max_pc_size, device=args.device)
     if synthetic:
         n_val = max(1, synthetic // 4)
-        dset_train = SyntheticPairs(synthetic, synthetic_points, seed=args.random_seed, use_augmentations=args.use_aug, device=args.device)
-        dset_valid = SyntheticPairs(n_val, synthetic_points, seed=args.random_seed + 100003, device=args.device)
+        dset_train = SyntheticPairs(synthetic, synthetic_points, seed=args.random_seed, use_augmentations=args.use_aug, device=args.device,
+                                    items_on_device=device_collate)
+        dset_valid = SyntheticPairs(n_val, synthetic_points, seed=args.random_seed + 100003, device=args.device, items_on_device=device_collate)
     else:
         if not args.cache_data_path:
             raise ValueError("no pair cache: give --cache DIR (or `cache_data_path` in the config), or --synthetic N")
 
         def cached(split, size, aug):
-            d = CachedPairDataset(args.cache_data_path, split=split, dataset=args.dataset, use_augmentations=aug, device=args.device)
+            d = CachedPairDataset(args.cache_data_path, split=split, dataset=args.dataset, use_augmentations=aug, device=args.device,
+                                  items_on_device=device_collate)
             if size != -1:
                 d.files = d.files[:size]
             return d
         dset_train, dset_valid = cached('train', args.train_size, args.use_aug), cached('val', args.val_size, False)
-    # a worker process must not open the GPU: items made there (augmentation) force the loading into this process
-    workers = 0 if (args.use_aug or synthetic) else args.num_workers
+    # a worker process must not open the GPU: items made there (augmentation) or collated there force the loading into this process
+    workers = 0 if (args.use_aug or synthetic or device_collate) else args.num_workers
     mk = lambda d, shuffle: torch.utils.data.DataLoader(d, shuffle=shuffle, num_workers=workers, batch_size=args.batch_size,
-                                                        collate_fn=collate_fn, pin_memory=True)
+                                                        collate_fn=collate_fn, pin_memory=not device_collate)
     return mk(dset_train, True), mk(dset_valid, False)
 
 
-def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=None):
+def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=None, device_collate=False):
     """train_coloring.py:263-437 -> the run directory.  Quirks kept: every "best" file stores the validation TOTAL loss; the
     UME and point-wise "best" follow the total (eval_one_epoch returns it three times); without the registration loss the validation
-    registration loss is 0.0, so `best_reg_loss` (from inf) is written once, after the first epoch, and `best_mCHR` (from 0.0) never."""
+    registration loss is 0.0, so `best_reg_loss` (from inf) is written once, after the first epoch, and `best_mCHR` (from 0.0) never.
+    device_collate: batches are collated on the device and the training loop reads its scalars one batch late (module docstring)."""
     torch.manual_seed(args.random_seed)
     np.random.seed(args.random_seed)
     device = torch.device(args.device)
@@ -357,7 +426,7 @@ def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=
     else:
         run_name = os.path.basename(os.path.normpath(out_path))
     os.makedirs(out_path, exist_ok=True)
-    dloader_train, dloader_valid = make_loaders(args, synthetic, synthetic_points)
+    dloader_train, dloader_valid = make_loaders(args, synthetic, synthetic_points, device_collate)
     model = ResUNetSmall2(in_channels=1, out_channels=args.out_channels, trainable=True).to(device)
     point_wise_loss_fn = MyInfoNCELossNoSeg(num_samples=args.num_pw_samples, tau=args.tau, neg_euclid_dist=NEG_EUCLID_DIST)
     ctx = TrainContext(args)
@@ -370,7 +439,7 @@ def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=
             "best_inlear_ratio": 0.0, "best_mCHR": 0.0}
     for epoch in range(start_epoch, args.num_epochs):
         model.train()
-        train_one_epoch(epoch, dloader_train, model, point_wise_loss_fn, optimizer, summary_writer, ctx)
+        train_one_epoch(epoch, dloader_train, model, point_wise_loss_fn, optimizer, summary_writer, ctx, late_read=device_collate)
         model.eval()
         total, pw, ume, reg, inlear, mchr = eval_one_epoch(epoch, dloader_valid, model, point_wise_loss_fn, summary_writer, ctx)
         for name, value, better in (("best_total_loss", total, total < best["best_total_loss"]),
@@ -399,6 +468,8 @@ def main(argv=None):
     parser.add_argument('--batch-size', type=int, default=None)
     parser.add_argument('--output-path', default=None)
     parser.add_argument('--resume', default=None, help="resume_train_path of the config")
+    parser.add_argument('--device-collate', action='store_true',
+                        help="collate on the GPU and read each step's scalars one batch late (same batches, same log)")
     cli = parser.parse_args(argv)
     over = {k: v for k, v in (("cache_data_path", cli.cache), ("num_epochs", cli.epochs), ("batch_size", cli.batch_size),
                               ("output_path", cli.output_path), ("resume_train_path", cli.resume)) if v is not None}
@@ -408,7 +479,7 @@ def main(argv=None):
         args.ume_max_nn, args.ume_min_nn, args.ume_r_nn, args.ume_n_samples, args.num_pw_samples = 64, 8, 2.0, 32, 128
         args.eval_num_kpts, args.batch_size = 32, min(args.batch_size, 2)
     print(f"Train {args.dataset} config: {cli.config_path or 'built-in defaults'}")
-    out = run(args, synthetic=cli.synthetic, synthetic_points=cli.synthetic_points)
+    out = run(args, synthetic=cli.synthetic, synthetic_points=cli.synthetic_points, device_collate=cli.device_collate)
     print(f"run directory: {out}")
     return out
 
