@@ -30,6 +30,20 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert _lib.load().umereg_abi_version() == _lib.ABI_VERSION == 2
 
 
+def test_load_typed_types_a_table_once_and_names_a_missing_symbol():
+    """_lib.load_typed: what every module's load_native() goes through"""
+    from umeregrobust_amd import _lib, gt_matches
+    lib = _lib.load_typed(gt_matches.GT_MATCH_SIGNATURES)
+    assert lib is _lib.load() and lib is gt_matches.load_native()
+    assert lib.umereg_gt_matches_workspace_bytes.restype is ctypes.c_size_t
+    assert lib.umereg_gt_matches_workspace_bytes.argtypes == [ctypes.c_int] * 3
+    tables = len(_lib._typed)
+    assert _lib.load_typed(gt_matches.GT_MATCH_SIGNATURES) is lib and len(_lib._typed) == tables
+    with pytest.raises(_lib.NativeLibraryError, match="does not export umereg_no_such_entry"):
+        _lib.load_typed({"umereg_no_such_entry": (ctypes.c_int, [])})
+    assert len(_lib._typed) == tables
+
+
 def test_no_cpu_fallback_without_device():
     import torch
     from umeregrobust_amd import _lib, ops

@@ -155,16 +155,27 @@ def opts_ptr(opts):
 
 
 _lib = None
+_typed = []     # the signature tables typed on _lib so far (the tables themselves: they are module constants)
 
 
 class NativeLibraryError(RuntimeError):
     pass
 
 
+def _set_types(lib, signatures):
+    for name, (res, args) in signatures.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise NativeLibraryError(f"{LIB_PATH} does not export {name}") from e
+        fn.restype = res
+        fn.argtypes = args
+
+
 def load():
     """Load (once) and type every symbol.  Raises NativeLibraryError when the .so is absent:
     build it with `python -c "import __graft_entry__ as g; g.build()"`."""
-    global _lib
+    global _lib, _typed
     if _lib is not None:
         return _lib
     if not os.path.exists(LIB_PATH):
@@ -172,16 +183,20 @@ def load():
             f"{LIB_PATH} not found: the HIP extension has not been built "
             "(run __graft_entry__.build()); umeregrobust_amd has no CPU fallback")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise NativeLibraryError(f"{LIB_PATH} does not export {name}") from e
-        fn.restype = res
-        fn.argtypes = args
+    _set_types(lib, SIGNATURES)
     if lib.umereg_abi_version() != ABI_VERSION:
         raise NativeLibraryError(f"ABI version mismatch: {lib.umereg_abi_version()} != {ABI_VERSION}")
-    _lib = lib
+    _lib, _typed = lib, [SIGNATURES]
+    return lib
+
+
+def load_typed(signatures):
+    """load(), with the entry points of one more header typed: `signatures` is a table like SIGNATURES, typed once per
+    loaded library.  Raises NativeLibraryError when the library is absent or lacks one of the symbols."""
+    lib = load()
+    if not any(t is signatures for t in _typed):
+        _set_types(lib, signatures)
+        _typed.append(signatures)
     return lib
 
 

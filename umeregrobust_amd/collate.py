@@ -32,22 +32,10 @@ COLLATE_SIGNATURES = {
 # the dtypes the kernel gathers; a field of another dtype (a cache written elsewhere) is gathered with torch indexing instead
 KERNEL_DTYPES = {"pts": torch.float32, "seg": torch.int64, "coords": torch.int32}
 
-_typed = None
-
 
 def load_native():
     """libumereg.so with the entry points of include/umereg_collate.h typed (raises without the built library)."""
-    global _typed
-    lib = _lib.load()
-    if _typed is not lib:
-        for name, (res, args) in COLLATE_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise _lib.NativeLibraryError(f"{_lib.LIB_PATH} does not export {name}") from e
-            fn.restype, fn.argtypes = res, args
-        _typed = lib
-    return lib
+    return _lib.load_typed(COLLATE_SIGNATURES)
 
 
 def workspace_bytes(ns, nt, n_matches):

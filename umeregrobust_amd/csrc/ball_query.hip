@@ -81,11 +81,7 @@ UMEREG_API int umereg_ball_query_ex_f32(const float* p1, const float* p2, const 
     UMEREG_REQUIRE(radius > 0.f, "ball_query: radius must be positive");
     UMEREG_REQUIRE((flags & ~UMEREG_BALL_FMA) == 0, "ball_query: unknown flags 0x%x", flags);
     if (int rc = check_device()) return rc;
-    if (!workspace || workspace_bytes < umereg_ball_query_workspace_bytes(B, n2) || ((uintptr_t)workspace & 15)) {
-        set_error("ball_query: workspace too small or misaligned (%zu < %zu)", workspace_bytes,
-                  umereg_ball_query_workspace_bytes(B, n2));
-        return UMEREG_EWORKSPACE;
-    }
+    UMEREG_REQUIRE_WORKSPACE("ball_query", workspace, workspace_bytes, umereg_ball_query_workspace_bytes(B, n2));
     hipStream_t st = (hipStream_t)stream;
     if (int rc = launch_prep(p2, (char*)workspace, B, n2, radius, st)) return rc;
     int cap, waves;

@@ -8,13 +8,13 @@
 //            contiguous over the lanes); coordinates come out as {b, x, y, z}
 //   first    first_row[s] = min row index over the rows of `matches` that name source s            (integer atomicMin)
 //   lowest   rows that ARE their source's first row and whose source survived: first_src[t] = min s  (integer atomicMin)
-//   compact  targets with a candidate that survived themselves, in ascending target index: per-block counts, a scan, a scatter
+//   compact  targets with a candidate that survived themselves, in ascending target index (compact.h)
 //
 // The two minima do not depend on the order in which the atomics land; the row order comes from the scan.  This is launch-bound,
 // bandwidth-trivial work (a few hundred KB per element): seven short launches per element and no more machinery than that.
 #include <limits.h>
 
-#include "common.h"
+#include "compact.h"
 #include "umereg_collate.h"
 
 namespace umereg {
@@ -121,52 +121,32 @@ __global__ __launch_bounds__(kCollateBlock) void collate_first_src_kernel(const 
     if (first_row[s] == (int)r && pos_src[s] >= 0) atomicMin(&first_src[t], (int)s);
 }
 
-// pass 0: surviving targets per block of kCollateCompactBlock; pass 1: their rows at the block's offset
+// compact.h's count (PASS 0) and scatter (PASS 1) over the targets that kept a candidate and survived themselves
 template <int PASS>
 __global__ __launch_bounds__(kCollateCompactBlock) void collate_compact_kernel(const int* __restrict__ first_src,
                                                                                 const int* __restrict__ pos_src,
                                                                                 const int* __restrict__ pos_tgt, int nt,
                                                                                 int* __restrict__ bcnt, int64_t* __restrict__ out_rows)
 {
-    __shared__ int wave_cnt[kCollateCompactBlock / 64];
     const int64_t t = (int64_t)blockIdx.x * kCollateCompactBlock + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int s = INT_MAX, pt = -1;
     if (t < nt) { s = first_src[t]; pt = pos_tgt[t]; }
     const bool keep = s != INT_MAX && pt >= 0;
-    const unsigned long long bal = __ballot(keep);
-    if (lane == 0) wave_cnt[wave] = __popcll(bal);
-    __syncthreads();
-    int before = 0, total = 0;
-    for (int k = 0; k < kCollateCompactBlock / 64; ++k) { const int c = wave_cnt[k]; before += k < wave ? c : 0; total += c; }
+    const BlockRank k = block_rank<kCollateCompactBlock>(keep);
     if (PASS == 0) {
-        if (threadIdx.x == 0) bcnt[blockIdx.x] = total;
+        if (threadIdx.x == 0) bcnt[blockIdx.x] = k.total;
     } else if (keep) {
-        const size_t r = (size_t)(bcnt[blockIdx.x] + before + mbcnt(bal));
+        const size_t r = (size_t)(bcnt[blockIdx.x] + k.before);
         out_rows[2 * r] = (int64_t)pos_src[s];
         out_rows[2 * r + 1] = (int64_t)pt;
     }
 }
 
-// exclusive scan of the block counts (in place), total -> out_count[0]
+// block counts -> block offsets (in place), number of rows -> out_count[0]
 __global__ __launch_bounds__(1024) void collate_scan_kernel(int n_blocks, int* __restrict__ bcnt, int* __restrict__ out_count)
 {
-    __shared__ int part[1024];
-    const int per = (n_blocks + 1023) / 1024;
-    const int a = min((int)threadIdx.x * per, n_blocks), b = min(a + per, n_blocks);
-    int s = 0;
-    for (int k = a; k < b; ++k) s += bcnt[k];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int v = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int run = part[threadIdx.x] - s;
-    for (int k = a; k < b; ++k) { const int t = bcnt[k]; bcnt[k] = run; run += t; }
-    if (threadIdx.x == 1023) out_count[0] = part[1023];
+    const int total = scan_counts<1024>(bcnt, bcnt, nullptr, n_blocks);
+    if (threadIdx.x == 1023) out_count[0] = total;
 }
 
 static bool collate_sizes_ok(int64_t ns, int64_t nt, int64_t m)
@@ -206,10 +186,7 @@ UMEREG_API int umereg_collate_element(const float* src_pts, const int64_t* src_s
                    "%s: a field needs both its input and its output pointer, or neither", who);
     if (int rc = check_device()) return rc;
     const CollateWs w = collate_ws((int)ns, (int)nt);
-    if (!workspace || workspace_bytes < w.total || ((uintptr_t)workspace & 15)) {
-        set_error("%s: workspace too small or misaligned (%zu < %zu)", who, workspace_bytes, w.total);
-        return UMEREG_EWORKSPACE;
-    }
+    UMEREG_REQUIRE_WORKSPACE(who, workspace, workspace_bytes, w.total);
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     int* pos_src = reinterpret_cast<int*>(ws + w.off_pos_src);

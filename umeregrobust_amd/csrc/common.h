@@ -24,6 +24,16 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
         }                                         \
     } while (0)
 
+// the caller's workspace: there, at least `need` bytes (evaluated once) and 16-byte aligned, or the entry returns UMEREG_EWORKSPACE
+#define UMEREG_REQUIRE_WORKSPACE(who, ptr, bytes, need)                                                                   \
+    do {                                                                                                                  \
+        const size_t need__ = (need);                                                                                     \
+        if (!(ptr) || (bytes) < need__ || ((uintptr_t)(ptr) & 15)) {                                                      \
+            ::umereg::set_error("%s: workspace too small or misaligned (%zu < %zu)", who, (size_t)(bytes), need__);       \
+            return UMEREG_EWORKSPACE;                                                                                     \
+        }                                                                                                                 \
+    } while (0)
+
 #define UMEREG_CHECK_LAUNCH(what)                                                        \
     do {                                                                                 \
         hipError_t e__ = hipGetLastError();                                              \

@@ -377,10 +377,7 @@ UMEREG_API int umereg_corr_scores_ex_f32(const float* src_pts, const float* tgt_
     UMEREG_REQUIRE(((uintptr_t)src_wfeat & 15) == 0 && ((uintptr_t)tgt_wfeat & 15) == 0, "corr_scores: features must be 16-byte aligned");
     if (int rc = check_device()) return rc;
     const CorrWs ws = corr_ws(Ns, Nt, M, flags);
-    if (!workspace || workspace_bytes < ws.total || ((uintptr_t)workspace & 15)) {
-        set_error("corr_scores: workspace too small or misaligned (%zu < %zu)", workspace_bytes, ws.total);
-        return UMEREG_EWORKSPACE;
-    }
+    UMEREG_REQUIRE_WORKSPACE("corr_scores", workspace, workspace_bytes, ws.total);
     CorrCtx c = {};
     c.src_pts = src_pts; c.tgt_pts = tgt_pts; c.vp4 = (const float4*)src_wfeat; c.vq4 = (const float4*)tgt_wfeat; c.T = T;
     c.Ns = Ns; c.Nt = Nt; c.M = M; c.K = K; c.flags = flags; c.sigma = sigma; c.scores = scores; c.st = (hipStream_t)stream; c.ws = ws;

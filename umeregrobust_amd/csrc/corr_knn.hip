@@ -315,10 +315,7 @@ UMEREG_API int umereg_knn_points_f32(const float* p1, const float* p2, int B, in
     UMEREG_REQUIRE(B > 0 && n1 > 0 && n2 > 0, "knn_points: B, n1, n2 must be positive (got %d, %d, %d)", B, n1, n2);
     UMEREG_REQUIRE(K > 0 && K <= 64 && K <= n2, "knn_points: K must be in [1, min(64, n2)] (got K=%d, n2=%d)", K, n2);
     if (int rc = check_device()) return rc;
-    if (!workspace || workspace_bytes < umereg_knn_workspace_bytes(B, n2) || ((uintptr_t)workspace & 15)) {
-        set_error("knn_points: workspace too small or misaligned (%zu < %zu)", workspace_bytes, umereg_knn_workspace_bytes(B, n2));
-        return UMEREG_EWORKSPACE;
-    }
+    UMEREG_REQUIRE_WORKSPACE("knn_points", workspace, workspace_bytes, umereg_knn_workspace_bytes(B, n2));
     hipStream_t st = (hipStream_t)stream;
     if (int rc = launch_prep(p2, (char*)workspace, B, n2, -(float)K, st)) return rc;
     if (K == 1) {
@@ -365,10 +362,7 @@ UMEREG_API int umereg_nn1_pair_f32(const float* q_src, const float* q_tgt, const
                    nq_src, nq_tgt, n_src, n_tgt);
     if (int rc = check_device()) return rc;
     const size_t need = umereg_nn1_pair_workspace_bytes(n_src, n_tgt);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)) {
-        set_error("nn1_pair: workspace too small or misaligned (%zu < %zu)", workspace_bytes, need);
-        return UMEREG_EWORKSPACE;
-    }
+    UMEREG_REQUIRE_WORKSPACE("nn1_pair", workspace, workspace_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     const int N = n_src > n_tgt ? n_src : n_tgt, nq = nq_src > nq_tgt ? nq_src : nq_tgt;
     PairDesc* dp = (PairDesc*)((char*)workspace + need - 256);
@@ -393,10 +387,7 @@ UMEREG_API int umereg_feature_spatial_var_f32(const float* pts, const float* fea
     UMEREG_REQUIRE(knn > 1 && knn <= 64 && knn <= N, "feature_spatial_var: knn must be in [2, min(64, N)] (got %d)", knn);
     UMEREG_REQUIRE(((uintptr_t)feat & 15) == 0, "feature_spatial_var: feat must be 16-byte aligned");
     if (int rc = check_device()) return rc;
-    if (!workspace || workspace_bytes < umereg_knn_workspace_bytes(B, N) || ((uintptr_t)workspace & 15)) {
-        set_error("feature_spatial_var: workspace too small or misaligned");
-        return UMEREG_EWORKSPACE;
-    }
+    UMEREG_REQUIRE_WORKSPACE("feature_spatial_var", workspace, workspace_bytes, umereg_knn_workspace_bytes(B, N));
     hipStream_t st = (hipStream_t)stream;
     // small clouds go one wavefront per query through coop_knn, which never walks the grid: the table is then sorted along the
     // Hilbert curve, so that its 64-point chunks -- what that search prunes with -- are compact blobs instead of 40 m strips

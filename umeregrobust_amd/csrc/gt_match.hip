@@ -12,12 +12,13 @@
 //            x-cells of a (z, y) row are ONE contiguous run of the sorted table, read 8 points (128 B) at a time; fp64
 //            distance, lower index on a tie; three xor steps reduce the 8 lanes; the winner is kept iff d2 < r * r
 //   mutual   (mutual form) drop i unless the reverse search maps its j* back to i
-//   compact  rows (i, j*) in ascending i: per-block counts, a scan, a scatter -- no atomics, hence one order
+//   compact  rows (i, j*) in ascending i (compact.h)
 //
 // Work per query is the points of the cells its radius reaches, wherever the query lies; a query whose range misses the grid
 // reads nothing.  fp64 use is 8 VALU operations per candidate on a gather-bound loop.
 #include <float.h>
 
+#include "compact.h"
 #include "grid.h"
 #include "umereg_gt_matches.h"
 
@@ -162,48 +163,28 @@ __global__ __launch_bounds__(256) void gt_mutual_kernel(int* __restrict__ nn_st,
     if (j >= 0 && nn_ts[j] != i) nn_st[i] = -1;
 }
 
-// pass 0: matched queries per block of kGtCompactBlock; pass 1: their rows at the block's offset
+// compact.h's count (PASS 0) and scatter (PASS 1) over the matched queries: rows (i, nn[i])
 template <int PASS>
 __global__ __launch_bounds__(kGtCompactBlock) void gt_compact_kernel(const int* __restrict__ nn, int n, int* __restrict__ bcnt,
                                                                      int64_t* __restrict__ out_rows)
 {
-    __shared__ int wave_cnt[kGtCompactBlock / 64];
     const int i = blockIdx.x * kGtCompactBlock + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = i < n ? nn[i] : -1;
-    const unsigned long long b = __ballot(j >= 0);
-    if (lane == 0) wave_cnt[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0, total = 0;
-    for (int k = 0; k < kGtCompactBlock / 64; ++k) { const int c = wave_cnt[k]; before += k < wave ? c : 0; total += c; }
+    const BlockRank k = block_rank<kGtCompactBlock>(j >= 0);
     if (PASS == 0) {
-        if (threadIdx.x == 0) bcnt[blockIdx.x] = total;
+        if (threadIdx.x == 0) bcnt[blockIdx.x] = k.total;
     } else if (j >= 0) {
-        const size_t r = (size_t)(bcnt[blockIdx.x] + before + mbcnt(b));
+        const size_t r = (size_t)(bcnt[blockIdx.x] + k.before);
         out_rows[2 * r] = (int64_t)i;
         out_rows[2 * r + 1] = (int64_t)j;
     }
 }
 
-// exclusive scan of the block counts (in place), total -> out_count[0]
+// block counts -> block offsets (in place), number of rows -> out_count[0]
 __global__ __launch_bounds__(1024) void gt_scan_kernel(int n_blocks, int* __restrict__ bcnt, int* __restrict__ out_count)
 {
-    __shared__ int part[1024];
-    const int per = (n_blocks + 1023) / 1024;
-    const int a = min((int)threadIdx.x * per, n_blocks), b = min(a + per, n_blocks);
-    int s = 0;
-    for (int k = a; k < b; ++k) s += bcnt[k];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int v = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int run = part[threadIdx.x] - s;
-    for (int k = a; k < b; ++k) { const int t = bcnt[k]; bcnt[k] = run; run += t; }
-    if (threadIdx.x == 1023) out_count[0] = part[1023];
+    const int total = scan_counts<1024>(bcnt, bcnt, nullptr, n_blocks);
+    if (threadIdx.x == 1023) out_count[0] = total;
 }
 
 // nn[i] of n_q queries against n_t targets, into the side's slice of the workspace
@@ -243,10 +224,7 @@ static int gt_matches(const char* who, const float* src, int n_src, const float*
     UMEREG_REQUIRE(radius > 0.0 && radius <= DBL_MAX, "%s: the radius must be positive and finite", who);
     if (int rc = check_device()) return rc;
     const GtWs w = gt_ws(n_src, n_tgt, mutual);
-    if (!workspace || workspace_bytes < w.total || ((uintptr_t)workspace & 15)) {
-        set_error("%s: workspace too small or misaligned (%zu < %zu)", who, workspace_bytes, w.total);
-        return UMEREG_EWORKSPACE;
-    }
+    UMEREG_REQUIRE_WORKSPACE(who, workspace, workspace_bytes, w.total);
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     if (int rc = launch_zero(out_count, 8, 1, 8, st)) return rc;

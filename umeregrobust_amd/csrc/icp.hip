@@ -283,10 +283,7 @@ static int icp_enqueue(const float* src, const float* tgt, int n_src, int n_tgt,
     UMEREG_REQUIRE(max_correspondence_distance > 0.f && max_iteration >= 0 && iterations >= 0, "icp_point_to_point: bad distance / iteration limit");
     if (int rc = check_device()) return rc;
     const size_t need = umereg_icp_workspace_bytes(n_src, n_tgt);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)) {
-        set_error("icp_point_to_point: workspace too small or misaligned (%zu < %zu)", workspace_bytes, need);
-        return UMEREG_EWORKSPACE;
-    }
+    UMEREG_REQUIRE_WORKSPACE("icp_point_to_point", workspace, workspace_bytes, need);
     char* ws = (char*)workspace;
     const GridWs w = grid_ws(n_tgt);
     IcpState* state = (IcpState*)(ws + w.total);

@@ -114,10 +114,7 @@ static int dist_common(const float* ume1, const float* ume2, int B, int n1, int 
     UMEREG_REQUIRE((!order1 && !order2) || (order1 && order2 && refine && B == 1), "%s: a slot order needs both sets, f16r and B = 1", who);
     UMEREG_REQUIRE(((uintptr_t)ume1 & 15) == 0 && ((uintptr_t)ume2 & 15) == 0, "%s: UME pointers must be 16-byte aligned", who);
     if (int rc = check_device()) return rc;
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)) {
-        set_error("%s: workspace too small or misaligned (%zu < %zu)", who, workspace_bytes, need);
-        return UMEREG_EWORKSPACE;
-    }
+    UMEREG_REQUIRE_WORKSPACE(who, workspace, workspace_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     float* QA = (float*)workspace;
     float* QB = (float*)((char*)workspace + qa_bytes(n1));

@@ -66,10 +66,7 @@ static int pair_match_chain(const float* pts, const float* feat, const int64_t* 
     UMEREG_REQUIRE(((uintptr_t)F & 15) == 0 && (ragged || ((uintptr_t)feat & 15) == 0), "%s: feat and F must be 16-byte aligned", who);
     if (int rc = check_device()) return rc;
     const size_t need = umereg_pair_match_workspace_bytes_ex(N, n_kp, opts);
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)) {
-        set_error("%s: workspace too small or misaligned (%zu < %zu)", who, workspace_bytes, need);
-        return UMEREG_EWORKSPACE;
-    }
+    UMEREG_REQUIRE_WORKSPACE(who, workspace, workspace_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     char* ws_mom = (char*)workspace;
     const size_t mom_bytes = align_up(umereg_ume_moments_workspace_bytes(2, N), 256);

@@ -3,15 +3,14 @@
 // :407-413; datasets/nuscenes/nuscenes_dataset.py:403-421), and the compaction of what is left, in scan order.
 //
 //   count    one thread per scan row (an aligned 16-byte row is read as a vector, of which the compiler keeps the dwords in use: x, y
-//            here, x, y, z in the scatter; a 12-byte or unaligned row is scalar loads): keep / error predicate, wave ballots,
-//            per-block keep count and error bits -> workspace
-//   scan     one block: exclusive scan of the block counts (in place), total and the OR of the error bits -> out_count
-//   scatter  the same predicate again, row written at block offset + waves before + lanes before (ballot / mbcnt)
+//            here, x, y, z in the scatter; a 12-byte or unaligned row is scalar loads): keep / error predicate, per-block keep count
+//            and error bits -> workspace
+//   scan     one block: the block counts -> block offsets, total and the OR of the error bits -> out_count
+//   scatter  the same predicate again, the row written at its rank
 //
-// The compaction is collate.hip's: order comes from the scan, never from atomics, and every workspace word the scan reads was
-// written by the count pass of the same call.  Launch-bound, bandwidth-trivial work (2 MB per KITTI scan, read twice): three short
-// launches and no more machinery than that.
-#include "common.h"
+// The compaction is compact.h's; every workspace word the scan reads was written by the count pass of the same call.  Launch-bound,
+// bandwidth-trivial work (2 MB per KITTI scan, read twice): three short launches and no more machinery than that.
+#include "compact.h"
 #include "umereg_scan_prep.h"
 
 namespace umereg {
@@ -45,17 +44,15 @@ struct ScanPrepArgs {
     float ego_hx, ego_hy;      // both > 0, or both 0 (filter off)
 };
 
-// PASS 0: keep count and error bits of the block -> bcnt / berr.  PASS 1: the kept rows at the block's offset.
+// compact.h's count (PASS 0: also the block's error bits -> berr) and scatter (PASS 1) over the rows that stay.
 // VEC4: rows of 4 floats at a 16-byte aligned base, read as one vector.
 template <int PASS, bool VEC4>
 __global__ __launch_bounds__(kScanPrepBlock) void scan_prep_kernel(ScanPrepArgs a, int* __restrict__ bcnt, int* __restrict__ berr,
                                                                     float* __restrict__ out_pts, int64_t* __restrict__ out_seg,
                                                                     int64_t* __restrict__ out_index)
 {
-    __shared__ int wave_cnt[kScanPrepBlock / 64];
     __shared__ int wave_err[kScanPrepBlock / 64];
     const int64_t i = (int64_t)blockIdx.x * kScanPrepBlock + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     bool keep = false;
     int err = 0;
     float x = 0.f, y = 0.f, z = 0.f;
@@ -84,60 +81,37 @@ __global__ __launch_bounds__(kScanPrepBlock) void scan_prep_kernel(ScanPrepArgs 
         const bool ego = a.ego_hx > 0.f && fabsf(x) <= a.ego_hx && fabsf(y) <= a.ego_hy;      // (false for a NaN coordinate)
         keep = !ego && (seg != 0 || (a.flags & UMEREG_SCAN_KEEP_UNLABELED));
     }
-    const unsigned long long bal = __ballot(keep);
     if (PASS == 0) {
         const unsigned long long e1 = __ballot(err & 1), e2 = __ballot(err & 2);
-        if (lane == 0) {
-            wave_cnt[wave] = __popcll(bal);
-            wave_err[wave] = (e1 ? 1 : 0) | (e2 ? 2 : 0);
-        }
-        __syncthreads();
+        if (lane_id() == 0) wave_err[threadIdx.x >> 6] = (e1 ? 1 : 0) | (e2 ? 2 : 0);      // (read behind block_rank's barrier)
+    }
+    const BlockRank k = block_rank<kScanPrepBlock>(keep);
+    if (PASS == 0) {
         if (threadIdx.x == 0) {
-            int total = 0, e = 0;
-            for (int k = 0; k < kScanPrepBlock / 64; ++k) { total += wave_cnt[k]; e |= wave_err[k]; }
-            bcnt[blockIdx.x] = total;
+            int e = 0;
+            for (int v = 0; v < kScanPrepBlock / 64; ++v) e |= wave_err[v];
+            bcnt[blockIdx.x] = k.total;
             berr[blockIdx.x] = e;
         }
-    } else {
-        if (lane == 0) wave_cnt[wave] = __popcll(bal);
-        __syncthreads();
-        if (keep) {
-            int before = 0;
-            for (int k = 0; k < wave; ++k) before += wave_cnt[k];
-            const size_t r = (size_t)(bcnt[blockIdx.x] + before + mbcnt(bal));       // r <= i < n: inside the outputs
-            out_pts[3 * r] = x; out_pts[3 * r + 1] = y; out_pts[3 * r + 2] = z;
-            out_seg[r] = seg;
-            if (out_index) out_index[r] = i;
-        }
+    } else if (keep) {
+        const size_t r = (size_t)(bcnt[blockIdx.x] + k.before);       // r <= i < n: inside the outputs
+        out_pts[3 * r] = x; out_pts[3 * r + 1] = y; out_pts[3 * r + 2] = z;
+        out_seg[r] = seg;
+        if (out_index) out_index[r] = i;
     }
 }
 
-// exclusive scan of the block counts (in place), total -> out_count[0], OR of the blocks' error bits -> out_count[1]
+// block counts -> block offsets (in place), number of kept rows -> out_count[0], OR of the blocks' error bits -> out_count[1]
 __global__ __launch_bounds__(kScanPrepScanBlock) void scan_prep_scan_kernel(int n_blocks, int* __restrict__ bcnt,
                                                                              const int* __restrict__ berr, int* __restrict__ out_count)
 {
-    __shared__ int part[kScanPrepScanBlock];
-    __shared__ int err_bits[kScanPrepScanBlock];
-    const int per = (n_blocks + kScanPrepScanBlock - 1) / kScanPrepScanBlock;
-    const int a = min((int)threadIdx.x * per, n_blocks), b = min(a + per, n_blocks);
-    int s = 0, e = 0;
-    for (int k = a; k < b; ++k) { s += bcnt[k]; e |= berr[k]; }
-    part[threadIdx.x] = s;
-    err_bits[threadIdx.x] = e;
-    __syncthreads();
-    for (int off = 1; off < kScanPrepScanBlock; off <<= 1) {
-        const bool has = (int)threadIdx.x >= off;
-        const int v = has ? part[threadIdx.x - off] : 0, w = has ? err_bits[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        err_bits[threadIdx.x] |= w;
-        __syncthreads();
-    }
-    int run = part[threadIdx.x] - s;
-    for (int k = a; k < b; ++k) { const int t = bcnt[k]; bcnt[k] = run; run += t; }
+    int e = 0;
+    for (int k = threadIdx.x; k < n_blocks; k += kScanPrepScanBlock) e |= berr[k];
+    const int total = scan_counts<kScanPrepScanBlock>(bcnt, bcnt, nullptr, n_blocks);
+    const int e1 = __syncthreads_or(e & 1), e2 = __syncthreads_or(e & 2);
     if (threadIdx.x == kScanPrepScanBlock - 1) {
-        out_count[0] = part[kScanPrepScanBlock - 1];
-        out_count[1] = err_bits[kScanPrepScanBlock - 1];
+        out_count[0] = total;
+        out_count[1] = (e1 ? 1 : 0) | (e2 ? 2 : 0);
     }
 }
 
@@ -166,10 +140,7 @@ UMEREG_API int umereg_scan_prep_f32(const float* scan, int64_t n, int stride, co
                    "%s: a pointer is not aligned to its element type", who);
     if (int rc = check_device()) return rc;
     const ScanPrepWs w = scan_prep_ws(n);
-    if (!workspace || workspace_bytes < w.total || ((uintptr_t)workspace & 15)) {
-        set_error("%s: workspace too small or misaligned (%zu < %zu)", who, workspace_bytes, w.total);
-        return UMEREG_EWORKSPACE;
-    }
+    UMEREG_REQUIRE_WORKSPACE(who, workspace, workspace_bytes, w.total);
     hipStream_t st = (hipStream_t)stream;
     int* bcnt = reinterpret_cast<int*>((char*)workspace + w.off_bcnt);
     int* berr = reinterpret_cast<int*>((char*)workspace + w.off_berr);

@@ -7,6 +7,7 @@
 // occurrence), stable: inside a cell by input index -- a cell holds at most 512 points of a cloud, so a point's rank is
 // counted directly among its cell's points.  Deterministic throughout: every later level takes the FIRST row (in the order
 // of the level below) that falls into a cell as the cell's representative, compacted by a scan.
+#include "compact.h"
 #include "sparse.h"
 
 namespace umereg {
@@ -105,60 +106,30 @@ __global__ __launch_bounds__(kB) void fn_flag_kernel(char* __restrict__ ws, FnWs
     reinterpret_cast<int*>(ws + w.off_flag)[r] = fn_mins(ws, w, t)[s] == (unsigned int)r;
 }
 
-// compaction of the flags, pass 0: flagged rows per block of kFnScanBlock; pass 1: newid[r] = rank of a flagged row
+// compaction of the flags (compact.h), pass 0: flagged rows per block of kFnScanBlock; pass 1: newid[r] = rank of a flagged row
 template <int PASS>
 __global__ __launch_bounds__(kFnScanBlock) void fn_compact_kernel(char* __restrict__ ws, FnWs w, const int32_t* __restrict__ n_ptr)
 {
-    __shared__ int wave_cnt[kFnScanBlock / 64];
     const int n = *n_ptr;
-    if ((int)blockIdx.x * kFnScanBlock >= n) return;
+    if ((int)blockIdx.x * kFnScanBlock >= n) return;      // (whole blocks: uniform, in front of block_rank)
     const int* flag = reinterpret_cast<const int*>(ws + w.off_flag);
     int* bcnt = reinterpret_cast<int*>(ws + w.off_bcnt);
     const int r = blockIdx.x * kFnScanBlock + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const bool f = r < n && flag[r];
-    const unsigned long long b = __ballot(f);
-    if (lane == 0) wave_cnt[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0, total = 0;
-    for (int k = 0; k < kFnScanBlock / 64; ++k) {
-        const int c = wave_cnt[k];
-        before += k < wave ? c : 0;
-        total += c;
-    }
+    const BlockRank k = block_rank<kFnScanBlock>(f);
     if (PASS == 0) {
-        if (threadIdx.x == 0) bcnt[blockIdx.x] = total;
+        if (threadIdx.x == 0) bcnt[blockIdx.x] = k.total;
     } else if (r < n) {
-        reinterpret_cast<int*>(ws + w.off_newid)[r] = f ? bcnt[blockIdx.x] + before + mbcnt(b) : -1;
+        reinterpret_cast<int*>(ws + w.off_newid)[r] = f ? bcnt[blockIdx.x] + k.before : -1;
     }
 }
 
-// exclusive scan (one workgroup) of in[0 .. ceil(*n_ptr / div)) -> out (and out2), sum -> *total
+// exclusive scan (one workgroup) of in[0 .. ceil(*n_ptr / div)) -> out (and out2), sum -> *total; in and out may be one array
 __global__ __launch_bounds__(1024) void fn_scan_kernel(const int* in, int* out, int* __restrict__ out2, const int32_t* __restrict__ n_ptr,
                                                        int div, int32_t* __restrict__ total)
 {
-    __shared__ int part[1024];
-    const int n = (*n_ptr + div - 1) / div;
-    const int per = (n + 1023) / 1024;
-    const int a = threadIdx.x * per, b = min(a + per, n);
-    int s = 0;
-    for (int k = a; k < b; ++k) s += in[k];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int v = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int run = part[threadIdx.x] - s;
-    for (int k = a; k < b; ++k) {
-        const int t = in[k];
-        out[k] = run;
-        if (out2) out2[k] = run;
-        run += t;
-    }
-    if (threadIdx.x == 1023 && total) *total = part[1023];
+    const int sum = scan_counts<1024>(in, out, out2, (*n_ptr + div - 1) / div);
+    if (threadIdx.x == 1023 && total) *total = sum;
 }
 
 // cell ids of the representatives -> the table's row array

@@ -5,9 +5,9 @@
 //
 // No sort: a voxel's first point is the minimum index over its points, which an open-addressing hash table over the
 // 63-bit voxel key finds with one atomicMin per point (order independent, hence deterministic); the representatives are
-// the points whose own index is their voxel's minimum, compacted in index order by a block count -> scan -> scatter.
+// the points whose own index is their voxel's minimum, compacted in index order (compact.h).
 // 4 small kernels + 1 memset instead of ~15 torch launches with two device sorts (evaluate.py's loop: 0.30 -> 0.03 ms).
-#include "common.h"
+#include "compact.h"
 
 namespace umereg {
 
@@ -74,55 +74,35 @@ __global__ __launch_bounds__(256) void voxel_insert_kernel(const float* __restri
     slot_of[i] = s;
 }
 
-// pass 0: number of representatives per block of kVoxBlock points; pass 1: their indices at the block's offset
+// compact.h's count (PASS 0) and scatter (PASS 1) over the representatives: the points that are their voxel's minimum
 template <int PASS>
 __global__ __launch_bounds__(kVoxBlock) void voxel_compact_kernel(int n, char* __restrict__ ws, int64_t* __restrict__ out_idx)
 {
-    __shared__ int wave_cnt[kVoxBlock / 64];
     const VoxWs w = vox_ws(n);
     const unsigned int* mins = reinterpret_cast<const unsigned int*>(ws + w.off_min);
     const unsigned int* slot_of = reinterpret_cast<const unsigned int*>(ws + w.off_slot);
     int* bcnt = reinterpret_cast<int*>(ws + w.off_bcnt);
     const int i = blockIdx.x * kVoxBlock + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     bool rep = false;
     if (i < n) {
         const unsigned int s = slot_of[i];
         rep = s != 0xffffffffu && mins[s] == (unsigned int)i;
     }
-    const unsigned long long b = __ballot(rep);
-    if (lane == 0) wave_cnt[wave] = __popcll(b);
-    __syncthreads();
-    int before = 0, total = 0;
-    for (int k = 0; k < kVoxBlock / 64; ++k) { const int c = wave_cnt[k]; before += k < wave ? c : 0; total += c; }
+    const BlockRank r = block_rank<kVoxBlock>(rep);
     if (PASS == 0) {
-        if (threadIdx.x == 0) bcnt[blockIdx.x] = total;
+        if (threadIdx.x == 0) bcnt[blockIdx.x] = r.total;
     } else if (rep) {
-        out_idx[bcnt[blockIdx.x] + before + __popcll(b & ((1ull << lane) - 1ull))] = (int64_t)i;
+        out_idx[bcnt[blockIdx.x] + r.before] = (int64_t)i;
     }
 }
 
-// exclusive scan of the block counts (in place), total -> out_count[0]
+// block counts -> block offsets (in place), number of representatives -> out_count[0]
 __global__ __launch_bounds__(1024) void voxel_scan_kernel(int n, char* __restrict__ ws, int* __restrict__ out_count)
 {
-    __shared__ int part[1024];
     const VoxWs w = vox_ws(n);
     int* bcnt = reinterpret_cast<int*>(ws + w.off_bcnt);
-    const int per = (w.n_blocks + 1023) / 1024;
-    const int a = threadIdx.x * per, b = min(a + per, w.n_blocks);
-    int s = 0;
-    for (int k = a; k < b; ++k) s += bcnt[k];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int v = (int)threadIdx.x >= off ? part[threadIdx.x - off] : 0;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int run = part[threadIdx.x] - s;
-    for (int k = a; k < b; ++k) { const int t = bcnt[k]; bcnt[k] = run; run += t; }
-    if (threadIdx.x == 1023) out_count[0] = part[1023];
+    const int total = scan_counts<1024>(bcnt, bcnt, nullptr, w.n_blocks);
+    if (threadIdx.x == 1023) out_count[0] = total;
 }
 
 }  // namespace umereg
@@ -142,10 +122,7 @@ UMEREG_API int umereg_voxel_first_index_f32(const float* pts, int n, float voxel
     UMEREG_REQUIRE(voxel > 0.f, "voxel_first_index: the voxel edge must be positive");
     if (int rc = check_device()) return rc;
     const VoxWs w = vox_ws(n);
-    if (!workspace || workspace_bytes < w.total || ((uintptr_t)workspace & 15)) {
-        set_error("voxel_first_index: workspace too small or misaligned (%zu < %zu)", workspace_bytes, w.total);
-        return UMEREG_EWORKSPACE;
-    }
+    UMEREG_REQUIRE_WORKSPACE("voxel_first_index", workspace, workspace_bytes, w.total);
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     // keys = all ones (empty), minima = all ones (> every index): one memset over both regions

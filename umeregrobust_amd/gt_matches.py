@@ -27,22 +27,10 @@ GT_MATCH_SIGNATURES = {
 
 MAX_COORD = 1048576.0       # UMEREG_GT_MATCHES_MAX_COORD
 
-_typed = None
-
 
 def load_native():
     """libumereg.so with the entry points of include/umereg_gt_matches.h typed (raises without the built library)."""
-    global _typed
-    lib = _lib.load()
-    if _typed is not lib:
-        for name, (res, args) in GT_MATCH_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise _lib.NativeLibraryError(f"{_lib.LIB_PATH} does not export {name}") from e
-            fn.restype, fn.argtypes = res, args
-        _typed = lib
-    return lib
+    return _lib.load_typed(GT_MATCH_SIGNATURES)
 
 
 def _stream(dev):

@@ -74,22 +74,10 @@ LAYERS = (
     ("conv1_tr", "norm1_tr"), ("block1_tr.conv1", "block1_tr.norm1"),
     ("mlp1", None), ("final", None))
 
-_typed = None
-
 
 def load_native():
     """libumereg.so with the entry points of include/umereg_featnet.h typed (raises without the built library)."""
-    global _typed
-    lib = _lib.load()
-    if _typed is not lib:
-        for name, (res, args) in FEATNET_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise _lib.NativeLibraryError(f"{_lib.LIB_PATH} does not export {name}") from e
-            fn.restype, fn.argtypes = res, args
-        _typed = lib
-    return lib
+    return _lib.load_typed(FEATNET_SIGNATURES)
 
 
 def layer_info():

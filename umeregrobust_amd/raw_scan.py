@@ -45,22 +45,10 @@ EXTENSIONS_SCAN, EXTENSIONS_LABEL = (".bin",), (".label",)   # LaserScan.EXTENSI
 NUSCENES_EGO_BOX = (2.5, 1.0)                                # nuscenes_dataset.py:404
 LABEL_COPY_DIST_THR = 3.0                                    # SemanticKITTIDataset.LABEL_COPY_DIST_THR
 
-_typed = None
-
 
 def load_native():
     """libumereg.so with the entry points of include/umereg_scan_prep.h typed (raises without the built library)."""
-    global _typed
-    lib = _lib.load()
-    if _typed is not lib:
-        for name, (res, args) in SCAN_PREP_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise _lib.NativeLibraryError(f"{_lib.LIB_PATH} does not export {name}") from e
-            fn.restype, fn.argtypes = res, args
-        _typed = lib
-    return lib
+    return _lib.load_typed(SCAN_PREP_SIGNATURES)
 
 
 def workspace_bytes(n):

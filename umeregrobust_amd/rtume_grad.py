@@ -23,22 +23,10 @@ RTUME_GRAD_SIGNATURES = {
 
 MIN_GAP = 1e-8      # UMEREG_RTUME_BWD_MIN_GAP: s'_i + s'_j <= MIN_GAP * s1 -> the pair (i, j) has no gradient
 
-_typed = None
-
 
 def load_native():
     """libumereg.so with the entry point of include/umereg_rtume_grad.h typed (raises without the built library)."""
-    global _typed
-    lib = _lib.load()
-    if _typed is not lib:
-        for name, (res, args) in RTUME_GRAD_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise _lib.NativeLibraryError(f"{_lib.LIB_PATH} does not export {name}") from e
-            fn.restype, fn.argtypes = res, args
-        _typed = lib
-    return lib
+    return _lib.load_typed(RTUME_GRAD_SIGNATURES)
 
 
 def _on_gpu(who, *tensors):

@@ -37,22 +37,12 @@ N_TABLES, MAX_CH = 13, 256
 # summation; one chain over 27 x 256 products carries about twice the rounding error of eight chains over 27 x 32)
 SLICE = 32
 
-_typed = None
-
 
 def load_native():
-    """libumereg.so with the entry points of include/umereg_sparse_conv.h typed (raises without the built library)."""
-    global _typed
-    lib = _models.load_native()
-    if _typed is not lib:
-        for name, (res, args) in SPARSE_CONV_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise _lib.NativeLibraryError(f"{_lib.LIB_PATH} does not export {name}") from e
-            fn.restype, fn.argtypes = res, args
-        _typed = lib
-    return lib
+    """libumereg.so with the entry points of include/umereg_sparse_conv.h (and of umereg_featnet.h) typed (raises without the
+    built library)."""
+    _models.load_native()
+    return _lib.load_typed(SPARSE_CONV_SIGNATURES)
 
 
 def out_level(table):

@@ -29,22 +29,10 @@ UME_GRAD_SIGNATURES = {
 D_MIN = 4e-3        # UMEREG_UME_CDIST_BWD_DMIN: at or below it a pair has no gradient (the forward's noise floor at D = 0)
 MAX_K = 7680        # UMEREG_UME_GRAD_MAX_K
 
-_typed = None
-
 
 def load_native():
     """libumereg.so with the entry points of include/umereg_ume_grad.h typed (raises without the built library)."""
-    global _typed
-    lib = _lib.load()
-    if _typed is not lib:
-        for name, (res, args) in UME_GRAD_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise _lib.NativeLibraryError(f"{_lib.LIB_PATH} does not export {name}") from e
-            fn.restype, fn.argtypes = res, args
-        _typed = lib
-    return lib
+    return _lib.load_typed(UME_GRAD_SIGNATURES)
 
 
 def _stream(dev):
