@@ -262,15 +262,22 @@ def _phase_a(src_pts, tgt_pts, src_feat, tgt_feat, args, src_inds, tgt_inds, mat
     num_kpts = min(ume_src.shape[1], ume_tgt.shape[1])
     ume_src = ume_src[:, :num_kpts]
     ume_tgt = ume_tgt[:, :num_kpts]
-    # Matches (:215-225).  Hungarian matching (:216-222; off in every shipped config) needs the whole matrix on the
-    # host, exactly like the reference: D -> scipy.optimize.linear_sum_assignment -> (src rows, tgt columns)
+    # Matches (:215-225).  Hungarian matching (:216-222; off in every shipped config): by default the whole matrix goes to the
+    # host, exactly like the reference: D -> scipy.optimize.linear_sum_assignment -> (src rows, tgt columns); with
+    # args.assignment == "device" the solver of ops.linear_sum_assignment takes D where it lies
     D = None
     if getattr(args, "hungarian_matching_flag", False):
-        from scipy.optimize import linear_sum_assignment
+        assignment = getattr(args, "assignment", "host")
+        if assignment not in ("host", "device"):
+            raise ValueError(f"args.assignment must be 'host' or 'device', got {assignment!r}")
         D = ops.ume_cdist(ume_src, ume_tgt, timing=t_dist)
-        src_m, tgt_m = linear_sum_assignment(D[0].cpu().numpy())                              # :219
-        m_src = torch.from_numpy(src_m).long().to(dev)[None]                                  # m[..., 0]
-        m_tgt = torch.from_numpy(tgt_m).long().to(dev)[None]                                  # m[..., 1]
+        if assignment == "device":
+            m_src, m_tgt = ops.linear_sum_assignment(D[0:1])                                  # :219; [1, n] each
+        else:
+            from scipy.optimize import linear_sum_assignment
+            src_m, tgt_m = linear_sum_assignment(D[0].cpu().numpy())                          # :219
+            m_src = torch.from_numpy(src_m).long().to(dev)[None]                              # m[..., 0]
+            m_tgt = torch.from_numpy(tgt_m).long().to(dev)[None]                              # m[..., 1]
         ume_d = D[0, m_src[0], m_tgt[0]][None]                                                # :234
         prob = ops.match_prob(ume_d[0], args.tau) if args.filter_by_ume_dist_cond else None
         return SimpleNamespace(ume_src=ume_src, ume_tgt=ume_tgt, match=m_tgt, match_src=m_src, match_d=ume_d, prob=prob,

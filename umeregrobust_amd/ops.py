@@ -1019,3 +1019,7 @@ class PairMatchGraph(_PairGraph):
                                                            prob_host_ptr or None, stream_ptr)
         if rc:
             _lib.check(rc, "umereg_pair_match_graph_launch_from")
+
+
+# scipy.optimize.linear_sum_assignment on the device (include/umereg_assign.h, typed by its own table in assign.py)
+from .assign import linear_sum_assignment  # noqa: E402,F401

@@ -30,7 +30,11 @@ worker anyway).
 end to end: items stay where the augmentation made them, `collate.batch_collate_fn_dset_device` gathers them there, and
 `train_one_epoch` reads a step's scalars one batch late, after it has fetched and collated the next batch, so that the host's share
 of the data side (item read, augmentation launches, the numpy draws, collate launches) runs under the device's backward pass.  What
-is computed, the order in which the host RNG is consumed and everything that is logged are the same as without the flag."""
+is computed, the order in which the host RNG is consumed and everything that is logged are the same as without the flag.
+
+`--device-assignment` (`run(..., device_assignment=True)`) gives the validation epoch's inlier ratio the device solver
+(`calc_inliear_ratio(..., assignment="device")`): the distance matrices of a validation batch stay on the GPU and are solved side
+by side instead of one after another by scipy on the host.  Off by default."""
 import argparse
 import json
 import os
@@ -253,12 +257,13 @@ def train_one_epoch_late_read(epoch, data_loader, model, loss_func, optimizer, s
     print(f"train epoch {epoch + 1} done")
 
 
-def eval_one_epoch(epoch, data_loader, model, loss_func, summary_writer, ctx):
+def eval_one_epoch(epoch, data_loader, model, loss_func, summary_writer, ctx, assignment="host"):
     """The reference's eval_one_epoch (train_coloring.py:96-207) -> (valid_loss, valid_pw_loss, valid_ume_loss, valid_reg_loss,
     valid_inlear_ratio, valid_reg_acc).  Quirks kept: the first three are all the TOTAL loss (the UME one 0.0 without the UME loss);
     sums are divided by the number of batches, skipped ones included; the inlier-ratio call gets `[valid_batch_entries]`, a list, as
     the target's 'seg', which it never reads; with `calc_inlear_ratio_eval` off the ratio is 0.  One departure: `valid_reg_acc` is
-    0.0 without the registration loss, where the reference's return statement raises UnboundLocalError."""
+    0.0 without the registration loss, where the reference's return statement raises UnboundLocalError.  assignment: "host" or
+    "device", where the Hungarian matching of the inlier ratio runs (calc_inliear_ratio)."""
     sums = RunningSums()
     n_batches = len(data_loader)
     with_reg = ctx.use_ume_loss and ctx.use_reg_loss
@@ -282,7 +287,8 @@ def eval_one_epoch(epoch, data_loader, model, loss_func, summary_writer, ctx):
                 src_inputs = dict(pts=batch.src_pts[valid], seg=batch.src_seg[valid], feat=src_feat[valid])
                 tgt_inputs = dict(pts=batch.tgt_pts[valid], seg=[valid], feat=tgt_feat[valid])
                 ratio = calc_inliear_ratio(src_inputs, tgt_inputs, batch.src_pts_tform, batch.gt_tform[valid], ctx.ume_r_nn, ctx.ume_max_nn,
-                                           ctx.ume_min_nn, eval_num_kpts=ctx.eval_num_kpts, inlear_thr=ctx.eval_inlear_thr)
+                                           ctx.ume_min_nn, eval_num_kpts=ctx.eval_num_kpts, inlear_thr=ctx.eval_inlear_thr,
+                                           assignment=assignment)
                 sums.add(inlier_ratio=ratio.mean())
         if (i + 1) % 10 == 0:
             print(" | ".join(f"{k} {sums.get(k) / (i + 1):.4f}" for k in ("total", "pointwise", "ume", "reg")) +
@@ -412,11 +418,12 @@ def make_loaders(args, synthetic=0, synthetic_points=3000, device_collate=False)
     return mk(dset_train, True), mk(dset_valid, False)
 
 
-def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=None, device_collate=False):
+def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=None, device_collate=False, device_assignment=False):
     """train_coloring.py:263-437 -> the run directory.  Quirks kept: every "best" file stores the validation TOTAL loss; the
     UME and point-wise "best" follow the total (eval_one_epoch returns it three times); without the registration loss the validation
     registration loss is 0.0, so `best_reg_loss` (from inf) is written once, after the first epoch, and `best_mCHR` (from 0.0) never.
-    device_collate: batches are collated on the device and the training loop reads its scalars one batch late (module docstring)."""
+    device_collate: batches are collated on the device and the training loop reads its scalars one batch late (module docstring).
+    device_assignment: the validation epoch's Hungarian matching runs on the device (module docstring)."""
     torch.manual_seed(args.random_seed)
     np.random.seed(args.random_seed)
     device = torch.device(args.device)
@@ -441,7 +448,8 @@ def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=
         model.train()
         train_one_epoch(epoch, dloader_train, model, point_wise_loss_fn, optimizer, summary_writer, ctx, late_read=device_collate)
         model.eval()
-        total, pw, ume, reg, inlear, mchr = eval_one_epoch(epoch, dloader_valid, model, point_wise_loss_fn, summary_writer, ctx)
+        total, pw, ume, reg, inlear, mchr = eval_one_epoch(epoch, dloader_valid, model, point_wise_loss_fn, summary_writer, ctx,
+                                                            assignment="device" if device_assignment else "host")
         for name, value, better in (("best_total_loss", total, total < best["best_total_loss"]),
                                     ("best_pointwise_loss", pw, pw < best["best_pointwise_loss"]),
                                     ("best_ume_loss", ume, ume < best["best_ume_loss"]),
@@ -470,6 +478,8 @@ def main(argv=None):
     parser.add_argument('--resume', default=None, help="resume_train_path of the config")
     parser.add_argument('--device-collate', action='store_true',
                         help="collate on the GPU and read each step's scalars one batch late (same batches, same log)")
+    parser.add_argument('--device-assignment', action='store_true',
+                        help="solve the validation epoch's Hungarian matching on the GPU instead of with scipy on the host")
     cli = parser.parse_args(argv)
     over = {k: v for k, v in (("cache_data_path", cli.cache), ("num_epochs", cli.epochs), ("batch_size", cli.batch_size),
                               ("output_path", cli.output_path), ("resume_train_path", cli.resume)) if v is not None}
@@ -479,7 +489,8 @@ def main(argv=None):
         args.ume_max_nn, args.ume_min_nn, args.ume_r_nn, args.ume_n_samples, args.num_pw_samples = 64, 8, 2.0, 32, 128
         args.eval_num_kpts, args.batch_size = 32, min(args.batch_size, 2)
     print(f"Train {args.dataset} config: {cli.config_path or 'built-in defaults'}")
-    out = run(args, synthetic=cli.synthetic, synthetic_points=cli.synthetic_points, device_collate=cli.device_collate)
+    out = run(args, synthetic=cli.synthetic, synthetic_points=cli.synthetic_points, device_collate=cli.device_collate,
+              device_assignment=cli.device_assignment)
     print(f"run directory: {out}")
     return out
 
