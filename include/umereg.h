@@ -413,7 +413,12 @@ int umereg_hypothesis_gates_f32(const float* T, const float* gt_tform, int n, ui
 /* pytorch3d.ops.knn_points(p1, p2, K)   -- utils/loc_utils.py:580,623; evaluate.py:272,274
  * Exact K nearest points of p2[b] for every p1[b,i]: squared distances ascending, ties towards the
  * lower index (upstream leaves tie order unspecified).  K <= min(64, n2).
- *   p1 [B,n1,3]  p2 [B,n2,3]  ->  dists f32 [B,n1,K], idx int64 [B,n1,K] */
+ *   p1 [B,n1,3]  p2 [B,n2,3]  ->  dists f32 [B,n1,K], idx int64 [B,n1,K]
+ * K >= 2 runs one query per lane with a candidate list of K + 6 keys per lane in LDS.  Two things change with the sizes, the
+ * results do not: the list holds 16-bit target indices up to n2 = 65 536 and 32-bit ones from 65 537 on (another instance of
+ * the kernel), and with 32-bit indices a wavefront's list is (K + 6) * 512 bytes, so the workgroup has four wavefronts up to
+ * K = 26, two up to K = 58 (exactly 64 KiB of dynamic LDS at K = 58) and a single one from K = 59 on.  Queries are taken in the
+ * target grid's cell order while n1 <= n2 rounded up to a multiple of 256, in the caller's order beyond. */
 size_t umereg_knn_workspace_bytes(int B, int n2);
 int umereg_knn_points_f32(const float* p1, const float* p2, int B, int n1, int n2, int K, float* dists,
                           int64_t* idx, void* workspace, size_t workspace_bytes, void* stream);
@@ -432,7 +437,11 @@ int umereg_nn1_pair_f32(const float* q_src, const float* q_tgt, const float* p_s
 /* feature_spatial_var(pts, feat, knn)   -- utils/loc_utils.py:579-585
  * out[b,i] = mean over the knn-1 nearest OTHER points j of |feat[b,i] - feat[b,j]|_2 (self-kNN,
  * idx[:, :, 1:]); fused kNN + gather + norm, nothing of size [N,knn,32] is formed.
- *   pts [B,N,3], feat [B,N,32] -> out f32 [B,N]; workspace: umereg_knn_workspace_bytes(B, N) */
+ *   pts [B,N,3], feat [B,N,32] -> out f32 [B,N]; workspace: umereg_knn_workspace_bytes(B, N)
+ * 2 <= knn <= min(64, N).  Up to N = 32 768 one wavefront serves a query; larger clouds run umereg_knn_points_f32's
+ * one-query-per-lane search on themselves, with its switches: 16-bit list indices up to N = 65 536 and 32-bit ones from
+ * 65 537 on, one wavefront per workgroup from knn = 59 on with 32-bit indices, and 32 instead of 64 queries per wavefront
+ * while N <= 65 472.  The neighbours are the same whichever kernel runs; the two kernels sum them in different orders. */
 int umereg_feature_spatial_var_f32(const float* pts, const float* feat, int B, int N, int feat_dim, int knn,
                                    float* out, void* workspace, size_t workspace_bytes, void* stream);
 
