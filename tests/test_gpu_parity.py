@@ -215,7 +215,7 @@ def test_moments_packed_f32_option(gpu):
 @pytest.mark.parametrize("K", [750, 64, 1000, 1300])
 def test_moments_saturated_ball(gpu, K):
     """Dense cloud: every ball holds > K points -> first-K-by-index truncation must match.  K = 750 / 64: the K-th smallest index is
-    selected in registers (lists of <= 1 280 entries: K <= 768); K = 1 000 / 1 300: the selection walks the LDS list (radix passes);
+    selected in registers (lists of <= 1 280 entries: K <= 960, see lds_plan); K = 1 000 / 1 300: the selection walks the LDS list (radix passes);
     either way the list overflows several times per ball (~9 000 points inside) and room is made between trips of four chunks."""
     from umeregrobust_amd import ops
     rng = np.random.RandomState(8)

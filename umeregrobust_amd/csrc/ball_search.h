@@ -50,7 +50,8 @@ __device__ __forceinline__ int compact_le(int* lst, int cnt, int thr, int lane)
     return out;
 }
 
-// The same two steps with the list held in REGISTERS (lists of up to kSelRegs x 64 entries: K <= 768, every config of the reference).
+// The same two steps with the list held in REGISTERS (lists of up to kSelRegs x 64 entries, i.e. wherever lds_plan's smallest list
+// Kpad + (kScanUnroll + 1) * 64 fits them: K <= 960 with the defaults 20 and 4, every config of the reference).
 // select_kth walks the LDS list once per bit -- 18 passes x 24 dependent reads for a 200 000-point cloud, ~50 000 cycles of a wavefront's
 // life per selection -- and every saturated ball needs at least one (config 5: search 198 of the kernel's 248 us).  Here each lane
 // reads its <= kSelRegs entries once (the reads in flight together), the K-th smallest index is found by bisection on the VALUE with
@@ -237,8 +238,9 @@ constexpr void lds_plan(int K, int* cap, int* waves)
 {
     const int Kpad = (K + 63) / 64 * 64;
     // the list: >= K + a trip of kScanUnroll chunks + one (room is made before a trip's loads are issued); twice K + a chunk where that is
-    // more (fewer selections).  A list that can fit the in-register selection (kSelRegs entries per lane: K <= 768 -- the reference's 750 --
-    // with the default 20) is capped at what fits.  Measured (tools/exp_mom_time.py, us per pair SY / KT / NS; selection in LDS: 242 / 103 /
+    // more (fewer selections).  A list that can fit the in-register selection (kSelRegs entries per lane: cap_min <= reg_cap, which is
+    // K <= 960 with the defaults kSelRegs = 20, kScanUnroll = 4 -- the reference's 750 is inside) is capped at what fits; K = 961 is the first
+    // plan whose selection walks the LDS list.  Measured (tools/exp_mom_time.py, us per pair SY / KT / NS; selection in LDS: 242 / 103 /
     // 47): 25 registers (list 1 600) 149 / 108 / 50, 20 (1 280) 158 / 103 / 48 -- five registers more cost KT its eighth wavefront.
     const int reg_cap = kSelRegs * kWave, cap_min = Kpad + (kScanUnroll + 1) * kWave;
     const int cap_big = std::max(2 * Kpad + 64, cap_min);
