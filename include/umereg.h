@@ -388,7 +388,7 @@ int umereg_rtume_solve_f32(const float* G_all, const float* H_all, const int64_t
 
 /* ---------------------------------------------------------------------------------------------
  * a7  utils.eval_utils.relative_rotation_error(R, R_hat)             utils/eval_utils.py:60-76
- *   R, R_hat f32 [b,3,3] -> degrees f32 [b]
+ *   R, R_hat f32 [b,3,3] -> degrees f32 [b]; the trace is clamped as torch.clamp does: a NaN stays NaN
  * ------------------------------------------------------------------------------------------- */
 int umereg_rre_deg_f32(const float* R, const float* R_hat, int b, float* out_deg, void* stream);
 
@@ -402,6 +402,7 @@ int umereg_rre_deg_f32(const float* R, const float* R_hat, int b, float* out_deg
  *   counts[3] += #(rre <= 1   deg & rte <= 0.1 m)   "S.P"            (evaluate.py:305)
  * counts: uint64 [4], caller-initialised, accumulated with integer atomics (order-independent).
  *   T f32 [n,4,4], gt_tform f32 [4,4]; rre_deg / rte f32 [n] optional outputs.
+ *   A row with a NaN trace reports rre_deg = NaN (never 180) and passes no gate: it counts in counts[0] only.
  * ------------------------------------------------------------------------------------------- */
 int umereg_hypothesis_gates_f32(const float* T, const float* gt_tform, int n, uint64_t* counts,
                                 float* rre_deg, float* rte, void* stream);

@@ -110,7 +110,7 @@ __global__ void rre_kernel(const float* __restrict__ R, const float* __restrict_
         for (int q = 0; q < 3; ++q) d = d + c[p * 3 + q] * a[p * 3 + q];
         tr = tr + d;
     }
-    tr = fminf(fmaxf(tr, -1.0f), 3.0f);                                        // :68
+    tr = tr < -1.0f ? -1.0f : (tr > 3.0f ? 3.0f : tr);                         // :68 torch.clamp: a NaN trace stays NaN
     const float rad = acosf((tr - 1.0f) / 2.0f);                               // :71
     out[i] = rad * (180.0f / 3.141592653589793f);                              // :74
 }
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void hypothesis_gates_kernel(const float* __re
             for (int q = 0; q < 3; ++q) d = d + gt[p * 4 + q] * t[p * 4 + q];
             tr = tr + d;
         }
-        tr = fminf(fmaxf(tr, -1.0f), 3.0f);
+        tr = tr < -1.0f ? -1.0f : (tr > 3.0f ? 3.0f : tr);                                // torch.clamp: a NaN trace stays NaN (it fails every gate)
         rre = acosf((tr - 1.0f) / 2.0f) * (180.0f / 3.141592653589793f);
         const float dx = t[3] - gt[3], dy = t[7] - gt[7], dz = t[11] - gt[11];
         rte = sqrtf(dx * dx + dy * dy + dz * dz);                                         // evaluate.py:43

@@ -6,48 +6,12 @@
 // No sort: a voxel's first point is the minimum index over its points, which an open-addressing hash table over the
 // 63-bit voxel key finds with one atomicMin per point (order independent, hence deterministic); the representatives are
 // the points whose own index is their voxel's minimum, compacted in index order (compact.h).
+// The table plan, the key and its home slot are voxel_key.h's (host-checkable: tests/test_voxel_key_cpu.py).
 // 4 small kernels + 1 memset instead of ~15 torch launches with two device sorts (evaluate.py's loop: 0.30 -> 0.03 ms).
 #include "compact.h"
+#include "voxel_key.h"
 
 namespace umereg {
-
-constexpr int kVoxBlock = 1024;
-constexpr unsigned long long kVoxEmpty = ~0ull;
-
-struct VoxWs {
-    size_t off_keys, off_min, off_slot, off_bcnt, total;
-    unsigned int cap;     // table capacity (power of two, >= 2 n)
-    int n_blocks;
-};
-
-__host__ __device__ inline VoxWs vox_ws(int n)
-{
-    VoxWs w;
-    unsigned int cap = 1024u;
-    while (cap < 2u * (unsigned int)n) cap <<= 1;
-    w.cap = cap;
-    w.n_blocks = (n + kVoxBlock - 1) / kVoxBlock;
-    size_t o = 0;
-    w.off_keys = o; o += (size_t)cap * 8;
-    w.off_min = o;  o += (size_t)cap * 4;
-    w.off_slot = o; o += ((size_t)n + 3) / 4 * 16;
-    w.off_bcnt = o; o += ((size_t)w.n_blocks + 1 + 3) / 4 * 16;
-    w.total = (o + 255) / 256 * 256;
-    return w;
-}
-
-// floor(p / voxel) per axis (fp32 division and floor, as torch.floor(coordinates / quantization_size)), 21 bits per axis
-__device__ __forceinline__ bool voxel_key(const float* __restrict__ p, float voxel, unsigned long long& key)
-{
-    const float fx = floorf(p[0] / voxel), fy = floorf(p[1] / voxel), fz = floorf(p[2] / voxel);
-    const float lim = 1048575.0f;                       // |q| < 2^20
-    if (!(fabsf(fx) <= lim && fabsf(fy) <= lim && fabsf(fz) <= lim)) return false;      // (NaN / inf / out of range)
-    const unsigned long long qx = (unsigned long long)((long long)fx + 1048576ll);
-    const unsigned long long qy = (unsigned long long)((long long)fy + 1048576ll);
-    const unsigned long long qz = (unsigned long long)((long long)fz + 1048576ll);
-    key = (qx << 42) | (qy << 21) | qz;
-    return true;
-}
 
 __global__ __launch_bounds__(256) void voxel_insert_kernel(const float* __restrict__ pts, int n, float voxel, char* __restrict__ ws,
                                                            int* __restrict__ out_count)
@@ -64,7 +28,7 @@ __global__ __launch_bounds__(256) void voxel_insert_kernel(const float* __restri
         slot_of[i] = 0xffffffffu;
         return;
     }
-    unsigned int s = (unsigned int)((key * 0x9E3779B97F4A7C15ull) >> 32) & (w.cap - 1u);
+    unsigned int s = voxel_home_slot(key, w.cap);
     for (;;) {
         const unsigned long long old = atomicCAS(&keys[s], kVoxEmpty, key);
         if (old == kVoxEmpty || old == key) break;
