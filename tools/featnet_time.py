@@ -8,7 +8,10 @@
   * the fraction of the issued MFMA work that was useful: a tile of TM rows issues every offset some row of it uses, for all
     its rows (conv1 and `final` run on the VALU and are left out of both counts).
 
-    python tools/featnet_time.py [--config KT|NS] [--iters 50] [--warmup 10]
+    python tools/featnet_time.py [--config KT|NS] [--iters 50] [--warmup 10] [--precision f32|f16]
+
+`--precision f16`: the f16-operand forward (include/umereg_featnet_f16.h); the line carries a "precision" key, and the peak
+fraction stays relative to the fp32 matrix peak so that the two precisions' lines compare.
 
 `--train`: the trainable network (ResUNetSmall2(trainable=True), train mode) at the same cloud, or with `--batch B` at B such
 clouds in one call (16 KITTI-test clouds are 800 000 rows, the upper end of the reference's training shape: batch 8 x
@@ -185,6 +188,7 @@ def main(argv=None):
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--precision", default="f32", choices=list(models.PRECISIONS), help="operand precision of the fused forward")
     a = ap.parse_args(argv)
     assert torch.cuda.is_available(), "featnet_time measures on the GPU"
     dev = torch.device("cuda:0")
@@ -218,7 +222,7 @@ def main(argv=None):
         return e0.elapsed_time(e1) / a.iters
 
     ms_maps = timed(lambda: models.build_maps_raw(coords, 1, ws, status))
-    ms_total = timed(lambda: models.forward_raw(coords, feat, 1, params, ws, out, status))
+    ms_total = timed(lambda: models.forward_raw(coords, feat, 1, params, ws, out, status, a.precision))
     levels = models.check_status(status)
     masks = models.buffer_view(ws, n, 1, models.BUF_MASKS, n, torch.int32)      # [13][n] words, viewed as [n, 13]
     masks = masks.reshape(-1)[:13 * n].cpu().numpy().view(np.uint32).reshape(13, n)
@@ -228,7 +232,7 @@ def main(argv=None):
     useful_total = float(sum(useful))
     mfma_useful = float(sum(u for i, u in enumerate(useful) if i not in VALU_LAYERS))
     names = [name.split(".")[0] if name.startswith("block") and ".conv1" in name else name for name, _ in models.LAYERS]
-    line = dict(tool="featnet_time", config=a.config, n=n, levels=levels, iters=a.iters,
+    line = dict(tool="featnet_time", precision=a.precision, config=a.config, n=n, levels=levels, iters=a.iters,
                 ms_per_cloud=dict(maps=round(ms_maps, 4), conv=round(ms_conv, 4), total=round(ms_total, 4)),
                 useful_gflop=round(useful_total / 1e9, 3),
                 useful_tflops_in_conv=round(useful_total / (ms_conv * 1e-3) / 1e12, 2),

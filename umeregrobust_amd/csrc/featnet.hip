@@ -12,9 +12,13 @@
 // The single-layer entries of include/umereg_sparse_conv.h that launch these kernels live here too (a kernel is launched only
 // from the unit that defines it): the plain convolution over one table (fn_conv_kernel with the caller's scale / shift block,
 // no ReLU, the residual input used only to accumulate channel slices into the output) and conv1's forward.  The training path's own kernels are in sparse_wgrad.hip.
+//
+// The f16-operand inference mode (include/umereg_featnet_f16.h) is fn_conv_f16_kernel, the twin of fn_conv_kernel on
+// v_mfma_f32_32x32x16_f16, launched for layers 1..18 by the same forward; conv1 and `final` are the f32 kernels in both modes.
 #include <math.h>
 
 #include "sparse.h"
+#include "umereg_featnet_f16.h"
 #include "umereg_sparse_conv.h"
 
 namespace umereg {
@@ -210,6 +214,124 @@ __global__ __launch_bounds__(256) void fn_final_kernel(const float* __restrict__
         o[c4] = make_float4(acc[4 * c4] / nrm, acc[4 * c4 + 1] / nrm, acc[4 * c4 + 2] / nrm, acc[4 * c4 + 3] / nrm);
 }
 
+// ---- the f16-operand twin of fn_conv_kernel (include/umereg_featnet_f16.h) ------------------------------------------------------
+//
+// Same tiles, same offset walk, same prefetch and the same epilogue; the two staged tiles hold f16 (each gathered activation and
+// each weight rounded to nearest even where the tile is staged) and a 32-channel step is two v_mfma_f32_32x32x16_f16 with f32
+// accumulation: every output element is one fixed chain -- offsets ascending, channels ascending in groups of 16.
+// For 32x32x16, lane l (r = l & 31, h = l >> 5) holds A[r][8h + j] and B[8h + j][r], j = 0..7: the A tile is [row][channel], the B
+// tile is stored transposed, [output column][channel], so both fragments are 8 consecutive f16 = one 16-byte read.  Rows of 32
+// f16 are padded by one read width (8 f16) to 80 bytes: the 16 lanes that ds_read_b128 serves in one cycle read 16 rows distinct
+// mod 16, and 5 r mod 16 puts those on the 16 different 16-byte slots of the 256-byte bank row.
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+constexpr int kKP = kKC + 8;            // f16 per padded LDS row
+constexpr float kF16Max = 65504.f;
+
+struct ConvArgsF16 {
+    ConvArgs c;
+    int32_t* range;         // status word that takes UMEREG_FN_ERR_F16_RANGE when a stored value is not within +-65504 (or null)
+};
+
+template <int TM, int TN>
+__global__ __launch_bounds__(256) void fn_conv_f16_kernel(ConvArgsF16 args)
+{
+    constexpr int WM = TM / 32;                 // waves along the rows; (TM / 32) x (TN / 32) = 4 waves
+    constexpr int TPR = 256 / TM;               // staging threads per input row
+    constexpr int AF = kKC / TPR;               // activations each of them stages
+    constexpr int BF = kKC * TN / 256;          // weights per thread: BF consecutive channels of one output column
+    static_assert(WM * (TN / 32) == 4 && AF % 8 == 0 && (BF == 4 || BF == 8) && (256 / TN) * BF == kKC, "tile shape");
+    __shared__ __attribute__((aligned(16))) _Float16 As[TM][kKP];
+    __shared__ __attribute__((aligned(16))) _Float16 Bt[TN][kKP];   // Bt[col][channel]
+    __shared__ int Ns[TM][kFnVol];              // the tile's neighbour rows
+    __shared__ unsigned int s_mask;
+
+    const ConvArgs& a = args.c;
+    const int n_rows = *a.n_out;
+    const int m0 = blockIdx.x * TM;
+    if (m0 >= n_rows) return;
+    const int n0 = blockIdx.y * TN;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave % WM, wn = wave / WM;
+    if (tid == 0) s_mask = a.K > 1 ? 0u : 1u;
+    if (a.K > 1) {
+        const int* nb = a.nbr + (size_t)m0 * kFnVol;
+        for (int e = tid; e < TM * kFnVol; e += 256) Ns[e / kFnVol][e % kFnVol] = m0 + e / kFnVol < n_rows ? nb[e] : -1;
+    }
+    __syncthreads();
+    if (a.K > 1 && tid < TM && m0 + tid < n_rows) atomicOr(&s_mask, a.mask[m0 + tid]);
+    __syncthreads();
+
+    // steps: (offset k, channel slice) over the offsets some row of the tile uses, k ascending; the global loads of step s + 1
+    // (f32, as stored) are in flight while the MFMAs of step s run, and are rounded when they are staged
+    const int lr = tid / TPR, seg = tid % TPR, arow = m0 + lr;
+    const int bcol = tid % TN, bk = (tid / TN) * BF;
+    const int n_sl = a.cin / kKC;
+    unsigned int rem = s_mask;
+    int k = rem ? __builtin_ctz(rem) : 0, sl = 0;
+    float4 av[AF / 4];
+    float bv[BF];
+    auto load = [&](int k_, int sl_) {
+        const int src = arow < n_rows ? (a.K > 1 ? Ns[lr][k_] : arow) : -1;
+        if (src >= 0) {
+            const float4* p = reinterpret_cast<const float4*>(a.in + (size_t)src * a.ld_in + sl_ * kKC + seg * AF);
+#pragma unroll
+            for (int j = 0; j < AF / 4; ++j) av[j] = p[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < AF / 4; ++j) av[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        const float* q = a.W + ((size_t)k_ * a.cin + sl_ * kKC + bk) * a.cout + n0 + bcol;
+#pragma unroll
+        for (int j = 0; j < BF; ++j) bv[j] = q[(size_t)j * a.cout];
+    };
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    if (rem) load(k, sl);
+    while (rem) {
+        __syncthreads();                              // the previous step's LDS tiles are consumed
+#pragma unroll
+        for (int j = 0; j < AF / 8; ++j) {
+            f16x8 h;
+            h[0] = (_Float16)av[2 * j].x, h[1] = (_Float16)av[2 * j].y, h[2] = (_Float16)av[2 * j].z, h[3] = (_Float16)av[2 * j].w;
+            h[4] = (_Float16)av[2 * j + 1].x, h[5] = (_Float16)av[2 * j + 1].y, h[6] = (_Float16)av[2 * j + 1].z,
+            h[7] = (_Float16)av[2 * j + 1].w;
+            *reinterpret_cast<f16x8*>(&As[lr][seg * AF + 8 * j]) = h;
+        }
+#pragma unroll
+        for (int j = 0; j < BF; ++j) Bt[bcol][bk + j] = (_Float16)bv[j];
+        __syncthreads();
+        if (++sl == n_sl) {
+            sl = 0;
+            rem &= rem - 1u;
+            k = rem ? __builtin_ctz(rem) : 0;
+        }
+        if (rem) load(k, sl);
+#pragma unroll
+        for (int kk = 0; kk < kKC / 16; ++kk) {
+            const f16x8 x = *reinterpret_cast<const f16x8*>(&As[wm * 32 + (lane & 31)][16 * kk + 8 * (lane >> 5)]);
+            const f16x8 y = *reinterpret_cast<const f16x8*>(&Bt[wn * 32 + (lane & 31)][16 * kk + 8 * (lane >> 5)]);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(x, y, acc, 0, 0, 0);
+        }
+    }
+    // C/D: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+    const int col = n0 + wn * 32 + (lane & 31);
+    const float sc = a.scale[col], sh = a.shift[col];
+    bool out_of_range = false;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (row >= n_rows) continue;
+        float v = fmaf(acc[r], sc, sh);
+        if (a.res) v += a.res[(size_t)row * a.ld_res + col];
+        out_of_range |= v != v;                       // (a NaN, which the ReLU would hide, comes from infinities met on the way)
+        if (a.relu) v = fmaxf(v, 0.f);
+        out_of_range |= fabsf(v) > kF16Max;
+        a.out[(size_t)row * a.ld_out + col] = v;
+    }
+    if (args.range && out_of_range) atomicOr(args.range, UMEREG_FN_ERR_F16_RANGE);
+}
+
 struct Fwd {
     const float* params;
     FnParamOffsets po;
@@ -217,6 +339,7 @@ struct Fwd {
     FnWs w;
     int32_t* status;
     hipStream_t st;
+    bool f16;               // layers 1..18 on fn_conv_f16_kernel
 
     const int* nbr(int m) const { return reinterpret_cast<const int*>(ws + w.off_nbr) + (size_t)m * w.n * kFnVol; }
     const unsigned int* mask(int m) const { return reinterpret_cast<const unsigned int*>(ws + w.off_mask) + (size_t)m * w.n; }
@@ -231,6 +354,17 @@ struct Fwd {
         a.res = res, a.out = out, a.nbr = m >= 0 ? nbr(m) : nullptr, a.mask = m >= 0 ? mask(m) : nullptr;
         a.n_out = status + 1 + lo;
         a.ld_in = ld_in, a.ld_res = ld_res, a.ld_out = ld_out, a.cin = L.cin, a.cout = L.cout, a.K = L.K, a.relu = relu ? 1 : 0;
+        if (f16) {
+            // the range check covers what a later f16 layer gathers: mlp1's output feeds `final`, which is f32
+            const ConvArgsF16 h{a, i < 18 ? status : nullptr};
+            if (L.cout % 64 == 0) {
+                hipLaunchKernelGGL((fn_conv_f16_kernel<64, 64>), dim3((w.n + 63) / 64, L.cout / 64), dim3(256), 0, st, h);
+            } else {
+                hipLaunchKernelGGL((fn_conv_f16_kernel<128, 32>), dim3((w.n + 127) / 128, L.cout / 32), dim3(256), 0, st, h);
+            }
+            UMEREG_CHECK_LAUNCH("fn_conv_f16_kernel");
+            return UMEREG_OK;
+        }
         if (L.cout % 64 == 0) {
             hipLaunchKernelGGL((fn_conv_kernel<64, 64>), dim3((w.n + 63) / 64, L.cout / 64), dim3(256), 0, st, a);
         } else {
@@ -311,8 +445,10 @@ UMEREG_API int umereg_featnet_build_maps(const int32_t* coords, int n, int batch
     return fn_build_maps(coords, n, batch, (char*)workspace, status, (hipStream_t)stream);
 }
 
-UMEREG_API int umereg_featnet_forward_f32(const int32_t* coords, const float* feat, int n, int batch, const float* params, float* out,
-                                          int32_t* status, void* workspace, size_t workspace_bytes, void* stream)
+namespace {
+// the forward pass of both precisions (f16: layers 1..18 on fn_conv_f16_kernel; conv1 and `final` are the f32 kernels either way)
+int fn_forward(const int32_t* coords, const float* feat, int n, int batch, const float* params, float* out, int32_t* status,
+               void* workspace, size_t workspace_bytes, void* stream, bool f16)
 {
     UMEREG_REQUIRE(feat && params && out, "featnet_forward: null pointer");
     UMEREG_REQUIRE(((uintptr_t)params & 15) == 0 && ((uintptr_t)out & 15) == 0, "featnet_forward: params and out must be 16-byte aligned");
@@ -322,7 +458,7 @@ UMEREG_API int umereg_featnet_forward_f32(const int32_t* coords, const float* fe
     char* ws = (char*)workspace;
     if (int rc = fn_build_maps(coords, n, batch, ws, status, st)) return rc;
 
-    Fwd f{params, fn_params(), ws, w, status, st};
+    Fwd f{params, fn_params(), ws, w, status, st, f16};
     float* X = f.buf(w.off_x);
     float* S4 = f.buf(w.off_s4);
     float* cat[4];
@@ -358,16 +494,34 @@ UMEREG_API int umereg_featnet_forward_f32(const int32_t* coords, const float* fe
     UMEREG_CHECK_LAUNCH("fn_final_kernel");
     return UMEREG_OK;
 }
+}  // namespace
+
+UMEREG_API int umereg_featnet_forward_f32(const int32_t* coords, const float* feat, int n, int batch, const float* params, float* out,
+                                          int32_t* status, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return fn_forward(coords, feat, n, batch, params, out, status, workspace, workspace_bytes, stream, false);
+}
+
+// ---- include/umereg_featnet_f16.h ---------------------------------------------------------------------------------------------
+
+UMEREG_API int umereg_featnet_forward_f16(const int32_t* coords, const float* feat, int n, int batch, const float* params, float* out,
+                                          int32_t* status, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return fn_forward(coords, feat, n, batch, params, out, status, workspace, workspace_bytes, stream, true);
+}
 
 // ---- include/umereg_sparse_conv.h: the entries that launch this unit's kernels ---------------------------------------------------
 
-UMEREG_API int umereg_sparse_conv_f32(const void* workspace, size_t workspace_bytes, const int32_t* status, int n, int table,
-                                      const float* in, int ld_in, const float* W, int c_in, int c_out, const float* scale,
-                                      const float* shift, float* out, int ld_out, int accumulate, void* stream)
+namespace {
+// the plain convolution of both precisions; f16 also takes table -1: the 1x1 layer over level 0 (W [C_in][C_out])
+int fn_sparse_conv(const void* workspace, size_t workspace_bytes, const int32_t* status, int n, int table, const float* in, int ld_in,
+                   const float* W, int c_in, int c_out, const float* scale, const float* shift, float* out, int ld_out, int accumulate,
+                   void* stream, bool f16)
 {
     UMEREG_REQUIRE(workspace && status && in && W && scale && shift && out, "sparse_conv: null pointer");
     UMEREG_REQUIRE(n > 0, "sparse_conv: n must be positive (got %d)", n);
-    UMEREG_REQUIRE(table >= 0 && table < UMEREG_SPARSE_CONV_TABLES, "sparse_conv: table %d outside [0, %d)", table, UMEREG_SPARSE_CONV_TABLES);
+    UMEREG_REQUIRE(table >= (f16 ? -1 : 0) && table < UMEREG_SPARSE_CONV_TABLES, "sparse_conv: table %d outside [%d, %d)", table,
+                   f16 ? -1 : 0, UMEREG_SPARSE_CONV_TABLES);
     UMEREG_REQUIRE(c_in > 0 && c_in % 32 == 0 && c_in <= UMEREG_SPARSE_CONV_MAX_CH && c_out > 0 && c_out % 32 == 0 &&
                        c_out <= UMEREG_SPARSE_CONV_MAX_CH,
                    "sparse_conv: channels %d -> %d must be multiples of 32 up to %d", c_in, c_out, UMEREG_SPARSE_CONV_MAX_CH);
@@ -383,11 +537,21 @@ UMEREG_API int umereg_sparse_conv_f32(const void* workspace, size_t workspace_by
     ConvArgs a;
     a.in = in, a.W = W, a.scale = scale, a.shift = shift, a.res = accumulate ? out : nullptr, a.out = out;   // (res == out: each
                                                                                                              // element is read, then written, by one thread)
-    a.nbr = reinterpret_cast<const int*>(ws + w.off_nbr) + (size_t)table * w.n * kFnVol;
-    a.mask = reinterpret_cast<const unsigned int*>(ws + w.off_mask) + (size_t)table * w.n;
-    a.n_out = status + 1 + fn_map_out_level(table);
-    a.ld_in = ld_in, a.ld_res = ld_out, a.ld_out = ld_out, a.cin = c_in, a.cout = c_out, a.K = kFnVol, a.relu = 0;
+    a.nbr = table >= 0 ? reinterpret_cast<const int*>(ws + w.off_nbr) + (size_t)table * w.n * kFnVol : nullptr;
+    a.mask = table >= 0 ? reinterpret_cast<const unsigned int*>(ws + w.off_mask) + (size_t)table * w.n : nullptr;
+    a.n_out = status + 1 + (table >= 0 ? fn_map_out_level(table) : 0);
+    a.ld_in = ld_in, a.ld_res = ld_out, a.ld_out = ld_out, a.cin = c_in, a.cout = c_out, a.K = table >= 0 ? kFnVol : 1, a.relu = 0;
     hipStream_t st = (hipStream_t)stream;
+    if (f16) {
+        const ConvArgsF16 h{a, nullptr};
+        if (c_out % 64 == 0) {
+            hipLaunchKernelGGL((fn_conv_f16_kernel<64, 64>), dim3((n + 63) / 64, c_out / 64), dim3(256), 0, st, h);
+        } else {
+            hipLaunchKernelGGL((fn_conv_f16_kernel<128, 32>), dim3((n + 127) / 128, c_out / 32), dim3(256), 0, st, h);
+        }
+        UMEREG_CHECK_LAUNCH("fn_conv_f16_kernel");
+        return UMEREG_OK;
+    }
     if (c_out % 64 == 0) {
         hipLaunchKernelGGL((fn_conv_kernel<64, 64>), dim3((n + 63) / 64, c_out / 64), dim3(256), 0, st, a);
     } else {
@@ -395,6 +559,23 @@ UMEREG_API int umereg_sparse_conv_f32(const void* workspace, size_t workspace_by
     }
     UMEREG_CHECK_LAUNCH("fn_conv_kernel");
     return UMEREG_OK;
+}
+}  // namespace
+
+UMEREG_API int umereg_sparse_conv_f32(const void* workspace, size_t workspace_bytes, const int32_t* status, int n, int table,
+                                      const float* in, int ld_in, const float* W, int c_in, int c_out, const float* scale,
+                                      const float* shift, float* out, int ld_out, int accumulate, void* stream)
+{
+    return fn_sparse_conv(workspace, workspace_bytes, status, n, table, in, ld_in, W, c_in, c_out, scale, shift, out, ld_out, accumulate,
+                          stream, false);
+}
+
+UMEREG_API int umereg_sparse_conv_f16(const void* workspace, size_t workspace_bytes, const int32_t* status, int n, int table,
+                                      const float* in, int ld_in, const float* W, int c_in, int c_out, const float* scale,
+                                      const float* shift, float* out, int ld_out, int accumulate, void* stream)
+{
+    return fn_sparse_conv(workspace, workspace_bytes, status, n, table, in, ld_in, W, c_in, c_out, scale, shift, out, ld_out, accumulate,
+                          stream, true);
 }
 
 UMEREG_API int umereg_sparse_conv1_f32(const void* workspace, size_t workspace_bytes, const int32_t* status, int n, const float* feat,

@@ -34,7 +34,12 @@ that would need gradients raise.
 are needed, the forward runs layer by layer -- every 27-offset convolution is `sparse_conv.sparse_conv` (HIP forward, HIP
 input and weight gradients), batch norm is the model's own `nn.BatchNorm1d` modules (batch statistics over all rows of the
 call and running-stat updates in train mode, running statistics in eval mode), residual / ReLU / concatenation / the two
-1x1 layers / the L2 normalisation are torch ops.  Eval mode under `torch.no_grad()` stays the fused call, bit for bit."""
+1x1 layers / the L2 normalisation are torch ops.  Eval mode under `torch.no_grad()` stays the fused call, bit for bit.
+
+`ResUNetSmall2(..., precision="f16")` (include/umereg_featnet_f16.h; the default is "f32"): the fused call with the operands of
+the seventeen 27-offset convolutions after conv1 and of mlp1 rounded to f16 (round to nearest even) and every sum, the
+epilogues and all stored activations in f32 -- deterministic like the f32 path.  Inference only: train mode and a forward
+that needs gradients raise, there is no silent fallback to f32.  An activation beyond the f16 range raises ValueError."""
 import ctypes
 
 import torch
@@ -56,10 +61,19 @@ FEATNET_SIGNATURES = {
                                            c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/umereg_featnet_f16.h one to one
+FEATNET_F16_SIGNATURES = {
+    "umereg_featnet_forward_f16": FEATNET_SIGNATURES["umereg_featnet_forward_f32"],
+    "umereg_sparse_conv_f16": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
+                                       c_void_p, c_void_p, c_int, c_int, c_void_p]),
+}
+
 # include/umereg_featnet.h
 N_LAYERS, OUT_CHANNELS, N_STATUS, MAX_BATCH = 20, 32, 8, 127
 BUF_COORDS0, BUF_CAT0, BUF_S4, BUF_HIDDEN, BUF_PERM, BUF_MASKS = 0, 5, 9, 10, 11, 12
 ERR_RANGE, ERR_DUPLICATE = 1, 2
+ERR_F16_RANGE = 4           # include/umereg_featnet_f16.h
+PRECISIONS = ("f32", "f16")
 
 # the packed parameter block's layer order (umereg_featnet_layer_info) -> (kernel, batch norm or None)
 LAYERS = (
@@ -76,8 +90,17 @@ LAYERS = (
 
 
 def load_native():
-    """libumereg.so with the entry points of include/umereg_featnet.h typed (raises without the built library)."""
-    return _lib.load_typed(FEATNET_SIGNATURES)
+    """libumereg.so with the entry points of include/umereg_featnet.h and umereg_featnet_f16.h typed (raises without the built
+    library)."""
+    _lib.load_typed(FEATNET_SIGNATURES)
+    return _lib.load_typed(FEATNET_F16_SIGNATURES)
+
+
+def check_precision(precision):
+    """-> `precision`, one of PRECISIONS ("f32"; "f16": f16 operands, f32 accumulation, inference only); else ValueError"""
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+    return precision
 
 
 def layer_info():
@@ -104,12 +127,15 @@ def buffer_view(ws, n, batch, which, rows, dtype=torch.float32):
     return ws[off.value:off.value + rows * cols.value * esz].view(dtype).view(rows, cols.value)
 
 
-def forward_raw(coords, feat, batch, params, ws, out, status):
-    """One forward pass through the C ABI on the current stream; no host sync, no error check of `status`."""
+def forward_raw(coords, feat, batch, params, ws, out, status, precision="f32"):
+    """One forward pass through the C ABI on the current stream; no host sync, no error check of `status`.  precision="f16":
+    umereg_featnet_forward_f16 (include/umereg_featnet_f16.h), same buffers."""
+    check_precision(precision)
     lib = load_native()
     n = coords.shape[0]
-    rc = lib.umereg_featnet_forward_f32(coords.data_ptr(), feat.data_ptr(), int(n), int(batch), params.data_ptr(), out.data_ptr(),
-                                        status.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(coords.device).cuda_stream)
+    fn = lib.umereg_featnet_forward_f16 if precision == "f16" else lib.umereg_featnet_forward_f32
+    rc = fn(coords.data_ptr(), feat.data_ptr(), int(n), int(batch), params.data_ptr(), out.data_ptr(),
+            status.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(coords.device).cuda_stream)
     _lib.check(rc, "featnet_forward")
 
 
@@ -120,9 +146,12 @@ def build_maps_raw(coords, batch, ws, status):
     _lib.check(rc, "featnet_build_maps")
 
 
-def check_status(status):
+def check_status(status, precision="f32"):
     """Raise on the error bits of a forward pass's status (one device read); -> level sizes [5]."""
     s = status.cpu().tolist()
+    if s[0] & ERR_F16_RANGE and not s[0] & (ERR_DUPLICATE | ERR_RANGE):
+        raise ValueError(f"ResUNetSmall2(precision={precision!r}): an activation left the f16 range (|x| > 65504) and would "
+                         "reach the next layer as infinity; run this input with precision='f32'")
     if s[0] & ERR_DUPLICATE:
         raise ValueError("ResUNetSmall2: duplicate coordinates in a batch item (MinkowskiEngine would merge them; "
                          "the reference's inputs come from sparse_quantize and are unique)")
@@ -166,9 +195,11 @@ class ResUNetSmall2(nn.Module):
     TR_CHANNELS = [None, 64, 64, 64, 128, 128]
     STRIDES = [1, 2, 2, 2, 3]
 
-    def __init__(self, in_channels=1, out_channels=32, bn_momentum=0.1, normalize_feature=True, D=3, trainable=False):
+    def __init__(self, in_channels=1, out_channels=32, bn_momentum=0.1, normalize_feature=True, D=3, trainable=False,
+                 precision="f32"):
         super().__init__()
         self.trainable = bool(trainable)
+        self.precision = check_precision(precision)
         if (in_channels, out_channels, bool(normalize_feature), D) != (1, OUT_CHANNELS, True, 3):
             raise ValueError("the HIP network is built for in_channels=1, out_channels=32, normalize_feature=True, D=3 "
                              "(the configuration of reference evaluate.py:163)")
@@ -235,6 +266,10 @@ class ResUNetSmall2(nn.Module):
         halves of every level's concatenation, block5's output and mlp1's output (see include/umereg_featnet.h)."""
         F, C = x.F, x.C
         needs_grad = torch.is_grad_enabled() and (F.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if self.precision != "f32" and (self.training or needs_grad):
+            raise RuntimeError(f"ResUNetSmall2(precision={self.precision!r}) is inference only: the layer-wise path (train mode, "
+                               "or a forward that needs gradients) is f32, and there is no silent fallback to it; call .eval() "
+                               "under torch.no_grad(), or build the model with precision='f32'")
         if not self.trainable:
             if self.training:
                 raise RuntimeError("ResUNetSmall2 runs forward only with eval-mode batch norm: call .eval() first "
@@ -260,8 +295,8 @@ class ResUNetSmall2(nn.Module):
         ws = self._workspace(n, batch, F.device)
         out = torch.empty(n, OUT_CHANNELS, dtype=torch.float32, device=F.device)
         status = torch.empty(N_STATUS, dtype=torch.int32, device=F.device)
-        forward_raw(coords, feat, batch, params, ws, out, status)
-        sizes = check_status(status)
+        forward_raw(coords, feat, batch, params, ws, out, status, self.precision)
+        sizes = check_status(status, self.precision)
         res = SparseTensor(out, coordinates=coords)
         res._batch_size = batch
         if not debug:

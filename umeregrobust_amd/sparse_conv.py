@@ -113,11 +113,16 @@ def _rows(t, what):
     return t
 
 
-def conv_raw(x, kernel, maps, table, transpose=False, mirror=False):
+def conv_raw(x, kernel, maps, table, transpose=False, mirror=False, precision="f32"):
     """out[o] = sum_k x[nbr_table(o, k)] @ M[k], M = kernel, or with `transpose` M[k'] = kernel[k]^T (k' = 26 - k if `mirror`):
-    x f32 [rows of in_level(table), C] -> [rows of out_level(table), C']; kernel [27, C, C'] ([27, C', C] with `transpose`)"""
+    x f32 [rows of in_level(table), C] -> [rows of out_level(table), C']; kernel [27, C, C'] ([27, C', C] with `transpose`).
+    precision="f16" (include/umereg_featnet_f16.h; forward only, not differentiable): x and the kernel rounded to f16, sums in
+    f32, one chain over all channels as in the fused f16 forward; table -1 with a [C, C'] kernel is the 1x1 layer over level 0."""
+    _models.check_precision(precision)
     lib = load_native()
     x = _rows(x, "input")
+    if precision == "f16":
+        return _conv_f16(lib, x, kernel, maps, table, transpose, mirror)
     K, cin, cout = kernel.shape
     if transpose:
         cin, cout = cout, cin
@@ -135,6 +140,29 @@ def conv_raw(x, kernel, maps, table, transpose=False, mirror=False):
                                               x.data_ptr() + 4 * s * step, x.stride(0), kernel.data_ptr() + 4 * s * 27 * step * cout, step,
                                               cout, maps.ones.data_ptr(), maps.zeros.data_ptr(), out.data_ptr(), cout, int(s > 0),
                                               _stream(x.device)), "sparse_conv")
+    return out
+
+
+def _conv_f16(lib, x, kernel, maps, table, transpose, mirror):
+    if kernel.dim() == 2:
+        if table != -1 or transpose:
+            raise ValueError("sparse_conv: a [C_in, C_out] kernel is the 1x1 layer: table -1, no transpose")
+        (cin, cout), rows_in = kernel.shape, maps.sizes[0]
+        rows_out = rows_in
+    else:
+        if not 0 <= table < N_TABLES:
+            raise ValueError(f"sparse_conv: table {table} outside [0, {N_TABLES})")
+        K, cin, cout = kernel.shape
+        if transpose:
+            cin, cout = cout, cin
+        rows_in, rows_out = maps.sizes[in_level(table)], maps.sizes[out_level(table)]
+    if x.shape != (rows_in, cin):
+        raise ValueError(f"sparse_conv: table {table} reads [{rows_in}, {cin}] rows, got {tuple(x.shape)}")
+    kernel = repack_raw(kernel, True, mirror, cin) if transpose else kernel.contiguous()
+    out = torch.empty(rows_out, cout, dtype=torch.float32, device=x.device)
+    _lib.check(lib.umereg_sparse_conv_f16(maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, table, x.data_ptr(),
+                                          x.stride(0), kernel.data_ptr(), cin, cout, maps.ones.data_ptr(), maps.zeros.data_ptr(),
+                                          out.data_ptr(), cout, 0, _stream(x.device)), "sparse_conv_f16")
     return out
 
 
