@@ -18,7 +18,8 @@
  * its size (umereg_featnet_workspace_bytes), its debug buffers (umereg_featnet_buffer) and `status` are those of
  * umereg_featnet.h and serve both precisions.
  *
- * Inference only: the training path (umereg_sparse_conv.h) has no f16 form. */
+ * The entry points here are inference's; the f16-operand form of the training path (umereg_sparse_conv.h) is
+ * umereg_sparse_conv_f16.h. */
 #ifndef UMEREG_FEATNET_F16_H
 #define UMEREG_FEATNET_F16_H
 

@@ -23,6 +23,9 @@ the same products) and, with `--stats-csv`, the split of a profiled run into ker
     python tools/featnet_time.py --train [--batch B] --stats-csv DIR/train_kernel_stats.csv >> profiles/featnet/featnet_time.jsonl
 
 (`--profile-steps N`: N forward + backward passes and nothing else, no timing: the run to put under the profiler.)
+`--train --train-precision f16`: the same with ResUNetSmall2(trainable=True, train_precision="f16") (f16 operands in the
+layer-wise forward and in both gradients, include/umereg_sparse_conv_f16.h); the line carries a "train_precision" key, and
+the peak fraction stays relative to the fp32 matrix peak.
 """
 import argparse
 import json
@@ -80,8 +83,8 @@ def flop_counts(masks, levels, info):
 
 
 # kernel groups of a profiled training run (rocprofv3 kernel_stats.csv, by kernel name)
-GROUPS = (("conv_forward_and_input_gradient", ("fn_conv_kernel", "fn_conv1_kernel")),
-          ("weight_gradient", ("wg_mfma_kernel", "wg_c1_kernel", "wg_reduce_kernel")),
+GROUPS = (("conv_forward_and_input_gradient", ("fn_conv_kernel", "fn_conv1_kernel", "fn_conv_f16_kernel")),
+          ("weight_gradient", ("wg_mfma_kernel", "wg_c1_kernel", "wg_reduce_kernel", "wg_f16_kernel", "wg_f16_reduce_kernel")),
           ("repack", ("wg_repack_kernel",)))
 
 
@@ -114,7 +117,7 @@ def train_mode(a, dev):
     coords = torch.from_numpy(np.concatenate(clouds)).to(dev)
     n = coords.shape[0]
     torch.manual_seed(a.seed)
-    m = models.ResUNetSmall2(in_channels=1, out_channels=32, trainable=True).to(dev)
+    m = models.ResUNetSmall2(in_channels=1, out_channels=32, trainable=True, train_precision=a.train_precision).to(dev)
     st = SparseTensor(torch.ones(n, 1, device=dev), coordinates=coords)
     st._batch_size = a.batch
     G = torch.randn(n, 32, device=dev)
@@ -163,7 +166,7 @@ def train_mode(a, dev):
     masks = masks.reshape(-1)[:13 * n].cpu().numpy().view(np.uint32).reshape(13, n)
     useful, _ = flop_counts(masks, levels, models.layer_info())
     wgrad_flop = float(sum(u for (mp, _), u in zip(LAYER_MAPS, useful) if mp is not None))
-    line = dict(tool="featnet_time", mode="train", config=a.config, batch=a.batch, n=n, levels=levels, iters=a.iters,
+    line = dict(tool="featnet_time", mode="train", train_precision=a.train_precision, config=a.config, batch=a.batch, n=n, levels=levels, iters=a.iters,
                 ms_per_call=dict(fused_eval_forward=round(ms_fused, 4), layerwise_forward=round(ms_fwd, 4),
                                  forward_backward=round(ms_step, 4), backward=round(ms_step - ms_fwd, 4)),
                 wgrad_useful_gflop=round(wgrad_flop / 1e9, 3))
@@ -184,6 +187,8 @@ def main(argv=None):
     ap.add_argument("--profile-steps", type=int, default=0, help="--train: run N forward + backward passes only (for the profiler)")
     ap.add_argument("--stats-csv", default=None, help="--train: rocprofv3 kernel_stats.csv of a --profile-steps run to fold in")
     ap.add_argument("--stats-steps", type=int, default=5, help="--train: the --profile-steps of that run")
+    ap.add_argument("--train-precision", default="f32", choices=list(models.PRECISIONS),
+                    help="--train: operand precision of the layer-wise forward and backward")
     ap.add_argument("--config", default="KT", choices=["KT", "NS"])
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)

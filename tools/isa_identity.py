@@ -73,6 +73,12 @@ def _short(sym):
     if not m:
         return sym
     n, at = int(m.group(1)), m.end()
+    if sym[at:at + n] == "_GLOBAL__N_1":          # a kernel of the unit's anonymous namespace: its own name comes next
+        m = re.match(r"(\d+)", sym[at + n:])
+        if not m:
+            return sym
+        at += n + m.end()
+        n = int(m.group(1))
     name, rest = sym[at:at + n], sym[at + n:]
     if not rest.startswith("I"):
         return name

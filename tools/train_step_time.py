@@ -3,6 +3,10 @@ r = 5, 256 UME samples, 512 point-wise samples.
 
     python tools/train_step_time.py [--points 50000] [--steps 7] [--warmup 3] [--out profiles/train/train_step_time.jsonl]
     python tools/train_step_time.py --device-collate          # only the "device_collate" lines below
+    python tools/train_step_time.py --phases-only [--train-precision f16]      # only the "phases" lines
+
+`--train-precision f16`: the network of the "phases" lines is ResUNetSmall2(trainable=True, train_precision="f16") (f16 operands
+in its forward and backward, include/umereg_sparse_conv_f16.h); every "phases" line carries a "train_precision" key.
 
 Three kinds of lines (JSON, appended to --out):
   * "phases": per-phase medians of one training step.  Device phases are timed with events on the stream after warm-up
@@ -70,7 +74,7 @@ class timed:
         self.b.record()
 
 
-def step_phases(points, batch, steps, warmup, dev):
+def step_phases(points, batch, steps, warmup, dev, train_precision="f32"):
     from umeregrobust_amd import train_coloring as tc
     from umeregrobust_amd.datasets.kitti_dataset import augmented_item, batch_collate_fn_dset, read_cached_pair, write_cached_pair
     from umeregrobust_amd.loss import MyInfoNCELossNoSeg
@@ -84,7 +88,7 @@ def step_phases(points, batch, steps, warmup, dev):
         write_cached_pair(paths[-1], synth_train_item(500 + i, N=points, device=dev))
     torch.manual_seed(0)
     rng = np.random.RandomState(0)
-    model = ResUNetSmall2(in_channels=1, out_channels=32, trainable=True).to(dev).train()
+    model = ResUNetSmall2(in_channels=1, out_channels=32, trainable=True, train_precision=train_precision).to(dev).train()
     pw = MyInfoNCELossNoSeg(num_samples=args.num_pw_samples, tau=args.tau, neg_euclid_dist=tc.NEG_EUCLID_DIST)
     opt = torch.optim.Adam(model.parameters(), lr=args.lr, weight_decay=0.0)
     ctx = tc.TrainContext(args)
@@ -125,7 +129,7 @@ def step_phases(points, batch, steps, warmup, dev):
     per_item = {"aug_to_device": 2, "aug_thinning": 2, "aug_grid_points": 2, "aug_matches": 1, "aug_to_host": 1, "item_read_host": 1,
                 "aug_item_wall_host": 1}
     per_step = {k: round(v * per_item.get(k, 0) * batch, 4) if k in per_item else v for k, v in med.items()}
-    return {"kind": "phases", "points": points, "batch": batch, "steps": steps, "warmup": warmup, "collated_src_tgt_matches": n_pts,
+    return {"kind": "phases", "train_precision": train_precision, "points": points, "batch": batch, "steps": steps, "warmup": warmup, "collated_src_tgt_matches": n_pts,
             "keypoints": int(su.shape[1]), "median_ms_per_call": med, "median_ms_per_step": per_step}
 
 
@@ -271,6 +275,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "train", "train_step_time.jsonl"))
     ap.add_argument("--device-collate", action="store_true", help="only the host / device / device_late comparison of the collate")
     ap.add_argument("--rounds", type=int, default=2, help="turns per form of the --device-collate comparison")
+    ap.add_argument("--train-precision", default="f32", choices=["f32", "f16"], help="operand precision of the network in the phases lines")
+    ap.add_argument("--phases-only", action="store_true", help="skip the match-kernel comparison")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -282,13 +288,13 @@ def main():
                 f.write(json.dumps(line) + "\n")
                 f.flush()
             return
-        for hard in (False, True):
+        for hard in () if a.phases_only else (False, True):
             line = match_compare(a.points, a.match_reps, 10, dev, hard)
             print(json.dumps(line), flush=True)
             f.write(json.dumps(line) + "\n")
             f.flush()
         for batch in a.batches:
-            line = step_phases(a.points, batch, a.steps, a.warmup, dev)
+            line = step_phases(a.points, batch, a.steps, a.warmup, dev, a.train_precision)
             print(json.dumps(line), flush=True)
             f.write(json.dumps(line) + "\n")
             f.flush()

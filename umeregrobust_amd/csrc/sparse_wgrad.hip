@@ -12,35 +12,15 @@
 // chain of a (k, tile, segment) is the segment's active rows in ascending order, whatever the queue's chunking (a padded
 // pair adds x * 0 = +0).  Partial blocks go to the caller's scratch, [segment][27][C_in][C_out]; wg_reduce_kernel sums the
 // segments that hold rows in ascending order.  No atomics; every scratch word that is read was written by this call.
-// C_in = 1 (conv1) has a scalar kernel of the same decomposition.
-#include "sparse.h"
-#include "umereg_sparse_conv.h"
+// C_in = 1 (conv1) has a scalar kernel of the same decomposition.  The segmentation (wg_plan) is in sparse_wgrad.h: the f16-operand
+// form of this kernel (sparse_wgrad_f16.hip) cuts the rows the same way.
+#include "sparse_wgrad.h"
 
 namespace umereg {
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct WgPlan {
-    int rps, segments;      // rows per segment, segments over [0, n)
-    size_t block;           // floats of one [27][cin][cout] block
-};
-
-// depends on n, cin, cout only: at most 64 segments and about 64 MB of partial blocks, at least 1024 rows per segment
-WgPlan wg_plan(int n, int cin, int cout)
-{
-    WgPlan p;
-    p.block = (size_t)kFnVol * cin * cout;
-    size_t smax = ((size_t)64 << 20) / (p.block * 4);
-    if (smax < 1) smax = 1;
-    if (smax > UMEREG_SPARSE_CONV_MAX_SEGMENTS) smax = UMEREG_SPARSE_CONV_MAX_SEGMENTS;
-    size_t rps = align_up(((size_t)n + smax - 1) / smax, 64);
-    if (rps < 1024) rps = 1024;
-    p.rps = (int)rps;
-    p.segments = (int)(((size_t)n + rps - 1) / rps);
-    return p;
-}
 
 struct WgArgs {
     const float* in;            // input rows [., ld_in]
@@ -180,12 +160,6 @@ __global__ __launch_bounds__(256) void wg_repack_kernel(const float* __restrict_
     const int c = e % C, rl = (e / C) % slice, kp = (e / (C * slice)) % kFnVol, s = e / (C * slice * kFnVol);
     const int r = s * slice + rl, k = mirror ? kFnVol - 1 - kp : kp;
     out[e] = transpose ? W[((size_t)k * cin + c) * cout + r] : W[((size_t)k * cin + r) * cout + c];
-}
-
-bool wg_channels_ok(int cin, int cout)
-{
-    return (cin == 1 || (cin > 0 && cin % 32 == 0 && cin <= UMEREG_SPARSE_CONV_MAX_CH)) && cout > 0 && cout % 32 == 0 &&
-           cout <= UMEREG_SPARSE_CONV_MAX_CH;
 }
 
 template <int BI, int BO>

@@ -39,7 +39,14 @@ call and running-stat updates in train mode, running statistics in eval mode), r
 `ResUNetSmall2(..., precision="f16")` (include/umereg_featnet_f16.h; the default is "f32"): the fused call with the operands of
 the seventeen 27-offset convolutions after conv1 and of mlp1 rounded to f16 (round to nearest even) and every sum, the
 epilogues and all stored activations in f32 -- deterministic like the f32 path.  Inference only: train mode and a forward
-that needs gradients raise, there is no silent fallback to f32.  An activation beyond the f16 range raises ValueError."""
+that needs gradients raise, there is no silent fallback to f32.  An activation beyond the f16 range raises ValueError.
+
+`ResUNetSmall2(..., trainable=True, train_precision="f16")` (include/umereg_sparse_conv_f16.h; the default is "f32"): the
+operand precision of the layer-wise path, whatever `precision` is -- the seventeen 27-offset convolutions after conv1 and mlp1
+run `sparse_conv(..., precision="f16")` / `linear(..., precision="f16")`: f16 operands in the forward and in both gradients,
+f32 sums, parameters, gradients and saved activations; conv1, `final`, batch norm and the rest stay f32.  Deterministic.  No
+range check per layer (it would synchronise): an activation beyond +-65504 reaches the next layer as infinity and the loss as
+a non-finite value, which the training driver names where it reads the loss."""
 import ctypes
 
 import torch
@@ -196,10 +203,16 @@ class ResUNetSmall2(nn.Module):
     STRIDES = [1, 2, 2, 2, 3]
 
     def __init__(self, in_channels=1, out_channels=32, bn_momentum=0.1, normalize_feature=True, D=3, trainable=False,
-                 precision="f32"):
+                 precision="f32", train_precision="f32"):
         super().__init__()
         self.trainable = bool(trainable)
         self.precision = check_precision(precision)
+        if train_precision not in PRECISIONS:
+            raise ValueError(f"train_precision must be one of {PRECISIONS}, got {train_precision!r}")
+        if train_precision != "f32" and not self.trainable:
+            raise ValueError(f"ResUNetSmall2(train_precision={train_precision!r}) is the operand precision of the layer-wise path: "
+                             "it needs trainable=True")
+        self.train_precision = train_precision
         if (in_channels, out_channels, bool(normalize_feature), D) != (1, OUT_CHANNELS, True, 3):
             raise ValueError("the HIP network is built for in_channels=1, out_channels=32, normalize_feature=True, D=3 "
                              "(the configuration of reference evaluate.py:163)")
@@ -266,10 +279,11 @@ class ResUNetSmall2(nn.Module):
         halves of every level's concatenation, block5's output and mlp1's output (see include/umereg_featnet.h)."""
         F, C = x.F, x.C
         needs_grad = torch.is_grad_enabled() and (F.requires_grad or any(p.requires_grad for p in self.parameters()))
-        if self.precision != "f32" and (self.training or needs_grad):
+        if self.precision != "f32" and self.train_precision == "f32" and (self.training or needs_grad):
             raise RuntimeError(f"ResUNetSmall2(precision={self.precision!r}) is inference only: the layer-wise path (train mode, "
                                "or a forward that needs gradients) is f32, and there is no silent fallback to it; call .eval() "
-                               "under torch.no_grad(), or build the model with precision='f32'")
+                               "under torch.no_grad(), or build the model with precision='f32' (to train with f16 operands: "
+                               "trainable=True, train_precision='f16')")
         if not self.trainable:
             if self.training:
                 raise RuntimeError("ResUNetSmall2 runs forward only with eval-mode batch norm: call .eval() first "
@@ -334,23 +348,24 @@ class ResUNetSmall2(nn.Module):
                     raise ValueError(f"ResUNetSmall2: level {l} of this input has a single row, and train-mode batch norm needs "
                                      "more than one value per channel (use a larger cloud or .eval())")
         relu = torch.relu
+        tp = self.train_precision                     # (conv1, C_in = 1, stays f32 inside sparse_conv)
 
         def block(h, l, blk):
-            return relu(blk.norm1.bn(sc.sparse_conv(h, blk.conv1.kernel, maps, l)) + h)
+            return relu(blk.norm1.bn(sc.sparse_conv(h, blk.conv1.kernel, maps, l, precision=tp)) + h)
 
         skips = []
         h = F.detach().to(torch.float32)
         for l in range(5):
             conv, norm, blk = getattr(self, f"conv{l + 1}"), getattr(self, f"norm{l + 1}"), getattr(self, f"block{l + 1}")
-            h = block(norm.bn(sc.sparse_conv(h, conv.kernel, maps, 0 if l == 0 else 5 + l - 1)), l, blk)
+            h = block(norm.bn(sc.sparse_conv(h, conv.kernel, maps, 0 if l == 0 else 5 + l - 1, precision=tp)), l, blk)
             skips.append(h)
         s4 = h
         cats = [None] * 4
         for l in range(3, -1, -1):
             conv, norm, blk = getattr(self, f"conv{l + 1}_tr"), getattr(self, f"norm{l + 1}_tr"), getattr(self, f"block{l + 1}_tr")
-            tr = block(norm.bn(sc.sparse_conv(h, conv.kernel, maps, 9 + l)), l, blk)
+            tr = block(norm.bn(sc.sparse_conv(h, conv.kernel, maps, 9 + l, precision=tp)), l, blk)
             h = cats[l] = torch.cat([tr, skips[l]], dim=1)
-        hidden = relu(sc.linear(h, self.mlp1.kernel))
+        hidden = relu(sc.linear(h, self.mlp1.kernel, precision=tp, maps=maps))
         o = sc.linear(hidden, self.final.kernel) + self.final.bias
         o = o / o.norm(dim=1, keepdim=True)
         inv = torch.empty_like(maps.perm)

@@ -10,7 +10,14 @@ every level are in the library's own order; `maps.perm[j]` is the input row of l
 Backward: the input gradient is the same convolution kernel over the ADJOINT table with the kernel's slices transposed
 (self l: the same table with the offsets mirrored, k -> 26 - k; strided 5 + l <-> transposed 9 + l, same k), skipped when
 the input needs no gradient; the weight gradient dW[k] = sum_o x[nbr(o, k)]^T dY[o] is the library's deterministic
-segmented MFMA kernel.  Everything runs on the current stream and nothing waits for the device."""
+segmented MFMA kernel.  Everything runs on the current stream and nothing waits for the device.
+
+precision="f16" (include/umereg_sparse_conv_f16.h; opt-in, the default is "f32"): the operands of the three matrix products are
+rounded to f16 (to nearest even) and every sum stays f32.  Forward: `conv_raw(..., precision="f16")`.  Backward: the output
+gradient is scaled by 2^e (`grad_scale`: e computed on the device, no host sync) so that its largest magnitude lies in
+[2^14, 2^15) before it is rounded; the scaled gradient feeds both gradients and 2^-e is applied to the results (the input
+gradient's epilogue scale, one multiplication of dW).  The saved input is the f32 the forward rounded, so dW is the exact
+straight-through gradient of the forward.  Inputs, kernels, outputs and gradients are f32 tensors in both precisions."""
 import ctypes
 
 import torch
@@ -32,6 +39,11 @@ SPARSE_CONV_SIGNATURES = {
                                              c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
+# name -> (restype, argtypes); mirrors include/umereg_sparse_conv_f16.h one to one
+SPARSE_CONV_F16_SIGNATURES = {
+    "umereg_sparse_conv_wgrad_f16": SPARSE_CONV_SIGNATURES["umereg_sparse_conv_wgrad_f32"],
+}
+
 N_TABLES, MAX_CH = 13, 256
 # input channels per launch of the plain convolution: a longer contraction runs as slices accumulated in order (two-level
 # summation; one chain over 27 x 256 products carries about twice the rounding error of eight chains over 27 x 32)
@@ -39,10 +51,11 @@ SLICE = 32
 
 
 def load_native():
-    """libumereg.so with the entry points of include/umereg_sparse_conv.h (and of umereg_featnet.h) typed (raises without the
-    built library)."""
+    """libumereg.so with the entry points of include/umereg_sparse_conv.h and umereg_sparse_conv_f16.h (and of umereg_featnet.h)
+    typed (raises without the built library)."""
     _models.load_native()
-    return _lib.load_typed(SPARSE_CONV_SIGNATURES)
+    _lib.load_typed(SPARSE_CONV_SIGNATURES)
+    return _lib.load_typed(SPARSE_CONV_F16_SIGNATURES)
 
 
 def out_level(table):
@@ -113,16 +126,20 @@ def _rows(t, what):
     return t
 
 
-def conv_raw(x, kernel, maps, table, transpose=False, mirror=False, precision="f32"):
+def conv_raw(x, kernel, maps, table, transpose=False, mirror=False, precision="f32", scale=None):
     """out[o] = sum_k x[nbr_table(o, k)] @ M[k], M = kernel, or with `transpose` M[k'] = kernel[k]^T (k' = 26 - k if `mirror`):
     x f32 [rows of in_level(table), C] -> [rows of out_level(table), C']; kernel [27, C, C'] ([27, C', C] with `transpose`).
     precision="f16" (include/umereg_featnet_f16.h; forward only, not differentiable): x and the kernel rounded to f16, sums in
-    f32, one chain over all channels as in the fused f16 forward; table -1 with a [C, C'] kernel is the 1x1 layer over level 0."""
+    f32, one chain over all channels as in the fused f16 forward; table -1 with a [C, C'] kernel is the 1x1 layer over level 0
+    (`transpose`: the kernel is [C', C]); `scale` (f16 only): f32 [>= C'] on the device, the epilogue's factor per output channel
+    instead of ones."""
     _models.check_precision(precision)
     lib = load_native()
     x = _rows(x, "input")
     if precision == "f16":
-        return _conv_f16(lib, x, kernel, maps, table, transpose, mirror)
+        return _conv_f16(lib, x, kernel, maps, table, transpose, mirror, scale)
+    if scale is not None:
+        raise ValueError("sparse_conv: `scale` goes with precision='f16'")
     K, cin, cout = kernel.shape
     if transpose:
         cin, cout = cout, cin
@@ -143,12 +160,15 @@ def conv_raw(x, kernel, maps, table, transpose=False, mirror=False, precision="f
     return out
 
 
-def _conv_f16(lib, x, kernel, maps, table, transpose, mirror):
+def _conv_f16(lib, x, kernel, maps, table, transpose, mirror, scale=None):
     if kernel.dim() == 2:
-        if table != -1 or transpose:
-            raise ValueError("sparse_conv: a [C_in, C_out] kernel is the 1x1 layer: table -1, no transpose")
+        if table != -1:
+            raise ValueError("sparse_conv: a [C_in, C_out] kernel is the 1x1 layer: table -1")
+        if transpose:
+            kernel = kernel.t()
         (cin, cout), rows_in = kernel.shape, maps.sizes[0]
         rows_out = rows_in
+        transpose = False
     else:
         if not 0 <= table < N_TABLES:
             raise ValueError(f"sparse_conv: table {table} outside [0, {N_TABLES})")
@@ -160,8 +180,12 @@ def _conv_f16(lib, x, kernel, maps, table, transpose, mirror):
         raise ValueError(f"sparse_conv: table {table} reads [{rows_in}, {cin}] rows, got {tuple(x.shape)}")
     kernel = repack_raw(kernel, True, mirror, cin) if transpose else kernel.contiguous()
     out = torch.empty(rows_out, cout, dtype=torch.float32, device=x.device)
+    if scale is None:
+        scale = maps.ones
+    elif scale.dtype != torch.float32 or scale.device != x.device or scale.dim() != 1 or scale.numel() < cout or not scale.is_contiguous():
+        raise ValueError(f"sparse_conv: scale must be contiguous f32 [>= {cout}] on {x.device}")
     _lib.check(lib.umereg_sparse_conv_f16(maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, table, x.data_ptr(),
-                                          x.stride(0), kernel.data_ptr(), cin, cout, maps.ones.data_ptr(), maps.zeros.data_ptr(),
+                                          x.stride(0), kernel.data_ptr(), cin, cout, scale.data_ptr(), maps.zeros.data_ptr(),
                                           out.data_ptr(), cout, 0, _stream(x.device)), "sparse_conv_f16")
     return out
 
@@ -192,8 +216,11 @@ def repack_raw(kernel, transpose, mirror, slice):
     return out
 
 
-def wgrad_raw(x, dy, maps, table):
-    """dW [27, C_in, C_out] = sum_o x[nbr_table(o, k)]^T dy[o]; x [rows of in_level(table), C_in] (C_in = 1 included)"""
+def wgrad_raw(x, dy, maps, table, precision="f32"):
+    """dW [27, C_in, C_out] = sum_o x[nbr_table(o, k)]^T dy[o]; x [rows of in_level(table), C_in] (C_in = 1 included).
+    precision="f16" (include/umereg_sparse_conv_f16.h): x and dy rounded to f16, sums in f32, C_in a multiple of 32; dy as it is
+    given -- the caller scales it (`grad_scale`) and unscales the result."""
+    _models.check_precision(precision)
     lib = load_native()
     dy = _rows(dy, "output gradient")
     if x.shape[1] == 1:
@@ -208,18 +235,43 @@ def wgrad_raw(x, dy, maps, table):
         raise ValueError(f"sparse_conv_wgrad: channels {cin} -> {cout} not supported")
     scratch = maps.scratch(need)
     dw = torch.empty(27, cin, cout, dtype=torch.float32, device=x.device)
-    _lib.check(lib.umereg_sparse_conv_wgrad_f32(maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, table, x.data_ptr(),
-                                                x.stride(0), cin, dy.data_ptr(), dy.stride(0), cout, dw.data_ptr(), scratch.data_ptr(),
-                                                scratch.numel(), _stream(x.device)), "sparse_conv_wgrad")
+    fn = lib.umereg_sparse_conv_wgrad_f16 if precision == "f16" else lib.umereg_sparse_conv_wgrad_f32
+    _lib.check(fn(maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, table, x.data_ptr(), x.stride(0), cin,
+                  dy.data_ptr(), dy.stride(0), cout, dw.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream(x.device)),
+               "sparse_conv_wgrad" if precision == "f32" else "sparse_conv_wgrad_f16")
     return dw
+
+
+E_MAX = 126     # |e| of grad_scale is at most this: 2^e and 2^-e are normal f32 numbers
+
+
+def _pow2(e):
+    """2^e as f32 for an int32 tensor e in [-126, 127], by the exponent field (exact; no pow())"""
+    return ((e + 127) << 23).view(torch.float32)
+
+
+def grad_scale(dy):
+    """The backward scaling of include/umereg_sparse_conv_f16.h for an output gradient dy (f32): -> (e, 2^e, 2^-e) as 0-dim
+    tensors on dy's device (int32, f32, f32), e = 14 - floor(log2(max |dy|)) so that max |dy 2^e| lies in [2^14, 2^15); e = 0 if
+    max |dy| is zero or not finite.  Nothing is read back to the host.  e is held to +-126 (it exceeds that only for
+    max |dy| < 2^-112, where the scaled maximum then stays below 2^14)."""
+    if dy.numel():
+        lo, hi = torch.aminmax(dy.detach())          # one pass, no |dy| temporary; a NaN comes through both
+        m = torch.maximum(hi, -lo)
+    else:
+        m = torch.zeros((), dtype=dy.dtype, device=dy.device)
+    _, ex = torch.frexp(m)                           # m = mantissa 2^ex, mantissa in [0.5, 1): floor(log2 m) = ex - 1
+    ok = torch.isfinite(m) & (m > 0)
+    e = torch.where(ok, 15 - ex.to(torch.int32), torch.zeros_like(ex, dtype=torch.int32)).clamp(-E_MAX, E_MAX).to(torch.int32)
+    return e, _pow2(e), _pow2(-e)
 
 
 class _SparseConv(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, kernel, maps, table):
-        ctx.maps, ctx.table = maps, table
+    def forward(ctx, x, kernel, maps, table, precision="f32"):
+        ctx.maps, ctx.table, ctx.precision = maps, table, precision
         ctx.save_for_backward(x, kernel)
-        return conv_raw(x, kernel.detach(), maps, table)
+        return conv_raw(x, kernel.detach(), maps, table, precision=precision)
 
     @staticmethod
     def backward(ctx, dy):
@@ -227,12 +279,22 @@ class _SparseConv(torch.autograd.Function):
         maps, table = ctx.maps, ctx.table
         dy = dy.contiguous()
         dx = dw = None
+        if ctx.precision == "f16":
+            # include/umereg_sparse_conv_f16.h: one power-of-two scale per layer, computed on the device; dy 2^e feeds both gradients
+            _, up, down = grad_scale(dy)
+            dys = dy * up
+            if ctx.needs_input_grad[0]:
+                adj, mirror = adjoint(table)
+                dx = conv_raw(dys, kernel.detach(), maps, adj, transpose=True, mirror=mirror, precision="f16", scale=maps.ones * down)
+            if ctx.needs_input_grad[1]:
+                dw = wgrad_raw(x, dys, maps, table, precision="f16") * down
+            return dx, dw, None, None, None
         if ctx.needs_input_grad[0]:
             adj, mirror = adjoint(table)
             dx = conv_raw(dy, kernel.detach(), maps, adj, transpose=True, mirror=mirror)
         if ctx.needs_input_grad[1]:
             dw = wgrad_raw(x, dy, maps, table)
-        return dx, dw, None, None
+        return dx, dw, None, None, None
 
 
 class _SparseConv1(torch.autograd.Function):
@@ -251,10 +313,12 @@ class _SparseConv1(torch.autograd.Function):
         return None, dw, None
 
 
-def sparse_conv(x, kernel, maps, table):
+def sparse_conv(x, kernel, maps, table, precision="f32"):
     """Differentiable sparse convolution over table `table` of `maps`.  x: f32 [rows of the table's input level, C_in] in the
     level's row order -- for a [27, 1, 32] kernel (conv1, table 0): [n, 1] in INPUT row order, and it may not require grad;
-    kernel: [27, C_in, C_out].  -> f32 [rows of the table's output level, C_out]."""
+    kernel: [27, C_in, C_out].  -> f32 [rows of the table's output level, C_out].  precision="f16": f16 operands in the forward
+    and in both gradients (module docstring); a C_in = 1 kernel (conv1) stays f32 either way."""
+    _models.check_precision(precision)
     if not 0 <= table < N_TABLES:
         raise ValueError(f"sparse_conv: table {table} outside [0, {N_TABLES})")
     if x.device.type != "cuda" or kernel.device.type != "cuda":
@@ -268,7 +332,15 @@ def sparse_conv(x, kernel, maps, table):
             raise RuntimeError("sparse_conv: conv1 has no input gradient (the network's input features are constants); "
                                "detach the input features")
         return _SparseConv1.apply(x, kernel, maps)
-    return _SparseConv.apply(x, kernel, maps, table)
+    return _SparseConv.apply(x, kernel, maps, table, precision)
+
+
+def _block_wgrad(x, dy):
+    n, r = x.shape[0], _Linear.ROWS          # x^T dy summed in blocks of ROWS rows, then over the blocks
+    pad = (-n) % r
+    xp = torch.nn.functional.pad(x, (0, 0, 0, pad)).view(-1, r, x.shape[1])
+    dp = torch.nn.functional.pad(dy, (0, 0, 0, pad)).view(-1, r, dy.shape[1])
+    return torch.bmm(xp.transpose(1, 2), dp).sum(dim=0)
 
 
 class _Linear(torch.autograd.Function):
@@ -286,16 +358,42 @@ class _Linear(torch.autograd.Function):
     def backward(ctx, dy):
         x, W = ctx.saved_tensors
         dx = dy @ W.t() if ctx.needs_input_grad[0] else None
-        dw = None
-        if ctx.needs_input_grad[1]:
-            n, r = x.shape[0], _Linear.ROWS
-            pad = (-n) % r
-            xp = torch.nn.functional.pad(x, (0, 0, 0, pad)).view(-1, r, x.shape[1])
-            dp = torch.nn.functional.pad(dy, (0, 0, 0, pad)).view(-1, r, dy.shape[1])
-            dw = torch.bmm(xp.transpose(1, 2), dp).sum(dim=0)
+        dw = _block_wgrad(x, dy) if ctx.needs_input_grad[1] else None
         return dx, dw
 
 
-def linear(x, W):
-    """x [rows, C_in] @ W [C_in, C_out] with a block-summed weight gradient (the 1x1 layers of the network)"""
+class _LinearF16(torch.autograd.Function):
+    """mlp1 with f16 operands (include/umereg_sparse_conv_f16.h): forward and input gradient are the HIP convolution with
+    table -1 (x and W, the scaled dy and W^T rounded to f16; sums f32); the weight gradient stays `_Linear`'s f32 block sum."""
+
+    @staticmethod
+    def forward(ctx, x, W, maps):
+        ctx.maps = maps
+        ctx.save_for_backward(x, W)
+        return conv_raw(x, W.detach(), maps, -1, precision="f16")
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, W = ctx.saved_tensors
+        dy = dy.contiguous()
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            _, up, down = grad_scale(dy)
+            dx = conv_raw(dy * up, W.detach(), ctx.maps, -1, transpose=True, precision="f16", scale=ctx.maps.ones * down)
+        if ctx.needs_input_grad[1]:
+            dw = _block_wgrad(x, dy)
+        return dx, dw, None
+
+
+def linear(x, W, precision="f32", maps=None):
+    """x [rows, C_in] @ W [C_in, C_out] with a block-summed weight gradient (the 1x1 layers of the network).  precision="f16"
+    (mlp1): x [rows of level 0 of `maps`, C_in], operands of the forward and of the input gradient rounded to f16, channel counts
+    multiples of 32; the weight gradient stays the f32 block sum."""
+    _models.check_precision(precision)
+    if precision == "f16":
+        if maps is None:
+            raise ValueError("linear: precision='f16' runs on the HIP convolution and needs the CoordinateMaps of its rows (maps=...)")
+        if x.device.type != "cuda" or W.device.type != "cuda":
+            raise RuntimeError("linear: CPU tensors given; umeregrobust_amd has no CPU fallback (move the input to the GPU)")
+        return _LinearF16.apply(x, W, maps)
     return _Linear.apply(x, W)

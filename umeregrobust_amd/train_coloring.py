@@ -181,6 +181,15 @@ class RunningSums:
         return self.v.get(k, 0.0)
 
 
+def check_loss_is_finite(values, model):
+    """Where a step's loss scalars are on the host: with train_precision='f16' the layer-wise path makes no range check of its own
+    (it would synchronise), so an activation beyond the f16 range shows here, as a non-finite loss -- name the cause."""
+    if getattr(model, "train_precision", "f32") == "f16" and not np.isfinite(values["total"]):
+        raise FloatingPointError(f"the training loss is {values['total']} with train_precision='f16': an activation or a gradient left "
+                                 "the f16 range (|x| > 65504 reaches the next layer as infinity); train this run with "
+                                 "train_precision='f32'")
+
+
 def train_one_epoch(epoch, data_loader, model, loss_func, optimizer, summary_writer, ctx, late_read=False):
     """The reference's train_one_epoch (train_coloring.py:20-93) with its globals in `ctx`.  Quirks kept: a batch without matches is
     dropped before the forward pass and one without UME keypoints after it (so batch-norm statistics have seen it), both before
@@ -206,6 +215,7 @@ def train_one_epoch(epoch, data_loader, model, loss_func, optimizer, summary_wri
         terms["total"].backward()
         optimizer.step()
         values = {k: float(v.detach()) for k, v in terms.items()}
+        check_loss_is_finite(values, model)
         sums.add(**values)
         for k in ("total", "pointwise", "ume", "reg"):
             if k in values:
@@ -246,6 +256,7 @@ def train_one_epoch_late_read(epoch, data_loader, model, loss_func, optimizer, s
         data = next(batches, None)                        # item read, augmentation, draws, collate: under the step just enqueued
         if launched is not None:
             values = {k: float(v) for k, v in launched.items()}
+            check_loss_is_finite(values, model)
             sums.add(**values)
             for k in ("total", "pointwise", "ume", "reg"):
                 if k in values:
@@ -418,12 +429,15 @@ def make_loaders(args, synthetic=0, synthetic_points=3000, device_collate=False)
     return mk(dset_train, True), mk(dset_valid, False)
 
 
-def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=None, device_collate=False, device_assignment=False):
+def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=None, device_collate=False, device_assignment=False,
+        train_precision="f32"):
     """train_coloring.py:263-437 -> the run directory.  Quirks kept: every "best" file stores the validation TOTAL loss; the
     UME and point-wise "best" follow the total (eval_one_epoch returns it three times); without the registration loss the validation
     registration loss is 0.0, so `best_reg_loss` (from inf) is written once, after the first epoch, and `best_mCHR` (from 0.0) never.
     device_collate: batches are collated on the device and the training loop reads its scalars one batch late (module docstring).
-    device_assignment: the validation epoch's Hungarian matching runs on the device (module docstring)."""
+    device_assignment: the validation epoch's Hungarian matching runs on the device (module docstring).
+    train_precision: "f32", or "f16" for f16 operands in the network's layer-wise path (models.py; f32 parameters, so checkpoints
+    are the same either way); a non-finite loss then raises FloatingPointError."""
     torch.manual_seed(args.random_seed)
     np.random.seed(args.random_seed)
     device = torch.device(args.device)
@@ -434,7 +448,7 @@ def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=
         run_name = os.path.basename(os.path.normpath(out_path))
     os.makedirs(out_path, exist_ok=True)
     dloader_train, dloader_valid = make_loaders(args, synthetic, synthetic_points, device_collate)
-    model = ResUNetSmall2(in_channels=1, out_channels=args.out_channels, trainable=True).to(device)
+    model = ResUNetSmall2(in_channels=1, out_channels=args.out_channels, trainable=True, train_precision=train_precision).to(device)
     point_wise_loss_fn = MyInfoNCELossNoSeg(num_samples=args.num_pw_samples, tau=args.tau, neg_euclid_dist=NEG_EUCLID_DIST)
     ctx = TrainContext(args)
     optimizer = optim.Adam(model.parameters(), lr=args.lr, weight_decay=WEIGHT_DECAY)
@@ -480,6 +494,8 @@ def main(argv=None):
                         help="collate on the GPU and read each step's scalars one batch late (same batches, same log)")
     parser.add_argument('--device-assignment', action='store_true',
                         help="solve the validation epoch's Hungarian matching on the GPU instead of with scipy on the host")
+    parser.add_argument('--train-precision', choices=['f32', 'f16'], default='f32',
+                        help="operand precision of the network's forward and backward matrix products (f32 sums and parameters)")
     cli = parser.parse_args(argv)
     over = {k: v for k, v in (("cache_data_path", cli.cache), ("num_epochs", cli.epochs), ("batch_size", cli.batch_size),
                               ("output_path", cli.output_path), ("resume_train_path", cli.resume)) if v is not None}
@@ -490,7 +506,7 @@ def main(argv=None):
         args.eval_num_kpts, args.batch_size = 32, min(args.batch_size, 2)
     print(f"Train {args.dataset} config: {cli.config_path or 'built-in defaults'}")
     out = run(args, synthetic=cli.synthetic, synthetic_points=cli.synthetic_points, device_collate=cli.device_collate,
-              device_assignment=cli.device_assignment)
+              device_assignment=cli.device_assignment, train_precision=cli.train_precision)
     print(f"run directory: {out}")
     return out
 
