@@ -84,7 +84,7 @@ def flop_counts(masks, levels, info):
 
 # kernel groups of a profiled training run (rocprofv3 kernel_stats.csv, by kernel name)
 GROUPS = (("conv_forward_and_input_gradient", ("fn_conv_kernel", "fn_conv1_kernel", "fn_conv_f16_kernel")),
-          ("weight_gradient", ("wg_mfma_kernel", "wg_c1_kernel", "wg_reduce_kernel", "wg_f16_kernel", "wg_f16_reduce_kernel")),
+          ("weight_gradient", ("wg_mfma_kernel", "wg_c1_kernel", "wg_reduce_kernel", "wg_f16_kernel")),
           ("repack", ("wg_repack_kernel",)))
 
 

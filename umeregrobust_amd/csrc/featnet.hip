@@ -332,6 +332,20 @@ __global__ __launch_bounds__(256) void fn_conv_f16_kernel(ConvArgsF16 args)
     if (args.range && out_of_range) atomicOr(args.range, UMEREG_FN_ERR_F16_RANGE);
 }
 
+// one convolution launch over at most `rows_bound` output rows: 64 x 64 tiles where C_out allows, else 128 x 32; `range` as ConvArgsF16
+int fn_launch_conv(const ConvArgs& a, bool f16, int32_t* range, int rows_bound, hipStream_t st)
+{
+    const bool wide = a.cout % 64 == 0;
+    const dim3 grid = wide ? dim3((rows_bound + 63) / 64, a.cout / 64) : dim3((rows_bound + 127) / 128, a.cout / 32);
+    const ConvArgsF16 h{a, range};
+    if (f16 && wide) hipLaunchKernelGGL((fn_conv_f16_kernel<64, 64>), grid, dim3(256), 0, st, h);
+    else if (f16) hipLaunchKernelGGL((fn_conv_f16_kernel<128, 32>), grid, dim3(256), 0, st, h);
+    else if (wide) hipLaunchKernelGGL((fn_conv_kernel<64, 64>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((fn_conv_kernel<128, 32>), grid, dim3(256), 0, st, a);
+    UMEREG_CHECK_LAUNCH(f16 ? "fn_conv_f16_kernel" : "fn_conv_kernel");
+    return UMEREG_OK;
+}
+
 struct Fwd {
     const float* params;
     FnParamOffsets po;
@@ -341,37 +355,19 @@ struct Fwd {
     hipStream_t st;
     bool f16;               // layers 1..18 on fn_conv_f16_kernel
 
-    const int* nbr(int m) const { return reinterpret_cast<const int*>(ws + w.off_nbr) + (size_t)m * w.n * kFnVol; }
-    const unsigned int* mask(int m) const { return reinterpret_cast<const unsigned int*>(ws + w.off_mask) + (size_t)m * w.n; }
     float* buf(size_t off) const { return reinterpret_cast<float*>(ws + off); }
 
-    // layer `i` over map `m` (-1: 1x1), output level `lo`: in (ld_in) -> out (ld_out), optional residual
-    int conv(int i, int m, int lo, const float* in, int ld_in, float* out, int ld_out, const float* res, int ld_res, bool relu) const
+    // layer `i` over map `m` (-1: 1x1): in (ld_in) -> out (ld_out), optional residual
+    int conv(int i, int m, const float* in, int ld_in, float* out, int ld_out, const float* res, int ld_res, bool relu) const
     {
         const FnLayer& L = kFnLayers[i];
+        const FnTable t = fn_table(ws, w, m);
         ConvArgs a;
         a.in = in, a.W = params + po.w[i], a.scale = params + po.scale[i], a.shift = params + po.scale[i] + L.cout;
-        a.res = res, a.out = out, a.nbr = m >= 0 ? nbr(m) : nullptr, a.mask = m >= 0 ? mask(m) : nullptr;
-        a.n_out = status + 1 + lo;
+        a.res = res, a.out = out, a.nbr = t.nbr, a.mask = t.mask, a.n_out = status + 1 + t.level;
         a.ld_in = ld_in, a.ld_res = ld_res, a.ld_out = ld_out, a.cin = L.cin, a.cout = L.cout, a.K = L.K, a.relu = relu ? 1 : 0;
-        if (f16) {
-            // the range check covers what a later f16 layer gathers: mlp1's output feeds `final`, which is f32
-            const ConvArgsF16 h{a, i < 18 ? status : nullptr};
-            if (L.cout % 64 == 0) {
-                hipLaunchKernelGGL((fn_conv_f16_kernel<64, 64>), dim3((w.n + 63) / 64, L.cout / 64), dim3(256), 0, st, h);
-            } else {
-                hipLaunchKernelGGL((fn_conv_f16_kernel<128, 32>), dim3((w.n + 127) / 128, L.cout / 32), dim3(256), 0, st, h);
-            }
-            UMEREG_CHECK_LAUNCH("fn_conv_f16_kernel");
-            return UMEREG_OK;
-        }
-        if (L.cout % 64 == 0) {
-            hipLaunchKernelGGL((fn_conv_kernel<64, 64>), dim3((w.n + 63) / 64, L.cout / 64), dim3(256), 0, st, a);
-        } else {
-            hipLaunchKernelGGL((fn_conv_kernel<128, 32>), dim3((w.n + 127) / 128, L.cout / 32), dim3(256), 0, st, a);
-        }
-        UMEREG_CHECK_LAUNCH("fn_conv_kernel");
-        return UMEREG_OK;
+        // the range check covers what a later f16 layer gathers: mlp1's output feeds `final`, which is f32
+        return fn_launch_conv(a, f16, i < 18 ? status : nullptr, w.n, st);
     }
 };
 
@@ -429,12 +425,7 @@ int fn_check_maps_args(const int32_t* coords, int n, int batch, const int32_t* s
     UMEREG_REQUIRE(batch > 0 && batch <= UMEREG_FEATNET_MAX_BATCH, "featnet: batch %d outside [1, %d]", batch, UMEREG_FEATNET_MAX_BATCH);
     UMEREG_REQUIRE(((uintptr_t)coords & 15) == 0, "featnet: coords must be 16-byte aligned");
     if (int rc = check_device()) return rc;
-    const size_t need = fn_ws(n).total;
-    if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 255)) {
-        set_error("featnet: workspace too small or not 256-byte aligned (%zu < %zu)", workspace_bytes, need);
-        return UMEREG_EWORKSPACE;
-    }
-    return UMEREG_OK;
+    return fn_check_ws("featnet", workspace, workspace_bytes, n);
 }
 }  // namespace
 
@@ -466,16 +457,16 @@ int fn_forward(const int32_t* coords, const float* feat, int n, int batch, const
     const int* perm = reinterpret_cast<const int*>(ws + w.off_perm);
 
     // encoder: conv -> BN (X), block -> the skip columns of the level's concatenation (level 4: S4)
-    hipLaunchKernelGGL(fn_conv1_kernel, dim3((n + 7) / 8), dim3(256), 0, st, feat, perm, f.nbr(fn_map_self(0)), status + 1,
+    hipLaunchKernelGGL(fn_conv1_kernel, dim3((n + 7) / 8), dim3(256), 0, st, feat, perm, fn_table(ws, w, fn_map_self(0)).nbr, status + 1,
                        params + f.po.w[0], params + f.po.scale[0], params + f.po.scale[0] + 32, X);
     UMEREG_CHECK_LAUNCH("fn_conv1_kernel");
-    int rc = f.conv(1, fn_map_self(0), 0, X, 32, cat[0] + kFnCatTr[0], kFnCatCols[0], X, 32, true);
+    int rc = f.conv(1, fn_map_self(0), X, 32, cat[0] + kFnCatTr[0], kFnCatCols[0], X, 32, true);
     for (int l = 1; l < kFnLevels && !rc; ++l) {
         const int cout = kFnLayers[2 * l].cout;
-        rc = f.conv(2 * l, fn_map_down(l - 1), l, cat[l - 1] + kFnCatTr[l - 1], kFnCatCols[l - 1], X, cout, nullptr, 0, false);
+        rc = f.conv(2 * l, fn_map_down(l - 1), cat[l - 1] + kFnCatTr[l - 1], kFnCatCols[l - 1], X, cout, nullptr, 0, false);
         float* dst = l < 4 ? cat[l] + kFnCatTr[l] : S4;
         const int ld = l < 4 ? kFnCatCols[l] : 256;
-        if (!rc) rc = f.conv(2 * l + 1, fn_map_self(l), l, X, cout, dst, ld, X, cout, true);
+        if (!rc) rc = f.conv(2 * l + 1, fn_map_self(l), X, cout, dst, ld, X, cout, true);
     }
     // decoder: transposed conv -> BN (X), block -> the first columns of the finer level's concatenation
     for (int l = 3; l >= 0 && !rc; --l) {
@@ -483,11 +474,11 @@ int fn_forward(const int32_t* coords, const float* feat, int n, int batch, const
         const int cout = kFnLayers[i].cout;
         const float* src = l == 3 ? S4 : cat[l + 1];
         const int ld_src = l == 3 ? 256 : kFnCatCols[l + 1];
-        rc = f.conv(i, fn_map_up(l), l, src, ld_src, X, cout, nullptr, 0, false);
-        if (!rc) rc = f.conv(i + 1, fn_map_self(l), l, X, cout, cat[l], kFnCatCols[l], X, cout, true);
+        rc = f.conv(i, fn_map_up(l), src, ld_src, X, cout, nullptr, 0, false);
+        if (!rc) rc = f.conv(i + 1, fn_map_self(l), X, cout, cat[l], kFnCatCols[l], X, cout, true);
     }
     // mlp1 + ReLU -> X [n, 64]; final + L2 normalisation -> out in input row order
-    if (!rc) rc = f.conv(18, -1, 0, cat[0], kFnCatCols[0], X, 64, nullptr, 0, true);
+    if (!rc) rc = f.conv(18, -1, cat[0], kFnCatCols[0], X, 64, nullptr, 0, true);
     if (rc) return rc;
     hipLaunchKernelGGL(fn_final_kernel, dim3((n + 255) / 256), dim3(256), 0, st, X, perm, status + 1, params + f.po.w[19],
                        params + f.po.scale[19], params + f.po.scale[19] + 32, out);
@@ -528,37 +519,14 @@ int fn_sparse_conv(const void* workspace, size_t workspace_bytes, const int32_t*
     UMEREG_REQUIRE(ld_in >= c_in && ld_in % 4 == 0 && ld_out >= c_out, "sparse_conv: bad leading dimensions %d / %d", ld_in, ld_out);
     UMEREG_REQUIRE(((uintptr_t)in & 15) == 0 && ((uintptr_t)W & 15) == 0, "sparse_conv: in and W must be 16-byte aligned");
     if (int rc = check_device()) return rc;
-    const FnWs w = fn_ws(n);
-    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) {
-        set_error("sparse_conv: workspace too small or not 256-byte aligned (%zu < %zu)", workspace_bytes, w.total);
-        return UMEREG_EWORKSPACE;
-    }
-    const char* ws = (const char*)workspace;
+    if (int rc = fn_check_ws("sparse_conv", workspace, workspace_bytes, n)) return rc;
+    const FnTable t = fn_table(workspace, fn_ws(n), table);
     ConvArgs a;
     a.in = in, a.W = W, a.scale = scale, a.shift = shift, a.res = accumulate ? out : nullptr, a.out = out;   // (res == out: each
                                                                                                              // element is read, then written, by one thread)
-    a.nbr = table >= 0 ? reinterpret_cast<const int*>(ws + w.off_nbr) + (size_t)table * w.n * kFnVol : nullptr;
-    a.mask = table >= 0 ? reinterpret_cast<const unsigned int*>(ws + w.off_mask) + (size_t)table * w.n : nullptr;
-    a.n_out = status + 1 + (table >= 0 ? fn_map_out_level(table) : 0);
+    a.nbr = t.nbr, a.mask = t.mask, a.n_out = status + 1 + t.level;
     a.ld_in = ld_in, a.ld_res = ld_out, a.ld_out = ld_out, a.cin = c_in, a.cout = c_out, a.K = table >= 0 ? kFnVol : 1, a.relu = 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (f16) {
-        const ConvArgsF16 h{a, nullptr};
-        if (c_out % 64 == 0) {
-            hipLaunchKernelGGL((fn_conv_f16_kernel<64, 64>), dim3((n + 63) / 64, c_out / 64), dim3(256), 0, st, h);
-        } else {
-            hipLaunchKernelGGL((fn_conv_f16_kernel<128, 32>), dim3((n + 127) / 128, c_out / 32), dim3(256), 0, st, h);
-        }
-        UMEREG_CHECK_LAUNCH("fn_conv_f16_kernel");
-        return UMEREG_OK;
-    }
-    if (c_out % 64 == 0) {
-        hipLaunchKernelGGL((fn_conv_kernel<64, 64>), dim3((n + 63) / 64, c_out / 64), dim3(256), 0, st, a);
-    } else {
-        hipLaunchKernelGGL((fn_conv_kernel<128, 32>), dim3((n + 127) / 128, c_out / 32), dim3(256), 0, st, a);
-    }
-    UMEREG_CHECK_LAUNCH("fn_conv_kernel");
-    return UMEREG_OK;
+    return fn_launch_conv(a, f16, nullptr, n, (hipStream_t)stream);
 }
 }  // namespace
 
@@ -584,11 +552,8 @@ UMEREG_API int umereg_sparse_conv1_f32(const void* workspace, size_t workspace_b
     UMEREG_REQUIRE(workspace && status && feat && W && scale && shift && out, "sparse_conv1: null pointer");
     UMEREG_REQUIRE(n > 0, "sparse_conv1: n must be positive (got %d)", n);
     if (int rc = check_device()) return rc;
+    if (int rc = fn_check_ws("sparse_conv1", workspace, workspace_bytes, n)) return rc;
     const FnWs w = fn_ws(n);
-    if (workspace_bytes < w.total || ((uintptr_t)workspace & 255)) {
-        set_error("sparse_conv1: workspace too small or not 256-byte aligned (%zu < %zu)", workspace_bytes, w.total);
-        return UMEREG_EWORKSPACE;
-    }
     const char* ws = (const char*)workspace;
     hipLaunchKernelGGL(fn_conv1_kernel, dim3((n + 7) / 8), dim3(256), 0, (hipStream_t)stream, feat,
                        reinterpret_cast<const int*>(ws + w.off_perm), reinterpret_cast<const int*>(ws + w.off_nbr), status + 1, W, scale,

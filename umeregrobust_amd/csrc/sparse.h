@@ -1,5 +1,6 @@
-// sparse.h -- coordinate maps of the sparse feature network (sparse_map.hip builds them, featnet.hip convolves over them):
-// the workspace carve-up, the coordinate key, the kernel-offset table.  Not part of the C ABI.
+// sparse.h -- coordinate maps of the sparse feature network (sparse_map.hip builds them, featnet.hip and sparse_wgrad.hip convolve
+// over them): the workspace carve-up with its check and its table pointers, the coordinate key, the kernel-offset table.  Not part
+// of the C ABI.
 //
 // MinkowskiEngine 0.5.4 semantics restated here (parity unpinned):
 //   * strided output map: unique(floor(c / (ts s)) ts s) per axis, batch index kept (fn_coarsen);
@@ -108,6 +109,30 @@ inline FnWs fn_ws(int n)
     for (int l = 0; l < 4; ++l) w.off_cat[l] = take(N * kFnCatCols[l] * 4);
     w.total = o;
     return w;
+}
+
+// neighbour table `table` of a workspace as the convolution kernels take it; -1: no table (a 1x1 layer over level 0)
+struct FnTable {
+    const int* nbr;             // [rows][27]
+    const unsigned int* mask;   // [rows]
+    int level;                  // the level of its output rows: their count is status[1 + level]
+};
+
+inline FnTable fn_table(const void* ws, const FnWs& w, int table)
+{
+    if (table < 0) return {nullptr, nullptr, 0};
+    const char* p = (const char*)ws;
+    return {reinterpret_cast<const int*>(p + w.off_nbr) + (size_t)table * w.n * kFnVol,
+            reinterpret_cast<const unsigned int*>(p + w.off_mask) + (size_t)table * w.n, fn_map_out_level(table)};
+}
+
+// the caller's workspace of an n-point pass: there, at least fn_ws(n).total bytes and 256-byte aligned, or UMEREG_EWORKSPACE
+inline int fn_check_ws(const char* who, const void* ws, size_t bytes, int n)
+{
+    const size_t need = fn_ws(n).total;
+    if (ws && bytes >= need && ((uintptr_t)ws & 255) == 0) return UMEREG_OK;
+    set_error("%s: workspace too small or not 256-byte aligned (%zu < %zu)", who, bytes, need);
+    return UMEREG_EWORKSPACE;
 }
 
 // builds every level and every neighbour table of a forward pass (sparse_map.hip); status as umereg_featnet_forward_f32
