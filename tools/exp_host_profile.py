@@ -31,7 +31,7 @@ def submit(i):
 def finish(h):
     t0 = time.perf_counter()
     h.ready.synchronize(); t0 = lap("wait for prob (GPU behind host)", t0)
-    cond = choice_noreplace(rng, h.num_kpts, 2500, pipe.host_prob[h.slot].numpy()); t0 = lap("weighted draw", t0)
+    cond = choice_noreplace(rng, h.num_kpts, 2500, pipe.slots[h.slot].host_prob.numpy()); t0 = lap("weighted draw", t0)
     out = pipe.finish(h, cond=cond, order_caller=False); t0 = lap("finish (H2D + phase B enqueue)", t0)
     with torch.cuda.stream(pipe.stream_of(h)):
         ops.hypothesis_gates(out.rtume_tform[0], h.entry.gt, counts[h.slot])

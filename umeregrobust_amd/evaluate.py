@@ -1,96 +1,20 @@
 """Counterpart of the hot-path part of the reference's evaluate.py.
 
-`my_ume_generation` keeps the reference signature (evaluate.py:50); `register_pair` is the body
-of the per-pair loop between feature extraction and hypothesis selection (evaluate.py:195-254)
-as a function, with the host RNG made explicit so a caller can replay or inject the draws.
+`my_ume_generation` keeps the reference signature (evaluate.py:50); the per-pair loop between feature extraction and hypothesis
+selection (evaluate.py:195-254: `register_pair`, `RegistrationPipeline`) lives in pipeline.py and is imported back under its names.
 """
-from types import SimpleNamespace
-
 import contextlib
 
 import numpy as np
 import torch
 
 from . import ops, streams as _streams
-from .host_rng import choice_noreplace, choice_uniform_noreplace
+from .host_rng import choice_uniform_noreplace
+from .pipeline import (PairBatch, PairResult, RegistrationPipeline, _draw_keypoints, _draw_keypoints_host, _index_tensor,  # noqa: F401
+                       _phase_a, _phase_b, _PinnedRing, _ring, _to_host, phase_a_route, register_pair)
 from .utils.eval_utils import relative_rotation_error  # noqa: F401
 from .utils.loc_utils import (FeatureCorrelator, batch_estimate_transform_ume_old, ume_cdist,  # noqa: F401
                                ume_kp_layer)
-
-
-class _PinnedRing:
-    """Host -> device uploads of the loop's index arrays (keypoint draws, the weighted draw, the correlation sub-samples: 20-80 KB
-    each, five per pair) and the download of the match probabilities, through a small ring of PINNED buffers: a copy out of pageable
-    numpy memory blocks the host for 50-100 us (staging + synchronisation), a pinned one is an asynchronous enqueue.  A buffer is
-    reused only after the event recorded behind its last copy has completed (a no-op wait in practice: a pair passes several host
-    synchronisations before the ring comes round).  One ring per host thread (threading.local: the end-to-end legs run pairs on
-    several threads) and per device (an event belongs to the device it was first recorded on)."""
-    SLOTS = 8
-
-    def __init__(self):
-        self.buf = [None] * self.SLOTS
-        self.ev = [None] * self.SLOTS
-        self.k = 0
-
-    def slot(self, nbytes):
-        k = self.k = (self.k + 1) % self.SLOTS
-        if self.ev[k] is not None:
-            self.ev[k].synchronize()
-        if self.buf[k] is None or self.buf[k].numel() < nbytes:
-            self.buf[k] = torch.empty(max(int(nbytes), 1 << 16), dtype=torch.uint8, pin_memory=True)
-        return k, self.buf[k]
-
-    def mark(self, k, dev):
-        if self.ev[k] is None:
-            self.ev[k] = torch.cuda.Event()
-        self.ev[k].record(torch.cuda.current_stream(dev))
-
-
-_ring_tls = __import__("threading").local()
-
-
-def _ring(dev):
-    rings = getattr(_ring_tls, "rings", None)
-    if rings is None:
-        rings = _ring_tls.rings = {}
-    idx = torch.device(dev).index
-    idx = torch.cuda.current_device() if idx is None else idx
-    r = rings.get(idx)
-    if r is None:
-        r = rings[idx] = _PinnedRing()
-    return r
-
-
-def _index_tensor(idx, dev):
-    """int64 index tensor on `dev`; numpy / list input goes up asynchronously through the pinned ring."""
-    if isinstance(idx, torch.Tensor):
-        return idx.to(device=dev, dtype=torch.int64)
-    a = np.ascontiguousarray(np.asarray(idx), dtype=np.int64)
-    dev = torch.device(dev)
-    if dev.type != "cuda" or a.size < 256:
-        return torch.as_tensor(a, dtype=torch.int64, device=dev)
-    ring = _ring(dev)
-    k, buf = ring.slot(a.nbytes)
-    host = buf[:a.nbytes].view(torch.int64).view(a.shape)
-    host.numpy()[...] = a
-    out = torch.empty(a.shape, dtype=torch.int64, device=dev)
-    out.copy_(host, non_blocking=True)
-    ring.mark(k, dev)
-    return out
-
-
-def _to_host(t):
-    """numpy copy of a device tensor through the pinned ring: asynchronous copy + a wait on its own event (a plain .cpu() takes
-    the pageable path: tens of microseconds more per call)."""
-    if not t.is_cuda:
-        return t.detach().numpy()
-    ring = _ring(t.device)
-    k, buf = ring.slot(t.numel() * t.element_size())
-    host = buf[:t.numel() * t.element_size()].view(t.dtype).view(t.shape)
-    host.copy_(t, non_blocking=True)
-    ring.mark(k, t.device)
-    ring.ev[k].synchronize()
-    return host.numpy().copy()
 
 
 def pc_fcht(pc1_pts, pc2_pts, pc1_feat, pc2_feat, rtume_hypotises, gt_tform, corr_sigma, args, timing=None, return_tform=False):
@@ -231,498 +155,6 @@ def my_ume_generation(pts, kpts, feat, args):
     """reference evaluate.py:50-60.  pts [bs,N,3], kpts [bs,n,3], feat [bs,N,32] -> F [bs,n,32,4];
     args.ume_max_nn / args.ume_r_nn as in the benchmark YAMLs."""
     return ops.ume_moments(pts, kpts, feat, args.ume_max_nn, args.ume_r_nn)
-
-
-def _phase_a(src_pts, tgt_pts, src_feat, tgt_feat, args, src_inds, tgt_inds, materialize_D=False, timing=None,
-             pair=None, match_opts=None):
-    """evaluate.py:195-236 up to the match probabilities: everything before the host RNG draw."""
-    dev = src_pts.device
-    # UME matrices (:206-212); the keypoint gathers src_pts[0, src_inds] (:201-202) are fused into the kernel
-    t_mom = None if timing is None else timing.setdefault("moments", [])
-    t_dist = None if timing is None else timing.setdefault("dist", ops.TimingList())
-    if pair is not None and timing is None and not materialize_D and ops.DEFAULT_MATCH_PRECISION == "f16r" \
-            and not getattr(args, "hungarian_matching_flag", False):
-        # the whole of a1..a5 in one native call (same kernels as the layered path below), the two clouds read where they lie:
-        # N_src != N_tgt is the normal case (kitti_dataset.py:568-569), nothing is stacked
-        F, m_tgt, ume_d, prob = ops.pair_match_ragged(pair.src_pts, pair.tgt_pts, pair.src_feat, pair.tgt_feat, pair.inds[0], pair.inds[1],
-                                                      args.ume_max_nn, args.ume_r_nn,
-                                                      args.tau if args.filter_by_ume_dist_cond else None, opts=match_opts)
-        return SimpleNamespace(ume_src=F[0:1], ume_tgt=F[1:2], match=m_tgt, match_d=ume_d, prob=prob, D=None,
-                               src_inds=src_inds, tgt_inds=tgt_inds, num_kpts=F.shape[1], dev=dev,
-                               src_pts=src_pts, tgt_pts=tgt_pts)
-    if pair is not None and pair.pts is not None:
-        # (timed / layered calls) equally large clouds stacked by the caller: ONE batch of 2 through every kernel (same arithmetic
-        # per cloud; half the launches, twice the parallelism for the small grid-building kernels)
-        ume_both = ops.ume_moments(pair.pts, None, pair.feat, args.ume_max_nn, args.ume_r_nn, timing=t_mom,
-                                   kp_index=pair.inds)
-        ume_src, ume_tgt = ume_both[0:1], ume_both[1:2]
-    else:
-        ume_src = ops.ume_moments(src_pts, None, src_feat, args.ume_max_nn, args.ume_r_nn, timing=t_mom, kp_index=src_inds)
-        ume_tgt = ops.ume_moments(tgt_pts, None, tgt_feat, args.ume_max_nn, args.ume_r_nn, timing=t_mom, kp_index=tgt_inds)
-    num_kpts = min(ume_src.shape[1], ume_tgt.shape[1])
-    ume_src = ume_src[:, :num_kpts]
-    ume_tgt = ume_tgt[:, :num_kpts]
-    # Matches (:215-225).  Hungarian matching (:216-222; off in every shipped config): by default the whole matrix goes to the
-    # host, exactly like the reference: D -> scipy.optimize.linear_sum_assignment -> (src rows, tgt columns); with
-    # args.assignment == "device" the solver of ops.linear_sum_assignment takes D where it lies
-    D = None
-    if getattr(args, "hungarian_matching_flag", False):
-        assignment = getattr(args, "assignment", "host")
-        if assignment not in ("host", "device"):
-            raise ValueError(f"args.assignment must be 'host' or 'device', got {assignment!r}")
-        D = ops.ume_cdist(ume_src, ume_tgt, timing=t_dist)
-        if assignment == "device":
-            m_src, m_tgt = ops.linear_sum_assignment(D[0:1])                                  # :219; [1, n] each
-        else:
-            from scipy.optimize import linear_sum_assignment
-            src_m, tgt_m = linear_sum_assignment(D[0].cpu().numpy())                          # :219
-            m_src = torch.from_numpy(src_m).long().to(dev)[None]                              # m[..., 0]
-            m_tgt = torch.from_numpy(tgt_m).long().to(dev)[None]                              # m[..., 1]
-        ume_d = D[0, m_src[0], m_tgt[0]][None]                                                # :234
-        prob = ops.match_prob(ume_d[0], args.tau) if args.filter_by_ume_dist_cond else None
-        return SimpleNamespace(ume_src=ume_src, ume_tgt=ume_tgt, match=m_tgt, match_src=m_src, match_d=ume_d, prob=prob,
-                               D=D if materialize_D else None, src_inds=src_inds, tgt_inds=tgt_inds,
-                               num_kpts=m_src.shape[1], dev=dev, src_pts=src_pts, tgt_pts=tgt_pts)
-    if materialize_D:
-        D = ops.ume_cdist(ume_src, ume_tgt, timing=t_dist)
-        m_tgt = D.min(dim=-1)[1]
-        ume_d = torch.gather(D, 2, m_tgt.unsqueeze(-1)).squeeze(-1)
-    else:
-        m_tgt, ume_d = ops.ume_match(ume_src, ume_tgt, timing=t_dist, opts=match_opts)
-    prob = ops.match_prob(ume_d[0], args.tau) if args.filter_by_ume_dist_cond else None   # (:235-236)
-    return SimpleNamespace(ume_src=ume_src, ume_tgt=ume_tgt, match=m_tgt, match_d=ume_d, prob=prob, D=D,
-                           src_inds=src_inds, tgt_inds=tgt_inds, num_kpts=num_kpts, dev=dev,
-                           src_pts=src_pts, tgt_pts=tgt_pts)
-
-
-class PairBatch:
-    """A registration pair as the native a1-a5 entries take it: the two clouds WHERE THEY LIE -- src_pts [N_src,3], tgt_pts [N_tgt,3],
-    src_feat [N_src,32], tgt_feat [N_tgt,32], contiguous float32 on the device -- and the keypoint indices of both as the rows of
-    one int64 [2,n_kp] tensor (row 0 = source).  N_src != N_tgt is the NORMAL case: the reference's collate dilutes source and target
-    independently (datasets/kitti/kitti_dataset.py:568-569: min(len(cloud), max_pc_size) each, and the cached clouds are separately
-    voxelised reconstructions), and its loop draws num_init_sel = min(10000, N_src, N_tgt) keypoints from EACH cloud
-    (evaluate.py:195-204) -- so the sizes differ and vary pair to pair while the keypoint count is common to both.  Nothing is
-    stacked or copied: the kernels read each cloud through a device-side record (ops.pair_match_ragged, ops.PairMatchCapGraph).
-
-    PairBatch(pts, feat, inds) keeps the stacked form of earlier rounds -- pts [2,N,3], feat [2,N,32] -- for callers that hold
-    equally large clouds in one tensor (`.pts` / `.feat` are then set, the per-cloud attributes are views of them)."""
-
-    def __init__(self, pts, feat, inds):
-        assert pts.dim() == 3 and pts.shape[0] == 2 and feat.shape[:2] == pts.shape[:2] and inds.shape[0] == 2
-        self.pts, self.feat, self.inds = pts.contiguous(), feat.contiguous(), inds.contiguous().to(torch.int64)
-        self.src_pts, self.tgt_pts, self.src_feat, self.tgt_feat = self.pts[0], self.pts[1], self.feat[0], self.feat[1]
-
-    @property
-    def sizes(self):
-        """(N_src, N_tgt, n_kp)"""
-        return self.src_pts.shape[0], self.tgt_pts.shape[0], self.inds.shape[1]
-
-    def tensors(self):
-        return (self.src_pts, self.tgt_pts, self.src_feat, self.tgt_feat, self.inds)
-
-    def native(self):
-        """(six device addresses, N_src, N_tgt) as umereg_pair_match_graph_launch_ragged takes them; cached -- a PairBatch is
-        immutable once built (rebinding its tensors afterwards is not supported)."""
-        na = getattr(self, "_native", None)
-        if na is None:
-            na = self._native = (self.src_pts.data_ptr(), self.tgt_pts.data_ptr(), self.src_feat.data_ptr(), self.tgt_feat.data_ptr(),
-                                 self.inds.data_ptr(), self.inds.data_ptr() + 8 * self.inds.shape[1],
-                                 self.src_pts.shape[0], self.tgt_pts.shape[0])
-        return na
-
-    @classmethod
-    def from_clouds(cls, src_pts, tgt_pts, src_feat, tgt_feat, src_inds, tgt_inds):
-        """The pair over the caller's own tensors ([1,N,*] or [N,*] clouds of any two sizes; NO copy of the clouds).  Returns None
-        only for what the native entries cannot read in place (another dtype, a non-contiguous view, a host tensor) or for keypoint
-        sets of different length -- the layered per-cloud path handles those."""
-        cl = []
-        for t_, w_ in ((src_pts, 3), (tgt_pts, 3), (src_feat, 32), (tgt_feat, 32)):
-            if t_.dim() == 3 and t_.shape[0] == 1:
-                t_ = t_[0]
-            if not (t_.is_cuda and t_.dim() == 2 and t_.shape[1] == w_ and t_.dtype == torch.float32 and t_.is_contiguous()):
-                return None
-            cl.append(t_)
-        if cl[2].shape[0] != cl[0].shape[0] or cl[3].shape[0] != cl[1].shape[0] or src_inds.numel() != tgt_inds.numel() \
-                or src_inds.numel() == 0:
-            return None
-        base = getattr(src_inds, "_base", None)
-        if base is not None and base is getattr(tgt_inds, "_base", None) and base.dim() == 2 and base.shape[0] == 2 \
-                and base.is_contiguous() and src_inds.data_ptr() == base.data_ptr() and tgt_inds.data_ptr() == base[1].data_ptr():
-            inds = base                   # the two index sets are the rows of one [2, n_kp] upload already (_draw_keypoints)
-        else:
-            inds = torch.stack([src_inds.view(-1), tgt_inds.view(-1)], 0)
-        self = cls.__new__(cls)
-        self.pts = self.feat = None
-        self.src_pts, self.tgt_pts, self.src_feat, self.tgt_feat = cl
-        self.inds = inds.contiguous().to(device=cl[0].device, dtype=torch.int64)
-        return self
-
-
-class PairResult(SimpleNamespace):
-    """Namespace of one pair's results; the matched keypoint coordinates the reference materialises
-    (evaluate.py:228-229, 240-241) are gathered only if somebody reads them."""
-
-    @property
-    def src_keypoint_pts(self):
-        return self.src_pts[:, self.src_inds[:self.num_kpts]]
-
-    @property
-    def tgt_keypoint_pts(self):
-        return self.tgt_pts[:, self.tgt_inds[:self.num_kpts]]
-
-    @property
-    def h_index(self):
-        return self.match[0][self.g_index]
-
-    @property
-    def src_matches_keypoint_pts(self):
-        return self.src_keypoint_pts[:, self.g_index]
-
-    @property
-    def tgt_matches_keypoint_pts(self):
-        return self.tgt_keypoint_pts[:, self.h_index]
-
-
-def _phase_b(a, args, cond):
-    """evaluate.py:238-254: apply the drawn sub-sample and solve one SE(3) per kept match."""
-    dev = a.dev
-    if args.filter_by_ume_dist_cond:
-        g_index = _index_tensor(cond, dev)          # m[:,0] is arange (:225), so src rows = cond itself
-    else:
-        g_index = None
-    # Hypotheses (:248-254); the match gathers (:228-231, 243-244) are fused into the solve through the
-    # match table (target row of source row g = match[g])
-    if getattr(a, "match_src", None) is not None:
-        # Hungarian matches: match k pairs source row match_src[k] with target row match[k] (for a square or wide D the
-        # source rows are arange and this is the same table; explicit indices keep the tall case right)
-        sel = g_index if g_index is not None else torch.arange(a.num_kpts, device=dev)
-        T, _ = ops.rtume_solve(a.ume_src[0], a.ume_tgt[0], a.match_src[0][sel], a.match[0][sel])
-    else:
-        T, _ = ops.rtume_solve(a.ume_src[0], a.ume_tgt[0], g_index, None, h_of_g=a.match[0])
-    out = PairResult(**vars(a))
-    out.rtume_tform = T.view(1, -1, 4, 4)
-    out.cond = cond
-    out.g_index = g_index if g_index is not None else torch.arange(a.num_kpts, device=dev)
-    return out
-
-
-def _draw_keypoints_host(n_src, n_tgt, args, rng, src_inds=None, tgt_inds=None):
-    """Keypoint draws (:195-204) on the host numpy RNG (unless injected) -> index arrays, nothing touches the device."""
-    if args.filter_by_ume_dist_cond:
-        num_init_sel = min(10000, min(n_src, n_tgt))
-    else:
-        num_init_sel = min(min(n_src, n_tgt), args.ume_n_samples)
-    if src_inds is None:
-        src_inds = choice_uniform_noreplace(rng, n_src, num_init_sel)
-    if tgt_inds is None:
-        tgt_inds = choice_uniform_noreplace(rng, n_tgt, num_init_sel)
-    return src_inds, tgt_inds
-
-
-def _draw_keypoints(src_pts, tgt_pts, args, rng, src_inds, tgt_inds):
-    """Keypoint draws (:195-204): host numpy RNG unless injected; -> device index tensors."""
-    src_inds, tgt_inds = _draw_keypoints_host(src_pts.shape[1], tgt_pts.shape[1], args, rng, src_inds, tgt_inds)
-    if not isinstance(src_inds, torch.Tensor) and not isinstance(tgt_inds, torch.Tensor) and len(src_inds) == len(tgt_inds):
-        both = _index_tensor(np.stack([np.asarray(src_inds), np.asarray(tgt_inds)]), src_pts.device)      # one upload: [2, n_kp]
-        return both[0], both[1]
-    return _index_tensor(src_inds, src_pts.device), _index_tensor(tgt_inds, src_pts.device)
-
-
-def register_pair(src_pts, tgt_pts, src_feat, tgt_feat, args, rng=np.random, src_inds=None, tgt_inds=None,
-                  cond=None, materialize_D=False, timing=None, after_phase_a=None):
-    """The named hot path for one pair (reference evaluate.py:195-254).
-
-    src_pts/tgt_pts [1,N,3], src_feat/tgt_feat [1,N,32] on the GPU.  Host-RNG draws mirror the
-    reference's np.random.choice calls (:199-200, :238) and can be injected (src_inds, tgt_inds,
-    cond) for replay.  Returns a namespace with rtume_tform [1,M,4,4] and the intermediates the
-    downstream stages (hypothesis selection) need.
-    after_phase_a: optional callable, invoked once a1-a5 are enqueued and before the host waits for the match probabilities: device
-    work that does not depend on this function's results (the voxel thinning of the raw clouds, evaluate.prepare_selection) then
-    runs while the host draws.  It must not consume `rng`.
-    """
-    assert src_pts.shape[0] == 1, "the reference evaluates with batch_size: 1"
-    src_inds, tgt_inds = _draw_keypoints(src_pts, tgt_pts, args, rng, src_inds, tgt_inds)
-    pair = None
-    if timing is None and not materialize_D and src_pts.is_cuda and ops.DEFAULT_MATCH_PRECISION == "f16r" \
-            and not getattr(args, "hungarian_matching_flag", False):
-        # both clouds -- of whatever two sizes the collate produced (kitti_dataset.py:568-569) -- through every kernel as ONE batch
-        # of two and a1..a5 as one native call, read where they lie (no stacking copy)
-        pair = PairBatch.from_clouds(src_pts, tgt_pts, src_feat, tgt_feat, src_inds, tgt_inds)
-    a = _phase_a(src_pts, tgt_pts, src_feat, tgt_feat, args, src_inds, tgt_inds, materialize_D, timing, pair=pair)
-    if after_phase_a is not None:
-        a.side = after_phase_a()
-    if args.filter_by_ume_dist_cond and cond is None:
-        # tau-weighted sub-sampling of matches (:233-245): the draw consumes the HOST numpy RNG
-        num_matches = min(a.num_kpts, args.ume_n_samples)
-        cond = choice_noreplace(rng, a.num_kpts, num_matches, _to_host(a.prob))
-    return _phase_b(a, args, cond)
-
-
-class RegistrationPipeline:
-    """Same computation as register_pair, software-pipelined over consecutive pairs.
-
-    The reference draws the match sub-sample on the host (np.random.choice with p from the device,
-    evaluate.py:238): a device -> host -> device round trip in the middle of every pair.  Here phase A of
-    pair i+1 (moments, matching, probabilities: one native call) is enqueued on another HIP stream before
-    the host draws for pair i, so the draw overlaps GPU work, and the streams are not ordered against
-    each other, so the single-workgroup kernels of one pair run beside the machine-filling kernels of the
-    other.  Results are identical to register_pair given the same RNG stream; `submit` and `finish` must
-    be called in order.
-    """
-
-    def __init__(self, args, device, depth=2, rng=np.random, threaded_draw=False, use_graphs=False, stream_plan=None,
-                 match_opts=None, capacity=None):
-        """threaded_draw: run the host draw (event wait + choice) on one worker thread, in submission
-        order, so it also overlaps the main thread's kernel enqueues (the native draw releases the GIL).
-        Use depth >= 3 with it.  The worker is then the only consumer of `rng` between submit and finish,
-        so inject the keypoint indices (or draw them from a different generator)."""
-        self.args, self.rng, self.depth = args, rng, depth
-        self.match_opts = match_opts       # ops.MatchOpts of THIS pipeline's matcher calls (per call, not process state)
-        # use_graphs ("slot"; True / "pair" are accepted as the same thing): phase A (13 launches) as ONE hipGraph per pipeline slot,
-        # captured once at a CAPACITY -- clouds of up to `capacity` points (default: args.max_pc_size, the collate's bound,
-        # kitti_dataset.py:568-569; grown on demand) and the keypoint count of the first pair -- whose kernels read each submitted
-        # pair's clouds WHERE THEY LIE through a 64-byte device record (ops.PairMatchCapGraph).  What a loop over distinct pairs of
-        # varying size (reference evaluate.py:175: 1 475 of them, N_src != N_tgt) needs: a new pair, of whatever shape that fits, is
-        # a record write + a replay -- no re-capture, no staging copy, no dependence on where the caller keeps its tensors.  Only a
-        # cloud beyond the capacity or another keypoint count (min(10000, N_src, N_tgt): clouds below 10 000 points) captures anew.
-        # The graph writes into buffers it owns: a pair's phase-A outputs, rtume_tform and g_index (slot buffers) are valid until the
-        # slot's next submit / finish: consume or clone them before submitting `depth` more pairs.
-        if use_graphs not in (False, True, "pair", "slot"):
-            raise ValueError(f"use_graphs must be False, True / 'pair' or 'slot' (got {use_graphs!r})")
-        self.use_graphs = "slot" if use_graphs else False
-        self.capacity = int(capacity) if capacity else int(getattr(args, "max_pc_size", 0) or 0)
-        self.graphs = {}                 # (kept empty: the per-(slot, PairBatch) graphs of rounds 2-5 are gone)
-        self.slot_graphs = {}            # slot -> [PairMatchCapGraph, ...] most recently used last (one per keypoint count; <= 2)
-        self.captures = 0                # graphs captured so far (a stream of pairs that fit the capacity: `depth`)
-        self.pool = None
-        if threaded_draw:
-            from concurrent.futures import ThreadPoolExecutor
-            self.pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="umereg-draw")
-        self.dev = torch.device(device)
-        # Which slot streams share a HARDWARE QUEUE decides how the pairs' kernels overlap: the HIP runtime multiplexes all streams of the
-        # process onto four queues by a rule a caller cannot read back, and two streams on one queue run strictly one after the other
-        # (all slots on one queue 2 820 pairs/s, KT shape; a slot on the NULL stream's queue costs ~10 %).  Rounds 3-5 steered that by
-        # creation order ("sd": a spacer stream behind every slot stream) -- which holds only until the process creates one stream more
-        # somewhere else (BENCH r05 -> r06: evaluate_pairs 446 -> 375 pairs/s on unchanged code).  Now the slot streams are CHOSEN BY
-        # MEASUREMENT (streams.concurrent_streams: a spin kernel on one stream, a one-thread kernel on the other): consecutive slots on
-        # different queues, none on the null stream's.  stream_plan = a string of 's' / 'd' keeps the creation-order form (bench.py times
-        # both after every run: config.stream_plan_check).
-        self.streams, self._spacers = [], []
-        self.stream_plan = stream_plan or "measured"
-        with torch.cuda.device(self.dev):
-            if stream_plan in (None, "measured", "auto"):
-                self.streams = list(_streams.concurrent_streams(self.dev, depth))
-            else:
-                for tok in stream_plan + "s" * depth:           # 's' = the next slot's stream, 'd' = a spacer
-                    if tok == "s" and len(self.streams) >= depth:
-                        continue
-                    s_ = torch.cuda.Stream(self.dev)
-                    s_.cuda_stream                          # creates the HIP stream now
-                    (self.streams if tok == "s" else self._spacers).append(s_)
-        self.host_prob = [None] * depth
-        self.host_cond = [None] * depth
-        self.cond_uploaded = [None] * depth     # event: the H2D copy out of host_cond[k] has completed
-        self.in_flight = [False] * depth        # slot k holds a submitted pair whose finish() has not run yet
-        self.n_submitted = 0
-        # graph fast path: per-slot reusable event, pinned buffers with cached numpy views / addresses, device index buffer
-        self.ready_ev = [torch.cuda.Event() for _ in range(depth)]
-        self.host_cond_np = [None] * depth
-        self.cond_dev = [None] * depth
-        self.T_buf = [None] * depth
-        self.stream_ptrs = [s_.cuda_stream for s_ in self.streams]
-
-    def submit(self, src_pts, tgt_pts, src_feat, tgt_feat, src_inds=None, tgt_inds=None, timing=None, pair=None, rng=None):
-        """pair: optional PairBatch holding the same clouds/keypoints as a batch of 2 (then the per-cloud
-        arguments are only used for their shapes and as views for downstream consumers).
-        rng: numpy generator for THIS pair's draws (default: the pipeline's)."""
-        k = self.n_submitted % self.depth
-        if self.in_flight[k]:
-            raise RuntimeError(f"RegistrationPipeline: slot {k} still holds an unfinished pair -- at most depth={self.depth} "
-                               "pairs may be submitted before their finish() (its pinned buffers would be overwritten)")
-        a = self._submit_slot(k, src_pts, tgt_pts, src_feat, tgt_feat, src_inds, tgt_inds, timing, pair, rng)
-        # the slot is taken only once the pair is really enqueued: a submit that raised (graph capture, a bad argument, the
-        # host-side Hungarian step) leaves the pipeline usable
-        self.in_flight[k] = True
-        self.n_submitted += 1
-        return a
-
-    def _slot_graph(self, k, pair):
-        """The slot's capacity graph for a pair of these sizes; captured when none of the slot's graphs fits (first use, a cloud
-        beyond the capacity, another keypoint count)."""
-        args = self.args
-        tau = args.tau if args.filter_by_ume_dist_cond else None
-        n_src, n_tgt, n_kp = pair.sizes
-        lst = self.slot_graphs.setdefault(k, [])
-        for g in lst:
-            if g.fits(n_src, n_tgt, n_kp, args.ume_max_nn, args.ume_r_nn, tau, self.match_opts):
-                if g is not lst[-1]:
-                    lst.remove(g); lst.append(g)
-                return g
-        need = max(n_src, n_tgt)
-        if need > self.capacity:
-            self.capacity = (need + need // 8 + 1023) // 1024 * 1024       # (headroom: the next pair is a few per cent larger or smaller)
-        if len(lst) >= 2:
-            self.streams[k].synchronize()         # the old exec may still be running on the slot's stream
-            lst.pop(0)
-        with torch.cuda.stream(self.streams[k]):
-            # buffers owned by the graph are allocated under the slot's stream: that is the stream its kernels run on, so
-            # the caching allocator cannot hand them to somebody else while a replay is in flight
-            g = ops.PairMatchCapGraph(self.dev, self.capacity, n_kp, args.ume_max_nn, args.ume_r_nn, tau, opts=self.match_opts)
-        lst.append(g)
-        self.captures += 1
-        return g
-
-    def _submit_slot(self, k, src_pts, tgt_pts, src_feat, tgt_feat, src_inds, tgt_inds, timing, pair, rng):
-        st = self.streams[k]
-        rng = rng if rng is not None else self.rng
-        if pair is not None:
-            src_inds, tgt_inds = pair.inds[0], pair.inds[1]
-        else:
-            src_inds, tgt_inds = _draw_keypoints(src_pts, tgt_pts, self.args, rng, src_inds, tgt_inds)
-            if timing is None:
-                # the pair over the caller's own tensors (no copy of the clouds, whatever their two sizes): the one-call / graph path
-                pair = PairBatch.from_clouds(src_pts, tgt_pts, src_feat, tgt_feat, src_inds, tgt_inds)
-        st.wait_stream(torch.cuda.current_stream(self.dev))
-        # (no ordering between the phase-A blocks of consecutive pairs: the single-workgroup kernels of one pair --
-        # keypoint order, grid scan, softmax, RTUME -- then run beside the machine-filling kernels of the other:
-        # 0.416 -> 0.36 ms per pair)
-        graph = None
-        if self.use_graphs and pair is not None and timing is None and ops.DEFAULT_MATCH_PRECISION == "f16r" \
-                and not getattr(self.args, "hungarian_matching_flag", False) and self.pool is None \
-                and torch.cuda.current_device() == self.dev.index:
-            graph = self._slot_graph(k, pair)
-        if graph is not None:
-            # graph fast path: record write + replay + probability download in one native call on the slot's stream, no torch stream /
-            # device contexts, a per-slot event (the host side of a pair is as long as its GPU side: every 10 us count)
-            hp = None
-            if graph.prob is not None:
-                hp = self.host_prob[k]
-                if hp is None or hp.numel() != graph.prob.numel():
-                    hp = self.host_prob[k] = torch.empty(graph.prob.numel(), dtype=torch.float32, pin_memory=True)
-            graph.launch_native(pair.native(), hp.data_ptr() if hp is not None else 0, self.stream_ptrs[k])
-            ev = self.ready_ev[k]
-            ev.record(st)
-            a = SimpleNamespace(ume_src=graph.F[0:1], ume_tgt=graph.F[1:2], match=graph.m, match_d=graph.d, prob=graph.prob, D=None,
-                                src_inds=src_inds, tgt_inds=tgt_inds, num_kpts=graph.F.shape[1], dev=self.dev, src_pts=src_pts,
-                                tgt_pts=tgt_pts, ready=ev, slot=k, rng=rng, draw=None, graph=graph)
-            # the replay reads the caller's tensors on the SLOT's stream: the handle holds them until finish() has waited for `ready`
-            # (recorded behind the replay's last kernel), so a caller that rebinds `pair` right after submit() cannot have the
-            # caching allocator hand the blocks out on its own stream while the kernels are pending
-            a.keep = (pair, src_feat, tgt_feat)
-            return a
-        with torch.cuda.stream(st):
-            a = _phase_a(src_pts, tgt_pts, src_feat, tgt_feat, self.args, src_inds, tgt_inds, False, timing, pair,
-                         match_opts=self.match_opts)
-            if a.prob is not None:
-                if self.host_prob[k] is None or self.host_prob[k].numel() != a.prob.numel():
-                    self.host_prob[k] = torch.empty(a.prob.numel(), dtype=torch.float32, pin_memory=True)
-                self.host_prob[k].copy_(a.prob, non_blocking=True)
-            a.ready = torch.cuda.Event()
-            a.ready.record(st)
-        a.slot = k
-        a.rng = rng
-        a.draw = None
-        a.keep = (pair, src_pts, tgt_pts, src_feat, tgt_feat)     # read on the slot's stream, possibly allocated on another: alive until finish()
-        if self.pool is not None and self.args.filter_by_ume_dist_cond:
-            a.draw = self.pool.submit(self._draw, a)
-        return a
-
-    def _draw(self, a):
-        a.ready.synchronize()
-        num_matches = min(a.num_kpts, self.args.ume_n_samples)
-        return choice_noreplace(a.rng, a.num_kpts, num_matches, self.host_prob[a.slot].numpy())
-
-    def finish(self, a, cond=None, order_caller=True):
-        """Host draw (or the injected `cond`) + phase B of pair `a` on its slot's stream.  The CALLER'S current stream is made
-        to wait for that stream (no host synchronisation), so the returned tensors can be consumed with ordinary torch
-        semantics.  A caller that consumes them under `with torch.cuda.stream(pipe.stream_of(a))` only -- bench.py's loop --
-        passes order_caller=False and saves the event record / wait and the allocator bookkeeping (~15 us of host time).
-        With use_graphs the phase-A outputs (ume_src/ume_tgt, match, match_d, prob) are buffers owned by the slot's graph:
-        valid until the slot's next submit."""
-        st = self.streams[a.slot]
-        if not order_caller:
-            return self._finish_on_slot(a, cond, st)
-        caller = torch.cuda.current_stream(self.dev)
-        out = self._finish_on_slot(a, cond, st)
-        if caller != st:
-            caller.wait_stream(st)
-            for t_ in (out.rtume_tform, getattr(out, "g_index", None)):
-                if isinstance(t_, torch.Tensor):
-                    t_.record_stream(caller)          # allocated on the slot's stream, read on the caller's
-        return out
-
-    def _finish_on_slot(self, a, cond, st):
-        if not self.in_flight[a.slot]:
-            raise RuntimeError("RegistrationPipeline.finish: this pair was already finished")
-        self.in_flight[a.slot] = False
-        injected = cond is not None
-        if self.args.filter_by_ume_dist_cond and cond is None:
-            cond = a.draw.result() if a.draw is not None else self._draw(a)
-        # the pair's inputs were read on the slot's stream: after a host draw the host has waited for `ready` (behind those reads) and
-        # the handle's hold on them can simply go; otherwise (no weighted draw, or an injected `cond`) the allocator is told
-        keep, a.keep = getattr(a, "keep", None), None
-        if keep and (injected or not self.args.filter_by_ume_dist_cond):
-            for t_ in keep:
-                for u_ in (t_.tensors() if isinstance(t_, PairBatch) else (t_,)):
-                    if isinstance(u_, torch.Tensor) and u_.is_cuda:
-                        u_.record_stream(st)
-        del keep
-        graph = getattr(a, "graph", None)
-        if graph is not None and not isinstance(cond, torch.Tensor):
-            # graph fast path: index upload + SE(3) solve from the graph's own outputs in one native call
-            k = a.slot
-            out = PairResult(**vars(a))
-            if self.args.filter_by_ume_dist_cond:
-                c = np.asarray(cond, dtype=np.int64)
-                n = c.size
-                if self.host_cond[k] is None or self.host_cond[k].numel() != n or self.host_cond_np[k] is None \
-                        or self.cond_dev[k] is None or self.cond_dev[k].numel() != n:
-                    # (the plain-launch branch below allocates host_cond[k] alone: a slot that served a timed pair first has no views yet)
-                    if self.cond_uploaded[k] is not None:
-                        self.cond_uploaded[k].synchronize()
-                    self.host_cond[k] = torch.empty(n, dtype=torch.int64, pin_memory=True)
-                    self.host_cond_np[k] = self.host_cond[k].numpy()
-                    self.cond_dev[k] = torch.empty(n, dtype=torch.int64, device=self.dev)
-                if injected:
-                    a.ready.synchronize()     # (the draw path has waited already) the slot's previous upload out of the pinned buffer is done
-                self.host_cond_np[k][:] = c
-                # T and the index tensor are the slot's buffers (no per-pair allocation / cross-stream allocator bookkeeping):
-                # like the graph's own outputs they are valid until the slot's next finish
-                T = self.T_buf[k]
-                if T is None or T.shape[0] != n:
-                    T = self.T_buf[k] = torch.empty((n, 4, 4), dtype=torch.float32, device=self.dev)
-                graph.solve(self.host_cond[k].data_ptr(), n, self.cond_dev[k], T, self.stream_ptrs[k])
-                out.cond, out.g_index = c, self.cond_dev[k]
-            else:
-                n = a.num_kpts
-                T = self.T_buf[k]
-                if T is None or T.shape[0] != n:
-                    T = self.T_buf[k] = torch.empty((n, 4, 4), dtype=torch.float32, device=self.dev)
-                graph.solve(0, n, None, T, self.stream_ptrs[k])
-                out.cond, out.g_index = cond, torch.arange(n, device=self.dev)
-            out.rtume_tform = T.view(1, n, 4, 4)
-            return out
-        with torch.cuda.stream(st):
-            if self.args.filter_by_ume_dist_cond and not isinstance(cond, torch.Tensor):
-                # upload through pinned memory: a pageable-source copy blocks the host for tens of microseconds
-                c = np.asarray(cond, dtype=np.int64)
-                k = a.slot
-                if self.host_cond[k] is None or self.host_cond[k].numel() != c.size:
-                    self.host_cond[k] = torch.empty(c.size, dtype=torch.int64, pin_memory=True)
-                    self.host_cond_np[k] = None
-                elif self.cond_uploaded[k] is not None:
-                    self.cond_uploaded[k].synchronize()        # the previous pair's async upload out of this buffer is done
-                self.host_cond[k].numpy()[:] = c
-                cond_dev = self.host_cond[k].to(self.dev, non_blocking=True)
-                self.cond_uploaded[k] = torch.cuda.Event()
-                self.cond_uploaded[k].record(st)
-                out = _phase_b(a, self.args, cond_dev)
-                out.cond = c
-                return out
-            return _phase_b(a, self.args, cond)
-
-    def stream_of(self, a):
-        return self.streams[a.slot]
 
 
 _OVERLAP_STREAMS = {}
