@@ -28,15 +28,14 @@
 //   cdist_finish_kernel  dF = -2 (M - Q Q^T M) R^{-T} per keypoint, fp64, one 32-lane group per keypoint (lane = row)
 #include "common.h"
 #include "householder.h"
+#include "ume_grad_plan.h"
 #include "umereg_ume_grad.h"
 
 namespace umereg {
 
 using f32x16g = __attribute__((ext_vector_type(16))) float;
 
-constexpr int kGradWaves = 4;      // waves per workgroup
-constexpr int kRowTiles = 2;       // 32-row tiles of A (8 keypoints each) a wave keeps
-constexpr int kRowKp = 8 * kRowTiles;
+constexpr int kGradWaves = 4;      // waves per workgroup (kRowTiles, kRowKp: ume_grad_plan.h)
 
 __device__ __forceinline__ double wave_sum_f64(double v)
 {
@@ -322,26 +321,7 @@ __global__ __launch_bounds__(kWave* kGradWaves) void cdist_finish_kernel(const f
 
 // ---- host side -------------------------------------------------------------------------------------------------------
 
-static inline int pad_kp(int n) { return (n + kRowKp - 1) / kRowKp * kRowKp; }
-
-struct BwdPlan {
-    int n_rt, n_jt, tiles_per_split, splits, n_work;
-};
-
-// rows: keypoints of the side whose gradient is formed; cols: the other side's
-static BwdPlan bwd_plan(int rows, int cols)
-{
-    BwdPlan p;
-    p.n_rt = pad_kp(rows) / kRowKp;
-    p.n_jt = pad_kp(cols) / 8;
-    int splits = (4096 + p.n_rt - 1) / p.n_rt;     // enough waves for 256 CUs x 4 SIMDs several times over
-    if (splits > 32) splits = 32;
-    if (splits > p.n_jt) splits = p.n_jt;
-    p.tiles_per_split = (p.n_jt + splits - 1) / splits;
-    p.splits = (p.n_jt + p.tiles_per_split - 1) / p.tiles_per_split;
-    p.n_work = p.n_rt * p.splits;
-    return p;
-}
+// (pad_kp and bwd_plan, the rule of the splits: ume_grad_plan.h)
 
 struct SideLayout {
     size_t qrow, qcol, q64, r64;   // byte offsets
