@@ -26,6 +26,8 @@ the same products) and, with `--stats-csv`, the split of a profiled run into ker
 `--train --train-precision f16`: the same with ResUNetSmall2(trainable=True, train_precision="f16") (f16 operands in the
 layer-wise forward and in both gradients, include/umereg_sparse_conv_f16.h); the line carries a "train_precision" key, and
 the peak fraction stays relative to the fp32 matrix peak.
+`--train --fused-norm`: ResUNetSmall2(trainable=True, fused_norm=True) (batch norm, residual, ReLU and the f16 gradient scale on
+include/umereg_bn_act.h); the line carries a "fused_norm" key, and the profile's `norm_act` group holds the new kernels.
 """
 import argparse
 import json
@@ -85,7 +87,9 @@ def flop_counts(masks, levels, info):
 # kernel groups of a profiled training run (rocprofv3 kernel_stats.csv, by kernel name)
 GROUPS = (("conv_forward_and_input_gradient", ("fn_conv_kernel", "fn_conv1_kernel", "fn_conv_f16_kernel")),
           ("weight_gradient", ("wg_mfma_kernel", "wg_c1_kernel", "wg_reduce_kernel", "wg_f16_kernel")),
-          ("repack", ("wg_repack_kernel",)))
+          ("repack", ("wg_repack_kernel",)),
+          ("norm_act", ("bn_stats_kernel", "bn_fwd_apply_kernel", "bn_bwd_reduce_kernel", "bn_bwd_apply_kernel", "gs_partial_kernel",
+                        "gs_finish_kernel")))
 
 
 def kernel_groups(path, steps):
@@ -117,7 +121,7 @@ def train_mode(a, dev):
     coords = torch.from_numpy(np.concatenate(clouds)).to(dev)
     n = coords.shape[0]
     torch.manual_seed(a.seed)
-    m = models.ResUNetSmall2(in_channels=1, out_channels=32, trainable=True, train_precision=a.train_precision).to(dev)
+    m = models.ResUNetSmall2(in_channels=1, out_channels=32, trainable=True, train_precision=a.train_precision, fused_norm=a.fused_norm).to(dev)
     st = SparseTensor(torch.ones(n, 1, device=dev), coordinates=coords)
     st._batch_size = a.batch
     G = torch.randn(n, 32, device=dev)
@@ -166,7 +170,7 @@ def train_mode(a, dev):
     masks = masks.reshape(-1)[:13 * n].cpu().numpy().view(np.uint32).reshape(13, n)
     useful, _ = flop_counts(masks, levels, models.layer_info())
     wgrad_flop = float(sum(u for (mp, _), u in zip(LAYER_MAPS, useful) if mp is not None))
-    line = dict(tool="featnet_time", mode="train", train_precision=a.train_precision, config=a.config, batch=a.batch, n=n, levels=levels, iters=a.iters,
+    line = dict(tool="featnet_time", mode="train", train_precision=a.train_precision, fused_norm=bool(a.fused_norm), config=a.config, batch=a.batch, n=n, levels=levels, iters=a.iters,
                 ms_per_call=dict(fused_eval_forward=round(ms_fused, 4), layerwise_forward=round(ms_fwd, 4),
                                  forward_backward=round(ms_step, 4), backward=round(ms_step - ms_fwd, 4)),
                 wgrad_useful_gflop=round(wgrad_flop / 1e9, 3))
@@ -189,6 +193,7 @@ def main(argv=None):
     ap.add_argument("--stats-steps", type=int, default=5, help="--train: the --profile-steps of that run")
     ap.add_argument("--train-precision", default="f32", choices=list(models.PRECISIONS),
                     help="--train: operand precision of the layer-wise forward and backward")
+    ap.add_argument("--fused-norm", action="store_true", help="--train: batch norm, residual and ReLU on the fused HIP kernels")
     ap.add_argument("--config", default="KT", choices=["KT", "NS"])
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)

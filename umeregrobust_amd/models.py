@@ -46,7 +46,13 @@ operand precision of the layer-wise path, whatever `precision` is -- the sevente
 run `sparse_conv(..., precision="f16")` / `linear(..., precision="f16")`: f16 operands in the forward and in both gradients,
 f32 sums, parameters, gradients and saved activations; conv1, `final`, batch norm and the rest stay f32.  Deterministic.  No
 range check per layer (it would synchronise): an activation beyond +-65504 reaches the next layer as infinity and the loss as
-a non-finite value, which the training driver names where it reads the loss."""
+a non-finite value, which the training driver names where it reads the loss.
+
+`ResUNetSmall2(..., trainable=True, fused_norm=True)` (include/umereg_bn_act.h, umeregrobust_amd/bn_act.py; opt-in, the default
+path and its bits are unchanged): every `bn(conv)` and every `relu(bn(conv) + h)` of the layer-wise path is one
+`bn_act.batch_norm_act` (HIP statistics, apply and backward kernels; fp64 sums over a fixed tree), mlp1's ReLU is `bn_act.relu`,
+and with train_precision="f16" the backward scale comes from `bn_act.grad_scale_device`.  Parameters, buffers, state-dict keys and
+`packed_parameters` are the same modules' as ever: a checkpoint of either path loads into the other."""
 import ctypes
 
 import torch
@@ -203,9 +209,13 @@ class ResUNetSmall2(nn.Module):
     STRIDES = [1, 2, 2, 2, 3]
 
     def __init__(self, in_channels=1, out_channels=32, bn_momentum=0.1, normalize_feature=True, D=3, trainable=False,
-                 precision="f32", train_precision="f32"):
+                 precision="f32", train_precision="f32", fused_norm=False):
         super().__init__()
         self.trainable = bool(trainable)
+        self.fused_norm = bool(fused_norm)
+        if self.fused_norm and not self.trainable:
+            raise ValueError("ResUNetSmall2(fused_norm=True) selects the kernels of the layer-wise path's batch norm: it needs "
+                             "trainable=True")
         self.precision = check_precision(precision)
         if train_precision not in PRECISIONS:
             raise ValueError(f"train_precision must be one of {PRECISIONS}, got {train_precision!r}")
@@ -350,22 +360,36 @@ class ResUNetSmall2(nn.Module):
         relu = torch.relu
         tp = self.train_precision                     # (conv1, C_in = 1, stays f32 inside sparse_conv)
 
+        fused = self.fused_norm                       # batch norm, residual, ReLU and the f16 scale on include/umereg_bn_act.h
+        if fused:
+            from . import bn_act
+            relu = bn_act.relu
+
+        def conv(h, kernel, table):
+            return sc.sparse_conv(h, kernel, maps, table, precision=tp, fused_scale=fused)
+
+        def bn(norm, v):
+            return bn_act.batch_norm_act(v, norm.bn) if fused else norm.bn(v)
+
         def block(h, l, blk):
-            return relu(blk.norm1.bn(sc.sparse_conv(h, blk.conv1.kernel, maps, l, precision=tp)) + h)
+            v = conv(h, blk.conv1.kernel, l)
+            if fused:
+                return bn_act.batch_norm_act(v, blk.norm1.bn, residual=h, relu=True)
+            return relu(blk.norm1.bn(v) + h)
 
         skips = []
         h = F.detach().to(torch.float32)
         for l in range(5):
-            conv, norm, blk = getattr(self, f"conv{l + 1}"), getattr(self, f"norm{l + 1}"), getattr(self, f"block{l + 1}")
-            h = block(norm.bn(sc.sparse_conv(h, conv.kernel, maps, 0 if l == 0 else 5 + l - 1, precision=tp)), l, blk)
+            cv, norm, blk = getattr(self, f"conv{l + 1}"), getattr(self, f"norm{l + 1}"), getattr(self, f"block{l + 1}")
+            h = block(bn(norm, conv(h, cv.kernel, 0 if l == 0 else 5 + l - 1)), l, blk)
             skips.append(h)
         s4 = h
         cats = [None] * 4
         for l in range(3, -1, -1):
-            conv, norm, blk = getattr(self, f"conv{l + 1}_tr"), getattr(self, f"norm{l + 1}_tr"), getattr(self, f"block{l + 1}_tr")
-            tr = block(norm.bn(sc.sparse_conv(h, conv.kernel, maps, 9 + l, precision=tp)), l, blk)
+            cv, norm, blk = getattr(self, f"conv{l + 1}_tr"), getattr(self, f"norm{l + 1}_tr"), getattr(self, f"block{l + 1}_tr")
+            tr = block(bn(norm, conv(h, cv.kernel, 9 + l)), l, blk)
             h = cats[l] = torch.cat([tr, skips[l]], dim=1)
-        hidden = relu(sc.linear(h, self.mlp1.kernel, precision=tp, maps=maps))
+        hidden = relu(sc.linear(h, self.mlp1.kernel, precision=tp, maps=maps, fused_scale=fused))
         o = sc.linear(hidden, self.final.kernel) + self.final.bias
         o = o / o.norm(dim=1, keepdim=True)
         inv = torch.empty_like(maps.perm)

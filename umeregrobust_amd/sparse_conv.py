@@ -266,10 +266,18 @@ def grad_scale(dy):
     return e, _pow2(e), _pow2(-e)
 
 
+def _scale_of(dy, fused):
+    """`grad_scale(dy)`, or with `fused` the same three scalars from the kernels of include/umereg_bn_act.h"""
+    if fused:
+        from . import bn_act
+        return bn_act.grad_scale_device(dy)
+    return grad_scale(dy)
+
+
 class _SparseConv(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, kernel, maps, table, precision="f32"):
-        ctx.maps, ctx.table, ctx.precision = maps, table, precision
+    def forward(ctx, x, kernel, maps, table, precision="f32", fused_scale=False):
+        ctx.maps, ctx.table, ctx.precision, ctx.fused_scale = maps, table, precision, fused_scale
         ctx.save_for_backward(x, kernel)
         return conv_raw(x, kernel.detach(), maps, table, precision=precision)
 
@@ -281,20 +289,20 @@ class _SparseConv(torch.autograd.Function):
         dx = dw = None
         if ctx.precision == "f16":
             # include/umereg_sparse_conv_f16.h: one power-of-two scale per layer, computed on the device; dy 2^e feeds both gradients
-            _, up, down = grad_scale(dy)
+            _, up, down = _scale_of(dy, ctx.fused_scale)
             dys = dy * up
             if ctx.needs_input_grad[0]:
                 adj, mirror = adjoint(table)
                 dx = conv_raw(dys, kernel.detach(), maps, adj, transpose=True, mirror=mirror, precision="f16", scale=maps.ones * down)
             if ctx.needs_input_grad[1]:
                 dw = wgrad_raw(x, dys, maps, table, precision="f16") * down
-            return dx, dw, None, None, None
+            return dx, dw, None, None, None, None
         if ctx.needs_input_grad[0]:
             adj, mirror = adjoint(table)
             dx = conv_raw(dy, kernel.detach(), maps, adj, transpose=True, mirror=mirror)
         if ctx.needs_input_grad[1]:
             dw = wgrad_raw(x, dy, maps, table)
-        return dx, dw, None, None, None
+        return dx, dw, None, None, None, None
 
 
 class _SparseConv1(torch.autograd.Function):
@@ -313,11 +321,12 @@ class _SparseConv1(torch.autograd.Function):
         return None, dw, None
 
 
-def sparse_conv(x, kernel, maps, table, precision="f32"):
+def sparse_conv(x, kernel, maps, table, precision="f32", fused_scale=False):
     """Differentiable sparse convolution over table `table` of `maps`.  x: f32 [rows of the table's input level, C_in] in the
     level's row order -- for a [27, 1, 32] kernel (conv1, table 0): [n, 1] in INPUT row order, and it may not require grad;
     kernel: [27, C_in, C_out].  -> f32 [rows of the table's output level, C_out].  precision="f16": f16 operands in the forward
-    and in both gradients (module docstring); a C_in = 1 kernel (conv1) stays f32 either way."""
+    and in both gradients (module docstring); a C_in = 1 kernel (conv1) stays f32 either way.  fused_scale=True (f16 only): the
+    backward takes its scale from `bn_act.grad_scale_device` (two kernels) instead of `grad_scale` (the same scalars bit for bit)."""
     _models.check_precision(precision)
     if not 0 <= table < N_TABLES:
         raise ValueError(f"sparse_conv: table {table} outside [0, {N_TABLES})")
@@ -332,7 +341,7 @@ def sparse_conv(x, kernel, maps, table, precision="f32"):
             raise RuntimeError("sparse_conv: conv1 has no input gradient (the network's input features are constants); "
                                "detach the input features")
         return _SparseConv1.apply(x, kernel, maps)
-    return _SparseConv.apply(x, kernel, maps, table, precision)
+    return _SparseConv.apply(x, kernel, maps, table, precision, bool(fused_scale))
 
 
 def _block_wgrad(x, dy):
@@ -367,8 +376,8 @@ class _LinearF16(torch.autograd.Function):
     table -1 (x and W, the scaled dy and W^T rounded to f16; sums f32); the weight gradient stays `_Linear`'s f32 block sum."""
 
     @staticmethod
-    def forward(ctx, x, W, maps):
-        ctx.maps = maps
+    def forward(ctx, x, W, maps, fused_scale=False):
+        ctx.maps, ctx.fused_scale = maps, fused_scale
         ctx.save_for_backward(x, W)
         return conv_raw(x, W.detach(), maps, -1, precision="f16")
 
@@ -378,22 +387,22 @@ class _LinearF16(torch.autograd.Function):
         dy = dy.contiguous()
         dx = dw = None
         if ctx.needs_input_grad[0]:
-            _, up, down = grad_scale(dy)
+            _, up, down = _scale_of(dy, ctx.fused_scale)
             dx = conv_raw(dy * up, W.detach(), ctx.maps, -1, transpose=True, precision="f16", scale=ctx.maps.ones * down)
         if ctx.needs_input_grad[1]:
             dw = _block_wgrad(x, dy)
-        return dx, dw, None
+        return dx, dw, None, None
 
 
-def linear(x, W, precision="f32", maps=None):
+def linear(x, W, precision="f32", maps=None, fused_scale=False):
     """x [rows, C_in] @ W [C_in, C_out] with a block-summed weight gradient (the 1x1 layers of the network).  precision="f16"
     (mlp1): x [rows of level 0 of `maps`, C_in], operands of the forward and of the input gradient rounded to f16, channel counts
-    multiples of 32; the weight gradient stays the f32 block sum."""
+    multiples of 32; the weight gradient stays the f32 block sum.  fused_scale: as in `sparse_conv` (f16 only)."""
     _models.check_precision(precision)
     if precision == "f16":
         if maps is None:
             raise ValueError("linear: precision='f16' runs on the HIP convolution and needs the CoordinateMaps of its rows (maps=...)")
         if x.device.type != "cuda" or W.device.type != "cuda":
             raise RuntimeError("linear: CPU tensors given; umeregrobust_amd has no CPU fallback (move the input to the GPU)")
-        return _LinearF16.apply(x, W, maps)
+        return _LinearF16.apply(x, W, maps, bool(fused_scale))
     return _Linear.apply(x, W)
