@@ -13,6 +13,9 @@
 `--precision f16`: the f16-operand forward (include/umereg_featnet_f16.h); the line carries a "precision" key, and the peak
 fraction stays relative to the fp32 matrix peak so that the two precisions' lines compare.
 
+`--conv-mode pairs`: the pair-compacted engine (include/umereg_sparse_conv_pairs.h) in the fused forward and in `--train`; the line
+carries a "conv_mode" key, and the issued MFMA work and its useful share are those of the chosen engine.
+
 `--train`: the trainable network (ResUNetSmall2(trainable=True), train mode) at the same cloud, or with `--batch B` at B such
 clouds in one call (16 KITTI-test clouds are 800 000 rows, the upper end of the reference's training shape: batch 8 x
 max_pc_size 100 000).  One JSON line with ms per call of the fused eval forward (re-measured here, same session), the layer-
@@ -57,8 +60,10 @@ def voxel_cloud(seed, config):
     return np.concatenate([np.zeros((len(c), 1), np.int64), c], axis=1).astype(np.int32)
 
 
-def flop_counts(masks, levels, info):
-    """-> (useful flops per layer, issued MFMA flops per layer)"""
+def flop_counts(masks, levels, info, conv_mode="union"):
+    """-> (useful flops per layer, issued MFMA flops per layer); issued: what the engine `conv_mode` feeds the matrix unit -- "union":
+    a tile issues every offset some row of it uses, for all its rows; "pairs" (csrc/conv_pairs_plan.h): per tile of 128 rows and
+    offset, the active rows rounded up to blocks of 32 (1x1 layers run the union engine's kernel in both modes)"""
     pop = np.array([bin(i).count("1") for i in range(1 << 9)], dtype=np.int64)
 
     def popcount(m):
@@ -76,6 +81,12 @@ def flop_counts(masks, levels, info):
         else:
             m = masks[mp, :rows]
             useful.append(per * int(popcount(m).sum()))
+            if conv_mode == "pairs":
+                tm = 128
+                pad = np.zeros((-rows) % tm, dtype=m.dtype)
+                act = ((np.concatenate([m, pad])[:, None] >> np.arange(27, dtype=m.dtype)) & 1).reshape(-1, tm, 27).sum(axis=1)
+                issued.append(0 if i in VALU_LAYERS else per * 32 * int(((act + 31) // 32).sum()))
+                continue
             tm = 64 if cout % 64 == 0 else 128
             pad = np.zeros((-rows) % tm, dtype=m.dtype)
             tiles = np.bitwise_or.reduce(np.concatenate([m, pad]).reshape(-1, tm), axis=1)
@@ -85,7 +96,7 @@ def flop_counts(masks, levels, info):
 
 
 # kernel groups of a profiled training run (rocprofv3 kernel_stats.csv, by kernel name)
-GROUPS = (("conv_forward_and_input_gradient", ("fn_conv_kernel", "fn_conv1_kernel", "fn_conv_f16_kernel")),
+GROUPS = (("conv_forward_and_input_gradient", ("fn_conv_kernel", "fn_conv1_kernel", "fn_conv_f16_kernel", "cp_conv_kernel", "cp_conv_f16_kernel")),
           ("weight_gradient", ("wg_mfma_kernel", "wg_c1_kernel", "wg_reduce_kernel", "wg_f16_kernel")),
           ("repack", ("wg_repack_kernel",)),
           ("norm_act", ("bn_stats_kernel", "bn_fwd_apply_kernel", "bn_bwd_reduce_kernel", "bn_bwd_apply_kernel", "gs_partial_kernel",
@@ -121,7 +132,8 @@ def train_mode(a, dev):
     coords = torch.from_numpy(np.concatenate(clouds)).to(dev)
     n = coords.shape[0]
     torch.manual_seed(a.seed)
-    m = models.ResUNetSmall2(in_channels=1, out_channels=32, trainable=True, train_precision=a.train_precision, fused_norm=a.fused_norm).to(dev)
+    m = models.ResUNetSmall2(in_channels=1, out_channels=32, trainable=True, train_precision=a.train_precision, fused_norm=a.fused_norm,
+                             conv_mode=a.conv_mode).to(dev)
     st = SparseTensor(torch.ones(n, 1, device=dev), coordinates=coords)
     st._batch_size = a.batch
     G = torch.randn(n, 32, device=dev)
@@ -170,7 +182,7 @@ def train_mode(a, dev):
     masks = masks.reshape(-1)[:13 * n].cpu().numpy().view(np.uint32).reshape(13, n)
     useful, _ = flop_counts(masks, levels, models.layer_info())
     wgrad_flop = float(sum(u for (mp, _), u in zip(LAYER_MAPS, useful) if mp is not None))
-    line = dict(tool="featnet_time", mode="train", train_precision=a.train_precision, fused_norm=bool(a.fused_norm), config=a.config, batch=a.batch, n=n, levels=levels, iters=a.iters,
+    line = dict(tool="featnet_time", mode="train", conv_mode=a.conv_mode, train_precision=a.train_precision, fused_norm=bool(a.fused_norm), config=a.config, batch=a.batch, n=n, levels=levels, iters=a.iters,
                 ms_per_call=dict(fused_eval_forward=round(ms_fused, 4), layerwise_forward=round(ms_fwd, 4),
                                  forward_backward=round(ms_step, 4), backward=round(ms_step - ms_fwd, 4)),
                 wgrad_useful_gflop=round(wgrad_flop / 1e9, 3))
@@ -194,6 +206,8 @@ def main(argv=None):
     ap.add_argument("--train-precision", default="f32", choices=list(models.PRECISIONS),
                     help="--train: operand precision of the layer-wise forward and backward")
     ap.add_argument("--fused-norm", action="store_true", help="--train: batch norm, residual and ReLU on the fused HIP kernels")
+    ap.add_argument("--conv-mode", default="union", choices=list(models.CONV_MODES),
+                    help="engine of the 27-offset convolutions (pairs: include/umereg_sparse_conv_pairs.h), fused forward and --train alike")
     ap.add_argument("--config", default="KT", choices=["KT", "NS"])
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
@@ -205,7 +219,7 @@ def main(argv=None):
     if a.train:
         return train_mode(a, dev)
     torch.manual_seed(a.seed)
-    m = models.ResUNetSmall2(in_channels=1, out_channels=32)
+    m = models.ResUNetSmall2(in_channels=1, out_channels=32, conv_mode=a.conv_mode)
     with torch.no_grad():
         for mod in m.modules():
             if isinstance(mod, torch.nn.BatchNorm1d):
@@ -232,17 +246,17 @@ def main(argv=None):
         return e0.elapsed_time(e1) / a.iters
 
     ms_maps = timed(lambda: models.build_maps_raw(coords, 1, ws, status))
-    ms_total = timed(lambda: models.forward_raw(coords, feat, 1, params, ws, out, status, a.precision))
+    ms_total = timed(lambda: models.forward_raw(coords, feat, 1, params, ws, out, status, a.precision, a.conv_mode))
     levels = models.check_status(status)
     masks = models.buffer_view(ws, n, 1, models.BUF_MASKS, n, torch.int32)      # [13][n] words, viewed as [n, 13]
     masks = masks.reshape(-1)[:13 * n].cpu().numpy().view(np.uint32).reshape(13, n)
     info = models.layer_info()
-    useful, issued = flop_counts(masks, levels, info)
+    useful, issued = flop_counts(masks, levels, info, a.conv_mode)
     ms_conv = ms_total - ms_maps
     useful_total = float(sum(useful))
     mfma_useful = float(sum(u for i, u in enumerate(useful) if i not in VALU_LAYERS))
     names = [name.split(".")[0] if name.startswith("block") and ".conv1" in name else name for name, _ in models.LAYERS]
-    line = dict(tool="featnet_time", precision=a.precision, config=a.config, n=n, levels=levels, iters=a.iters,
+    line = dict(tool="featnet_time", precision=a.precision, conv_mode=a.conv_mode, config=a.config, n=n, levels=levels, iters=a.iters,
                 ms_per_cloud=dict(maps=round(ms_maps, 4), conv=round(ms_conv, 4), total=round(ms_total, 4)),
                 useful_gflop=round(useful_total / 1e9, 3),
                 useful_tflops_in_conv=round(useful_total / (ms_conv * 1e-3) / 1e12, 2),

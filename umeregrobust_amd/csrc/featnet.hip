@@ -15,11 +15,15 @@
 //
 // The f16-operand inference mode (include/umereg_featnet_f16.h) is fn_conv_f16_kernel, the twin of fn_conv_kernel on
 // v_mfma_f32_32x32x16_f16, launched for layers 1..18 by the same forward; conv1 and `final` are the f32 kernels in both modes.
+//
+// The entries of include/umereg_sparse_conv_pairs.h are the same two host paths (fn_forward, fn_sparse_conv) with `pairs` set:
+// fn_launch_conv then hands every 27-offset layer to sparse_conv_pairs.hip, and keeps the 1x1 layers here.
 #include <math.h>
 
 #include "sparse.h"
 #include "umereg_featnet_f16.h"
 #include "umereg_sparse_conv.h"
+#include "umereg_sparse_conv_pairs.h"
 
 namespace umereg {
 
@@ -55,19 +59,6 @@ FnParamOffsets fn_params()
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kKC = 32;     // input channels per staged slice
-
-struct ConvArgs {
-    const float* in;        // input rows (already offset to the first input column)
-    const float* W;         // [K][cin][cout]
-    const float* scale;
-    const float* shift;
-    const float* res;       // residual rows [., ld_res] or null
-    float* out;             // output rows (already offset to the first output column)
-    const int* nbr;         // [rows][27] or null (K = 1: output row o reads input row o)
-    const unsigned int* mask;
-    const int32_t* n_out;   // output rows (device)
-    int ld_in, ld_res, ld_out, cin, cout, K, relu;
-};
 
 template <int TM, int TN>
 __global__ __launch_bounds__(256) void fn_conv_kernel(ConvArgs a)
@@ -227,11 +218,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 constexpr int kKP = kKC + 8;            // f16 per padded LDS row
 constexpr float kF16Max = 65504.f;
 
-struct ConvArgsF16 {
-    ConvArgs c;
-    int32_t* range;         // status word that takes UMEREG_FN_ERR_F16_RANGE when a stored value is not within +-65504 (or null)
-};
-
 template <int TM, int TN>
 __global__ __launch_bounds__(256) void fn_conv_f16_kernel(ConvArgsF16 args)
 {
@@ -332,9 +318,12 @@ __global__ __launch_bounds__(256) void fn_conv_f16_kernel(ConvArgsF16 args)
     if (args.range && out_of_range) atomicOr(args.range, UMEREG_FN_ERR_F16_RANGE);
 }
 
-// one convolution launch over at most `rows_bound` output rows: 64 x 64 tiles where C_out allows, else 128 x 32; `range` as ConvArgsF16
-int fn_launch_conv(const ConvArgs& a, bool f16, int32_t* range, int rows_bound, hipStream_t st)
+// one convolution launch over at most `rows_bound` output rows: 64 x 64 tiles where C_out allows, else 128 x 32; `range` as ConvArgsF16.
+// `pairs`: a 27-offset layer goes to the pair-compacted engine of sparse_conv_pairs.hip instead (a 1x1 layer has every row active and
+// stays here)
+int fn_launch_conv(const ConvArgs& a, bool f16, int32_t* range, int rows_bound, hipStream_t st, bool pairs = false)
 {
+    if (pairs && a.K > 1) return fn_launch_conv_pairs(a, f16, range, rows_bound, st);
     const bool wide = a.cout % 64 == 0;
     const dim3 grid = wide ? dim3((rows_bound + 63) / 64, a.cout / 64) : dim3((rows_bound + 127) / 128, a.cout / 32);
     const ConvArgsF16 h{a, range};
@@ -354,6 +343,7 @@ struct Fwd {
     int32_t* status;
     hipStream_t st;
     bool f16;               // layers 1..18 on fn_conv_f16_kernel
+    bool pairs;             // layers 1..17 on the pair-compacted engine (include/umereg_sparse_conv_pairs.h)
 
     float* buf(size_t off) const { return reinterpret_cast<float*>(ws + off); }
 
@@ -367,7 +357,7 @@ struct Fwd {
         a.res = res, a.out = out, a.nbr = t.nbr, a.mask = t.mask, a.n_out = status + 1 + t.level;
         a.ld_in = ld_in, a.ld_res = ld_res, a.ld_out = ld_out, a.cin = L.cin, a.cout = L.cout, a.K = L.K, a.relu = relu ? 1 : 0;
         // the range check covers what a later f16 layer gathers: mlp1's output feeds `final`, which is f32
-        return fn_launch_conv(a, f16, i < 18 ? status : nullptr, w.n, st);
+        return fn_launch_conv(a, f16, i < 18 ? status : nullptr, w.n, st, pairs);
     }
 };
 
@@ -439,7 +429,7 @@ UMEREG_API int umereg_featnet_build_maps(const int32_t* coords, int n, int batch
 namespace {
 // the forward pass of both precisions (f16: layers 1..18 on fn_conv_f16_kernel; conv1 and `final` are the f32 kernels either way)
 int fn_forward(const int32_t* coords, const float* feat, int n, int batch, const float* params, float* out, int32_t* status,
-               void* workspace, size_t workspace_bytes, void* stream, bool f16)
+               void* workspace, size_t workspace_bytes, void* stream, bool f16, bool pairs = false)
 {
     UMEREG_REQUIRE(feat && params && out, "featnet_forward: null pointer");
     UMEREG_REQUIRE(((uintptr_t)params & 15) == 0 && ((uintptr_t)out & 15) == 0, "featnet_forward: params and out must be 16-byte aligned");
@@ -449,7 +439,7 @@ int fn_forward(const int32_t* coords, const float* feat, int n, int batch, const
     char* ws = (char*)workspace;
     if (int rc = fn_build_maps(coords, n, batch, ws, status, st)) return rc;
 
-    Fwd f{params, fn_params(), ws, w, status, st, f16};
+    Fwd f{params, fn_params(), ws, w, status, st, f16, pairs};
     float* X = f.buf(w.off_x);
     float* S4 = f.buf(w.off_s4);
     float* cat[4];
@@ -507,7 +497,7 @@ namespace {
 // the plain convolution of both precisions; f16 also takes table -1: the 1x1 layer over level 0 (W [C_in][C_out])
 int fn_sparse_conv(const void* workspace, size_t workspace_bytes, const int32_t* status, int n, int table, const float* in, int ld_in,
                    const float* W, int c_in, int c_out, const float* scale, const float* shift, float* out, int ld_out, int accumulate,
-                   void* stream, bool f16)
+                   void* stream, bool f16, bool pairs = false)
 {
     UMEREG_REQUIRE(workspace && status && in && W && scale && shift && out, "sparse_conv: null pointer");
     UMEREG_REQUIRE(n > 0, "sparse_conv: n must be positive (got %d)", n);
@@ -526,7 +516,7 @@ int fn_sparse_conv(const void* workspace, size_t workspace_bytes, const int32_t*
                                                                                                              // element is read, then written, by one thread)
     a.nbr = t.nbr, a.mask = t.mask, a.n_out = status + 1 + t.level;
     a.ld_in = ld_in, a.ld_res = ld_out, a.ld_out = ld_out, a.cin = c_in, a.cout = c_out, a.K = table >= 0 ? kFnVol : 1, a.relu = 0;
-    return fn_launch_conv(a, f16, nullptr, n, (hipStream_t)stream);
+    return fn_launch_conv(a, f16, nullptr, n, (hipStream_t)stream, pairs);
 }
 }  // namespace
 
@@ -544,6 +534,22 @@ UMEREG_API int umereg_sparse_conv_f16(const void* workspace, size_t workspace_by
 {
     return fn_sparse_conv(workspace, workspace_bytes, status, n, table, in, ld_in, W, c_in, c_out, scale, shift, out, ld_out, accumulate,
                           stream, true);
+}
+
+// ---- include/umereg_sparse_conv_pairs.h: the same two host paths with the 27-offset layers on sparse_conv_pairs.hip -----------------
+
+UMEREG_API int umereg_featnet_forward_pairs(const int32_t* coords, const float* feat, int n, int batch, const float* params, float* out,
+                                            int32_t* status, void* workspace, size_t workspace_bytes, void* stream, int f16)
+{
+    return fn_forward(coords, feat, n, batch, params, out, status, workspace, workspace_bytes, stream, f16 != 0, true);
+}
+
+UMEREG_API int umereg_sparse_conv_pairs(const void* workspace, size_t workspace_bytes, const int32_t* status, int n, int table,
+                                        const float* in, int ld_in, const float* W, int c_in, int c_out, const float* scale,
+                                        const float* shift, float* out, int ld_out, int accumulate, void* stream, int f16)
+{
+    return fn_sparse_conv(workspace, workspace_bytes, status, n, table, in, ld_in, W, c_in, c_out, scale, shift, out, ld_out, accumulate,
+                          stream, f16 != 0, true);
 }
 
 UMEREG_API int umereg_sparse_conv1_f32(const void* workspace, size_t workspace_bytes, const int32_t* status, int n, const float* feat,

@@ -1,6 +1,6 @@
-// sparse.h -- coordinate maps of the sparse feature network (sparse_map.hip builds them, featnet.hip and sparse_wgrad.hip convolve
-// over them): the workspace carve-up with its check and its table pointers, the coordinate key, the kernel-offset table.  Not part
-// of the C ABI.
+// sparse.h -- coordinate maps of the sparse feature network (sparse_map.hip builds them; featnet.hip, sparse_conv_pairs.hip and
+// sparse_wgrad.hip convolve over them): the workspace carve-up with its check and its table pointers, the coordinate key, the
+// kernel-offset table, and the argument record of the convolution kernels of both engines.  Not part of the C ABI.
 //
 // MinkowskiEngine 0.5.4 semantics restated here (parity unpinned):
 //   * strided output map: unique(floor(c / (ts s)) ts s) per axis, batch index kept (fn_coarsen);
@@ -134,6 +134,29 @@ inline int fn_check_ws(const char* who, const void* ws, size_t bytes, int n)
     set_error("%s: workspace too small or not 256-byte aligned (%zu < %zu)", who, bytes, need);
     return UMEREG_EWORKSPACE;
 }
+
+// one convolution launch as the kernels of featnet.hip (the "union" engine) and of sparse_conv_pairs.hip (the "pairs" engine) take it
+struct ConvArgs {
+    const float* in;        // input rows (already offset to the first input column)
+    const float* W;         // [K][cin][cout]
+    const float* scale;
+    const float* shift;
+    const float* res;       // residual rows [., ld_res] or null
+    float* out;             // output rows (already offset to the first output column)
+    const int* nbr;         // [rows][27] or null (K = 1: output row o reads input row o)
+    const unsigned int* mask;
+    const int32_t* n_out;   // output rows (device)
+    int ld_in, ld_res, ld_out, cin, cout, K, relu;
+};
+
+struct ConvArgsF16 {
+    ConvArgs c;
+    int32_t* range;         // status word that takes UMEREG_FN_ERR_F16_RANGE when a stored value is not within +-65504 (or null)
+};
+
+// a 27-offset layer on the pair-compacted engine (sparse_conv_pairs.hip; include/umereg_sparse_conv_pairs.h) over at most
+// `rows_bound` output rows; `range` as ConvArgsF16
+int fn_launch_conv_pairs(const ConvArgs& a, bool f16, int32_t* range, int rows_bound, hipStream_t st);
 
 // builds every level and every neighbour table of a forward pass (sparse_map.hip); status as umereg_featnet_forward_f32
 int fn_build_maps(const int32_t* coords, int n, int batch, char* ws, int32_t* status, hipStream_t st);

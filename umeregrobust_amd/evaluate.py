@@ -293,13 +293,15 @@ def synthetic_pairs(benchmark, indices, device):
                    tgt_feat=t(p.tgt_feat)[None], gt_tform=t(p.gt_tform))
 
 
-def cached_pairs(cache, cache_raw, split, indices, args, device, rng=np.random, checkpoint=None, feature_precision="f32"):
+def cached_pairs(cache, cache_raw, split, indices, args, device, rng=np.random, checkpoint=None, feature_precision="f32", conv_mode="union"):
     """Pairs from the reference's pre-processed cache (`datasets.CachedPairDataset`) through the reference's
     collate (`batch_collate_fn_dset`, batch_size 1: the dilution to args.max_pc_size with the host RNG), as the evaluation
     loop unpacks them (evaluate.py:175-187).  Without `checkpoint` the cache files must carry the feature network's outputs
     (`src_feat` / `tgt_feat`); with it (a weight file of the reference's save_checkpoint schema, or a state dict) the
     features are computed from the collate's coordinates by `models.ResUNetSmall2` (evaluate.py:163-165, :178-179,
-    :190-192), with `feature_precision` "f32" or "f16" (f16 operands, f32 accumulation: include/umereg_featnet_f16.h).  The raw clouds of the correlation stage (`dset_no_nksr[itr]`, :260) come from `cache_raw` (default: the
+    :190-192), with `feature_precision` "f32" or "f16" (f16 operands, f32 accumulation: include/umereg_featnet_f16.h) and
+    `conv_mode` "union" or "pairs" (the pair-compacted convolution engine, the same features bit for bit:
+    include/umereg_sparse_conv_pairs.h).  The raw clouds of the correlation stage (`dset_no_nksr[itr]`, :260) come from `cache_raw` (default: the
     same files)."""
     from .datasets import CachedPairDataset, batch_collate_fn_dset
     kind = getattr(args, "dataset", "kitti")
@@ -308,7 +310,7 @@ def cached_pairs(cache, cache_raw, split, indices, args, device, rng=np.random, 
         from .datasets import checkpoint_state_dict
         from .models import ResUNetSmall2
         from .sparse import SparseTensor
-        net = ResUNetSmall2(in_channels=1, out_channels=getattr(args, "out_ch", 32), precision=feature_precision)
+        net = ResUNetSmall2(in_channels=1, out_channels=getattr(args, "out_ch", 32), precision=feature_precision, conv_mode=conv_mode)
         net.load_state_dict(checkpoint_state_dict(checkpoint))
         net = net.to(device).eval()
     ds = CachedPairDataset(cache, split=split, with_features=net is None, dataset=kind)
@@ -350,6 +352,9 @@ def main(argv=None):
     parser.add_argument("--feature-precision", choices=["f32", "f16"], default="f32",
                         help="with --checkpoint: operand precision of the feature network (f16: f16 operands on the f16 matrix "
                              "instructions, f32 accumulation; include/umereg_featnet_f16.h)")
+    parser.add_argument("--conv-mode", choices=["union", "pairs"], default="union",
+                        help="with --checkpoint: engine of the feature network's 27-offset convolutions (pairs: per offset only the rows "
+                             "that have the neighbour reach the matrix unit; same features; include/umereg_sparse_conv_pairs.h)")
     parser.add_argument("--synthetic", type=int, default=8, help="number of synthetic pairs when no --pairs are given")
     parser.add_argument("--no-refine", action="store_true", help="skip the ICP refinement (evaluate.py:301)")
     cli = parser.parse_args(argv)
@@ -367,7 +372,7 @@ def main(argv=None):
         print(f"Evaluate {args.dataset} Benchmark: {args.benchmark} config file: {config_path}")
     if cli.cache:
         pairs = cached_pairs(cli.cache, cli.cache_raw, args.split, lambda n: shard_indices(n, rank, world), args, device, rng=rng,
-                             checkpoint=cli.checkpoint, feature_precision=cli.feature_precision)
+                             checkpoint=cli.checkpoint, feature_precision=cli.feature_precision, conv_mode=cli.conv_mode)
     elif cli.pairs:
         files = []
         for p in cli.pairs:

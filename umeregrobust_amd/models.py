@@ -52,7 +52,13 @@ a non-finite value, which the training driver names where it reads the loss.
 path and its bits are unchanged): every `bn(conv)` and every `relu(bn(conv) + h)` of the layer-wise path is one
 `bn_act.batch_norm_act` (HIP statistics, apply and backward kernels; fp64 sums over a fixed tree), mlp1's ReLU is `bn_act.relu`,
 and with train_precision="f16" the backward scale comes from `bn_act.grad_scale_device`.  Parameters, buffers, state-dict keys and
-`packed_parameters` are the same modules' as ever: a checkpoint of either path loads into the other."""
+`packed_parameters` are the same modules' as ever: a checkpoint of either path loads into the other.
+
+`ResUNetSmall2(..., conv_mode="pairs")` (include/umereg_sparse_conv_pairs.h, csrc/sparse_conv_pairs.hip; opt-in, the default is
+"union"): the seventeen 27-offset layers after conv1 run on the pair-compacted engine, which feeds the matrix unit, per offset,
+only the rows of a tile that have that neighbour -- in the fused call and in the layer-wise path (forward and input gradient; the
+weight gradient has no mode).  The values are the union engine's bit for bit; the mode combines freely with `precision`,
+`trainable`, `train_precision` and `fused_norm`, and leaves state dict and checkpoints alone."""
 import ctypes
 
 import torch
@@ -87,6 +93,7 @@ BUF_COORDS0, BUF_CAT0, BUF_S4, BUF_HIDDEN, BUF_PERM, BUF_MASKS = 0, 5, 9, 10, 11
 ERR_RANGE, ERR_DUPLICATE = 1, 2
 ERR_F16_RANGE = 4           # include/umereg_featnet_f16.h
 PRECISIONS = ("f32", "f16")
+CONV_MODES = ("union", "pairs")     # the engine of the 27-offset layers; "pairs": include/umereg_sparse_conv_pairs.h
 
 # the packed parameter block's layer order (umereg_featnet_layer_info) -> (kernel, batch norm or None)
 LAYERS = (
@@ -116,6 +123,13 @@ def check_precision(precision):
     return precision
 
 
+def check_conv_mode(conv_mode):
+    """-> `conv_mode`, one of CONV_MODES ("union"; "pairs": the pair-compacted engine, the same values); else ValueError"""
+    if conv_mode not in CONV_MODES:
+        raise ValueError(f"conv_mode must be one of {CONV_MODES}, got {conv_mode!r}")
+    return conv_mode
+
+
 def layer_info():
     """[(K, C_in, C_out, offset of W, offset of scale)] of the packed parameter block, from the library."""
     lib = load_native()
@@ -140,15 +154,23 @@ def buffer_view(ws, n, batch, which, rows, dtype=torch.float32):
     return ws[off.value:off.value + rows * cols.value * esz].view(dtype).view(rows, cols.value)
 
 
-def forward_raw(coords, feat, batch, params, ws, out, status, precision="f32"):
+def forward_raw(coords, feat, batch, params, ws, out, status, precision="f32", conv_mode="union"):
     """One forward pass through the C ABI on the current stream; no host sync, no error check of `status`.  precision="f16":
-    umereg_featnet_forward_f16 (include/umereg_featnet_f16.h), same buffers."""
+    umereg_featnet_forward_f16 (include/umereg_featnet_f16.h), same buffers.  conv_mode="pairs": umereg_featnet_forward_pairs
+    (include/umereg_sparse_conv_pairs.h) in the chosen precision, same buffers, same values."""
     check_precision(precision)
+    check_conv_mode(conv_mode)
     lib = load_native()
     n = coords.shape[0]
-    fn = lib.umereg_featnet_forward_f16 if precision == "f16" else lib.umereg_featnet_forward_f32
-    rc = fn(coords.data_ptr(), feat.data_ptr(), int(n), int(batch), params.data_ptr(), out.data_ptr(),
-            status.data_ptr(), ws.data_ptr(), ws.numel(), torch.cuda.current_stream(coords.device).cuda_stream)
+    args = (coords.data_ptr(), feat.data_ptr(), int(n), int(batch), params.data_ptr(), out.data_ptr(), status.data_ptr(), ws.data_ptr(),
+            ws.numel(), torch.cuda.current_stream(coords.device).cuda_stream)
+    if conv_mode == "pairs":
+        from . import sparse_conv
+        rc = sparse_conv.load_native().umereg_featnet_forward_pairs(*args, int(precision == "f16"))
+    elif precision == "f16":
+        rc = lib.umereg_featnet_forward_f16(*args)
+    else:
+        rc = lib.umereg_featnet_forward_f32(*args)
     _lib.check(rc, "featnet_forward")
 
 
@@ -209,8 +231,9 @@ class ResUNetSmall2(nn.Module):
     STRIDES = [1, 2, 2, 2, 3]
 
     def __init__(self, in_channels=1, out_channels=32, bn_momentum=0.1, normalize_feature=True, D=3, trainable=False,
-                 precision="f32", train_precision="f32", fused_norm=False):
+                 precision="f32", train_precision="f32", fused_norm=False, conv_mode="union"):
         super().__init__()
+        self.conv_mode = check_conv_mode(conv_mode)
         self.trainable = bool(trainable)
         self.fused_norm = bool(fused_norm)
         if self.fused_norm and not self.trainable:
@@ -319,7 +342,7 @@ class ResUNetSmall2(nn.Module):
         ws = self._workspace(n, batch, F.device)
         out = torch.empty(n, OUT_CHANNELS, dtype=torch.float32, device=F.device)
         status = torch.empty(N_STATUS, dtype=torch.int32, device=F.device)
-        forward_raw(coords, feat, batch, params, ws, out, status, self.precision)
+        forward_raw(coords, feat, batch, params, ws, out, status, self.precision, self.conv_mode)
         sizes = check_status(status, self.precision)
         res = SparseTensor(out, coordinates=coords)
         res._batch_size = batch
@@ -366,7 +389,7 @@ class ResUNetSmall2(nn.Module):
             relu = bn_act.relu
 
         def conv(h, kernel, table):
-            return sc.sparse_conv(h, kernel, maps, table, precision=tp, fused_scale=fused)
+            return sc.sparse_conv(h, kernel, maps, table, precision=tp, fused_scale=fused, conv_mode=self.conv_mode)
 
         def bn(norm, v):
             return bn_act.batch_norm_act(v, norm.bn) if fused else norm.bn(v)

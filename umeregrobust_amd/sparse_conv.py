@@ -44,6 +44,12 @@ SPARSE_CONV_F16_SIGNATURES = {
     "umereg_sparse_conv_wgrad_f16": SPARSE_CONV_SIGNATURES["umereg_sparse_conv_wgrad_f32"],
 }
 
+# name -> (restype, argtypes); mirrors include/umereg_sparse_conv_pairs.h one to one: the arguments of the union engine's entries + int f16
+SPARSE_CONV_PAIRS_SIGNATURES = {
+    "umereg_featnet_forward_pairs": (c_int, _models.FEATNET_SIGNATURES["umereg_featnet_forward_f32"][1] + [c_int]),
+    "umereg_sparse_conv_pairs": (c_int, SPARSE_CONV_SIGNATURES["umereg_sparse_conv_f32"][1] + [c_int]),
+}
+
 N_TABLES, MAX_CH = 13, 256
 # input channels per launch of the plain convolution: a longer contraction runs as slices accumulated in order (two-level
 # summation; one chain over 27 x 256 products carries about twice the rounding error of eight chains over 27 x 32)
@@ -51,10 +57,11 @@ SLICE = 32
 
 
 def load_native():
-    """libumereg.so with the entry points of include/umereg_sparse_conv.h and umereg_sparse_conv_f16.h (and of umereg_featnet.h)
-    typed (raises without the built library)."""
+    """libumereg.so with the entry points of include/umereg_sparse_conv.h, umereg_sparse_conv_f16.h and
+    umereg_sparse_conv_pairs.h (and of umereg_featnet.h) typed (raises without the built library)."""
     _models.load_native()
     _lib.load_typed(SPARSE_CONV_SIGNATURES)
+    _lib.load_typed(SPARSE_CONV_PAIRS_SIGNATURES)
     return _lib.load_typed(SPARSE_CONV_F16_SIGNATURES)
 
 
@@ -126,18 +133,20 @@ def _rows(t, what):
     return t
 
 
-def conv_raw(x, kernel, maps, table, transpose=False, mirror=False, precision="f32", scale=None):
+def conv_raw(x, kernel, maps, table, transpose=False, mirror=False, precision="f32", scale=None, conv_mode="union"):
     """out[o] = sum_k x[nbr_table(o, k)] @ M[k], M = kernel, or with `transpose` M[k'] = kernel[k]^T (k' = 26 - k if `mirror`):
     x f32 [rows of in_level(table), C] -> [rows of out_level(table), C']; kernel [27, C, C'] ([27, C', C] with `transpose`).
     precision="f16" (include/umereg_featnet_f16.h; forward only, not differentiable): x and the kernel rounded to f16, sums in
     f32, one chain over all channels as in the fused f16 forward; table -1 with a [C, C'] kernel is the 1x1 layer over level 0
     (`transpose`: the kernel is [C', C]); `scale` (f16 only): f32 [>= C'] on the device, the epilogue's factor per output channel
-    instead of ones."""
+    instead of ones.  conv_mode="pairs" (include/umereg_sparse_conv_pairs.h; the default is "union"): the pair-compacted engine,
+    the same values bit for bit (the 1x1 layer runs the union engine's kernel either way)."""
     _models.check_precision(precision)
+    pairs = _models.check_conv_mode(conv_mode) == "pairs"
     lib = load_native()
     x = _rows(x, "input")
     if precision == "f16":
-        return _conv_f16(lib, x, kernel, maps, table, transpose, mirror, scale)
+        return _conv_f16(lib, x, kernel, maps, table, transpose, mirror, scale, pairs)
     if scale is not None:
         raise ValueError("sparse_conv: `scale` goes with precision='f16'")
     K, cin, cout = kernel.shape
@@ -153,14 +162,14 @@ def conv_raw(x, kernel, maps, table, transpose=False, mirror=False, precision="f
     else:
         kernel = kernel.contiguous()
     for s in range(cin // step):
-        _lib.check(lib.umereg_sparse_conv_f32(maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, table,
-                                              x.data_ptr() + 4 * s * step, x.stride(0), kernel.data_ptr() + 4 * s * 27 * step * cout, step,
-                                              cout, maps.ones.data_ptr(), maps.zeros.data_ptr(), out.data_ptr(), cout, int(s > 0),
-                                              _stream(x.device)), "sparse_conv")
+        args = (maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, table, x.data_ptr() + 4 * s * step, x.stride(0),
+                kernel.data_ptr() + 4 * s * 27 * step * cout, step, cout, maps.ones.data_ptr(), maps.zeros.data_ptr(), out.data_ptr(),
+                cout, int(s > 0), _stream(x.device))
+        _lib.check(lib.umereg_sparse_conv_pairs(*args, 0) if pairs else lib.umereg_sparse_conv_f32(*args), "sparse_conv")
     return out
 
 
-def _conv_f16(lib, x, kernel, maps, table, transpose, mirror, scale=None):
+def _conv_f16(lib, x, kernel, maps, table, transpose, mirror, scale=None, pairs=False):
     if kernel.dim() == 2:
         if table != -1:
             raise ValueError("sparse_conv: a [C_in, C_out] kernel is the 1x1 layer: table -1")
@@ -184,9 +193,9 @@ def _conv_f16(lib, x, kernel, maps, table, transpose, mirror, scale=None):
         scale = maps.ones
     elif scale.dtype != torch.float32 or scale.device != x.device or scale.dim() != 1 or scale.numel() < cout or not scale.is_contiguous():
         raise ValueError(f"sparse_conv: scale must be contiguous f32 [>= {cout}] on {x.device}")
-    _lib.check(lib.umereg_sparse_conv_f16(maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, table, x.data_ptr(),
-                                          x.stride(0), kernel.data_ptr(), cin, cout, scale.data_ptr(), maps.zeros.data_ptr(),
-                                          out.data_ptr(), cout, 0, _stream(x.device)), "sparse_conv_f16")
+    args = (maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, table, x.data_ptr(), x.stride(0), kernel.data_ptr(), cin,
+            cout, scale.data_ptr(), maps.zeros.data_ptr(), out.data_ptr(), cout, 0, _stream(x.device))
+    _lib.check(lib.umereg_sparse_conv_pairs(*args, 1) if pairs else lib.umereg_sparse_conv_f16(*args), "sparse_conv_f16")
     return out
 
 
@@ -276,10 +285,10 @@ def _scale_of(dy, fused):
 
 class _SparseConv(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, kernel, maps, table, precision="f32", fused_scale=False):
-        ctx.maps, ctx.table, ctx.precision, ctx.fused_scale = maps, table, precision, fused_scale
+    def forward(ctx, x, kernel, maps, table, precision="f32", fused_scale=False, conv_mode="union"):
+        ctx.maps, ctx.table, ctx.precision, ctx.fused_scale, ctx.conv_mode = maps, table, precision, fused_scale, conv_mode
         ctx.save_for_backward(x, kernel)
-        return conv_raw(x, kernel.detach(), maps, table, precision=precision)
+        return conv_raw(x, kernel.detach(), maps, table, precision=precision, conv_mode=conv_mode)
 
     @staticmethod
     def backward(ctx, dy):
@@ -293,16 +302,17 @@ class _SparseConv(torch.autograd.Function):
             dys = dy * up
             if ctx.needs_input_grad[0]:
                 adj, mirror = adjoint(table)
-                dx = conv_raw(dys, kernel.detach(), maps, adj, transpose=True, mirror=mirror, precision="f16", scale=maps.ones * down)
+                dx = conv_raw(dys, kernel.detach(), maps, adj, transpose=True, mirror=mirror, precision="f16", scale=maps.ones * down,
+                              conv_mode=ctx.conv_mode)
             if ctx.needs_input_grad[1]:
                 dw = wgrad_raw(x, dys, maps, table, precision="f16") * down
-            return dx, dw, None, None, None, None
+            return dx, dw, None, None, None, None, None
         if ctx.needs_input_grad[0]:
             adj, mirror = adjoint(table)
-            dx = conv_raw(dy, kernel.detach(), maps, adj, transpose=True, mirror=mirror)
+            dx = conv_raw(dy, kernel.detach(), maps, adj, transpose=True, mirror=mirror, conv_mode=ctx.conv_mode)
         if ctx.needs_input_grad[1]:
             dw = wgrad_raw(x, dy, maps, table)
-        return dx, dw, None, None, None, None
+        return dx, dw, None, None, None, None, None
 
 
 class _SparseConv1(torch.autograd.Function):
@@ -321,13 +331,17 @@ class _SparseConv1(torch.autograd.Function):
         return None, dw, None
 
 
-def sparse_conv(x, kernel, maps, table, precision="f32", fused_scale=False):
+def sparse_conv(x, kernel, maps, table, precision="f32", fused_scale=False, conv_mode="union"):
     """Differentiable sparse convolution over table `table` of `maps`.  x: f32 [rows of the table's input level, C_in] in the
     level's row order -- for a [27, 1, 32] kernel (conv1, table 0): [n, 1] in INPUT row order, and it may not require grad;
     kernel: [27, C_in, C_out].  -> f32 [rows of the table's output level, C_out].  precision="f16": f16 operands in the forward
     and in both gradients (module docstring); a C_in = 1 kernel (conv1) stays f32 either way.  fused_scale=True (f16 only): the
-    backward takes its scale from `bn_act.grad_scale_device` (two kernels) instead of `grad_scale` (the same scalars bit for bit)."""
+    backward takes its scale from `bn_act.grad_scale_device` (two kernels) instead of `grad_scale` (the same scalars bit for bit).
+    conv_mode="pairs" (include/umereg_sparse_conv_pairs.h): the forward and the input gradient -- the same operator over the adjoint
+    table -- run on the pair-compacted engine, bit for bit the values of the default "union"; the weight gradient has no mode, and
+    neither has conv1."""
     _models.check_precision(precision)
+    _models.check_conv_mode(conv_mode)
     if not 0 <= table < N_TABLES:
         raise ValueError(f"sparse_conv: table {table} outside [0, {N_TABLES})")
     if x.device.type != "cuda" or kernel.device.type != "cuda":
@@ -341,7 +355,7 @@ def sparse_conv(x, kernel, maps, table, precision="f32", fused_scale=False):
             raise RuntimeError("sparse_conv: conv1 has no input gradient (the network's input features are constants); "
                                "detach the input features")
         return _SparseConv1.apply(x, kernel, maps)
-    return _SparseConv.apply(x, kernel, maps, table, precision, bool(fused_scale))
+    return _SparseConv.apply(x, kernel, maps, table, precision, bool(fused_scale), conv_mode)
 
 
 def _block_wgrad(x, dy):

@@ -430,7 +430,7 @@ def make_loaders(args, synthetic=0, synthetic_points=3000, device_collate=False)
 
 
 def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=None, device_collate=False, device_assignment=False,
-        train_precision="f32", fused_norm=False):
+        train_precision="f32", fused_norm=False, conv_mode="union"):
     """train_coloring.py:263-437 -> the run directory.  Quirks kept: every "best" file stores the validation TOTAL loss; the
     UME and point-wise "best" follow the total (eval_one_epoch returns it three times); without the registration loss the validation
     registration loss is 0.0, so `best_reg_loss` (from inf) is written once, after the first epoch, and `best_mCHR` (from 0.0) never.
@@ -439,7 +439,8 @@ def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=
     train_precision: "f32", or "f16" for f16 operands in the network's layer-wise path (models.py; f32 parameters, so checkpoints
     are the same either way); a non-finite loss then raises FloatingPointError.
     fused_norm: batch norm, residual and ReLU of the layer-wise path on the kernels of include/umereg_bn_act.h (models.py; the same
-    parameters and checkpoint keys)."""
+    parameters and checkpoint keys).
+    conv_mode: "union", or "pairs" for the pair-compacted engine of the 27-offset convolutions (models.py; the same values bit for bit)."""
     torch.manual_seed(args.random_seed)
     np.random.seed(args.random_seed)
     device = torch.device(args.device)
@@ -451,7 +452,7 @@ def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=
     os.makedirs(out_path, exist_ok=True)
     dloader_train, dloader_valid = make_loaders(args, synthetic, synthetic_points, device_collate)
     model = ResUNetSmall2(in_channels=1, out_channels=args.out_channels, trainable=True, train_precision=train_precision,
-                          fused_norm=fused_norm).to(device)
+                          fused_norm=fused_norm, conv_mode=conv_mode).to(device)
     point_wise_loss_fn = MyInfoNCELossNoSeg(num_samples=args.num_pw_samples, tau=args.tau, neg_euclid_dist=NEG_EUCLID_DIST)
     ctx = TrainContext(args)
     optimizer = optim.Adam(model.parameters(), lr=args.lr, weight_decay=WEIGHT_DECAY)
@@ -501,6 +502,8 @@ def main(argv=None):
                         help="operand precision of the network's forward and backward matrix products (f32 sums and parameters)")
     parser.add_argument('--fused-norm', action='store_true',
                         help="run the network's batch norm, residual and ReLU (and the f16 gradient scale) on the fused HIP kernels")
+    parser.add_argument('--conv-mode', choices=['union', 'pairs'], default='union',
+                        help="engine of the network's 27-offset convolutions, forward and input gradient (pairs: pair-compacted; same values)")
     cli = parser.parse_args(argv)
     over = {k: v for k, v in (("cache_data_path", cli.cache), ("num_epochs", cli.epochs), ("batch_size", cli.batch_size),
                               ("output_path", cli.output_path), ("resume_train_path", cli.resume)) if v is not None}
@@ -511,7 +514,8 @@ def main(argv=None):
         args.eval_num_kpts, args.batch_size = 32, min(args.batch_size, 2)
     print(f"Train {args.dataset} config: {cli.config_path or 'built-in defaults'}")
     out = run(args, synthetic=cli.synthetic, synthetic_points=cli.synthetic_points, device_collate=cli.device_collate,
-              device_assignment=cli.device_assignment, train_precision=cli.train_precision, fused_norm=cli.fused_norm)
+              device_assignment=cli.device_assignment, train_precision=cli.train_precision, fused_norm=cli.fused_norm,
+              conv_mode=cli.conv_mode)
     print(f"run directory: {out}")
     return out
 
