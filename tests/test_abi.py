@@ -9,25 +9,116 @@ import pytest
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def header_symbols():
-    text = open(os.path.join(REPO, "include", "umereg.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(umereg_[a-z0-9_]+)\s*\(", text)))
+import abi_headers
 
 
-def test_library_builds_and_exports_every_declared_symbol():
+def _alias(attr):
+    import importlib
+    module, name = attr.split(".")
+    return getattr(importlib.import_module("umeregrobust_amd." + module), name)
+
+
+def test_library_builds_and_one_table_per_header():
+    """the library builds and loads; include/ holds the thirteen headers, _lib.TABLES one table for each, no symbol in two of them"""
     import umeregrobust_amd
     from umeregrobust_amd import _lib
-    path = umeregrobust_amd.build_native()
-    assert os.path.exists(path)
-    lib = ctypes.CDLL(path)
-    syms = header_symbols()
-    assert len(syms) >= 20
-    for name in syms:
-        assert hasattr(lib, name), f"{name} declared in include/umereg.h but not exported"
-    # and the ctypes table mirrors the header one to one
-    assert sorted(_lib.SIGNATURES) == syms
+    assert os.path.exists(umeregrobust_amd.build_native())
+    assert sorted(os.listdir(abi_headers.INCLUDE)) == sorted(abi_headers.HEADERS) == sorted(_lib.TABLES) and len(_lib.TABLES) == 13
+    assert _lib.TABLES["umereg.h"] is _lib.SIGNATURES
+    names = [name for table in _lib.TABLES.values() for name in table]
+    assert len(names) == len(set(names)) == 113, sorted(n for n in set(names) if names.count(n) > 1)
     assert _lib.load().umereg_abi_version() == _lib.ABI_VERSION == 2
+
+
+@pytest.mark.parametrize("header", list(abi_headers.HEADERS))
+def test_table_mirrors_its_header_and_every_symbol_is_exported(header):
+    """Per header: the table's keys are the header's symbols (their number pinned), the built library exports each, every
+    declaration has as many parameters as the table has argtypes, the module's public alias IS the table, and no symbol of it is
+    in another header's table."""
+    import umeregrobust_amd
+    from umeregrobust_amd import _lib
+    alias, count = abi_headers.HEADERS[header]
+    table = _lib.TABLES[header]
+    assert _alias(alias) is table
+    declared = abi_headers.declarations(header)
+    assert sorted(table) == sorted(declared) and len(declared) == count
+    lib = ctypes.CDLL(umeregrobust_amd.build_native())
+    for name, n_params in declared.items():
+        assert hasattr(lib, name), f"{name} declared in include/{header} but not exported"
+        assert len(table[name][1]) == n_params, name
+    for other, theirs in _lib.TABLES.items():
+        assert other == header or not set(table) & set(theirs), (header, other)
+    assert _lib.load().umereg_abi_version() == _lib.ABI_VERSION == 2
+
+
+class _Entry:
+    """what `call` and `checked` need of a ctypes function: a name and a status"""
+
+    def __init__(self, status, log):
+        self.__name__, self.status, self.log = "umereg_fake_entry", status, log
+
+    def __call__(self, *args):
+        self.log.append(("call", args))
+        return self.status
+
+
+@pytest.fixture
+def guard_log(monkeypatch):
+    import torch
+    log = []
+
+    class Guard:
+        def __init__(self, dev):
+            self.dev = dev
+
+        def __enter__(self):
+            log.append(("enter", self.dev))
+
+        def __exit__(self, *exc):
+            log.append(("exit", self.dev))
+
+    monkeypatch.setattr(torch.cuda, "device", Guard)
+    return log
+
+
+def test_call_runs_the_entry_inside_the_guard_of_the_device_given(guard_log):
+    from umeregrobust_amd import _lib
+    dev = object()
+    assert _lib.call(dev, _Entry(0, guard_log), 1, None, 2.5) is None
+    assert guard_log == [("enter", dev), ("call", (1, None, 2.5)), ("exit", dev)] and guard_log[0][1] is dev
+    del guard_log[:]
+    with pytest.raises(RuntimeError, match=r"umereg_fake_entry failed \(code -3\)"):
+        _lib.call(dev, _Entry(-3, guard_log), 7)
+    assert guard_log == [("enter", dev), ("call", (7,)), ("exit", dev)]
+
+
+def test_checked_never_enters_a_guard(guard_log):
+    from umeregrobust_amd import _lib
+    assert _lib.checked(_Entry(0, guard_log), 1, 2) is None
+    with pytest.raises(RuntimeError, match=r"umereg_fake_entry failed \(code 5\)") as e:
+        _lib.checked(_Entry(5, guard_log))
+    assert e.value.code == 5
+    assert guard_log == [("call", (1, 2)), ("call", ())]
+
+
+# entries whose int is a value, not a status
+NOT_A_STATUS = {"umereg_abi_version", "umereg_device_count", "umereg_sparse_conv_wgrad_segments"}
+
+
+def test_no_status_entry_is_called_directly():
+    """Every entry that returns a status goes through _lib.call / _lib.checked (which name the entry that failed and, for `call`,
+    make the tensors' device current): nowhere under umeregrobust_amd/ is one called as `lib.umereg_...(`."""
+    from umeregrobust_amd import _lib
+    status = {name for table in _lib.TABLES.values() for name, (res, _) in table.items() if res is ctypes.c_int} - NOT_A_STATUS
+    assert len(status) == 80 and NOT_A_STATUS <= {n for t in _lib.TABLES.values() for n in t}
+    pkg, seen = os.path.join(REPO, "umeregrobust_amd"), 0
+    for root, _, files in os.walk(pkg):
+        for f in files:
+            if f.endswith(".py"):
+                called = re.findall(r"\.(umereg_\w+)\(", open(os.path.join(root, f)).read())
+                seen += len(called)
+                assert not set(called) & status, f"{os.path.join(root, f)} calls {sorted(set(called) & status)} directly"
+    assert seen >= 30      # (the size queries: the scan does see the package's calls)
 
 
 def test_load_typed_types_a_table_once_and_names_a_missing_symbol():

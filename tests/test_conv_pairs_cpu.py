@@ -1,15 +1,16 @@
 """CPU: the pair-compacted convolution engine (include/umereg_sparse_conv_pairs.h, csrc/sparse_conv_pairs.hip) without a GPU --
 the `conv_mode` keyword, the compaction plan's restatement (tests/conv_pairs_ref.py) against csrc/conv_pairs_plan.h, the issue
 count of the plan against the union walk's on all 13 tables of the 6 000-point cloud, and the host side of the new header."""
+import ctypes
 import inspect
 import os
-import re
 import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import abi_headers
 import conv_pairs_ref as cpr
 import featnet_ref as ref
 import test_featnet_gpu as fg
@@ -131,33 +132,22 @@ def test_plan_never_issues_more_blocks_than_the_union_walk():
 
 # ---- the host side of include/umereg_sparse_conv_pairs.h ---------------------------------------------------------------------------
 
-def _header():
-    text = open(os.path.join(REPO, "include", "umereg_sparse_conv_pairs.h")).read()
-    return text, re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
 def test_pairs_table_mirrors_its_header():
-    from umeregrobust_amd import _lib, models, sparse_conv
-    raw, text = _header()
-    syms = sorted(set(re.findall(r"\b(umereg_[a-z0-9_]+)\s*\(", text)))
-    assert syms == ["umereg_featnet_forward_pairs", "umereg_sparse_conv_pairs"] and sorted(sparse_conv.SPARSE_CONV_PAIRS_SIGNATURES) == syms
-    lib = sparse_conv.load_native()
-    c_int = sparse_conv.c_int
+    """(keys, exports, parameter counts, disjointness and the ABI version: tests/test_abi.py, one case per header)"""
+    from umeregrobust_amd import models, sparse_conv
+    header = "umereg_sparse_conv_pairs.h"
+    raw = open(os.path.join(abi_headers.INCLUDE, header)).read()
+    syms = ["umereg_featnet_forward_pairs", "umereg_sparse_conv_pairs"]
+    assert sorted(sparse_conv.SPARSE_CONV_PAIRS_SIGNATURES) == syms
+    c_int = ctypes.c_int
     for name in syms:
-        assert hasattr(lib, name), f"{name} declared in include/umereg_sparse_conv_pairs.h but not exported"
-        params = re.search(name + r"\s*\((.*?)\)\s*;", text, re.S).group(1)
-        assert len(params.split(",")) == len(sparse_conv.SPARSE_CONV_PAIRS_SIGNATURES[name][1]), name
-        assert params.split(",")[-1].strip() == "int f16"
+        assert abi_headers.params(header, name).split(",")[-1].strip() == "int f16"
     # the arguments of the union engine's entries, one to one, then `int f16`
     assert sparse_conv.SPARSE_CONV_PAIRS_SIGNATURES["umereg_featnet_forward_pairs"] == \
         (c_int, models.FEATNET_SIGNATURES["umereg_featnet_forward_f32"][1] + [c_int])
     assert sparse_conv.SPARSE_CONV_PAIRS_SIGNATURES["umereg_sparse_conv_pairs"] == \
         (c_int, sparse_conv.SPARSE_CONV_SIGNATURES["umereg_sparse_conv_f32"][1] + [c_int])
-    # the older tables and headers stay what they were, and the ABI version stays
-    older = set(_lib.SIGNATURES) | set(models.FEATNET_SIGNATURES) | set(models.FEATNET_F16_SIGNATURES) | \
-        set(sparse_conv.SPARSE_CONV_SIGNATURES) | set(sparse_conv.SPARSE_CONV_F16_SIGNATURES)
-    assert not set(syms) & older
-    assert lib.umereg_abi_version() == 2
+    # the older headers stay what they were
     for h in ("umereg.h", "umereg_featnet.h", "umereg_featnet_f16.h", "umereg_sparse_conv.h", "umereg_sparse_conv_f16.h"):
         assert "_pairs" not in open(os.path.join(REPO, "include", h)).read(), h
     # the header states the two allowed differences

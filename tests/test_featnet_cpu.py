@@ -288,15 +288,9 @@ def test_sparse_tensor_decomposes_by_batch_index_in_row_order():
 
 # ---- the C ABI's host side ------------------------------------------------------------------------------------------------
 
-def _featnet_header_symbols():
-    text = open(os.path.join(REPO, "include", "umereg_featnet.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(umereg_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_featnet_table_mirrors_its_header():
+    """(keys, exports and parameter counts against the header: tests/test_abi.py, one case per header)"""
     from umeregrobust_amd import models
-    assert sorted(models.FEATNET_SIGNATURES) == _featnet_header_symbols()
     lib = models.load_native()
     info = models.layer_info()
     assert [(k, ci, co) for k, ci, co, _, _ in info] == [

@@ -14,6 +14,7 @@ import re
 import numpy as np
 import pytest
 
+import abi_headers
 import featnet_f16_ref as f16ref
 import featnet_ref as ref
 import test_featnet_gpu as fg
@@ -49,27 +50,14 @@ def test_roundings():
 
 # ---- the host side of include/umereg_featnet_f16.h ----------------------------------------------------------------------------
 
-def _header():
-    text = open(os.path.join(REPO, "include", "umereg_featnet_f16.h")).read()
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
 def test_f16_table_mirrors_its_header():
-    from umeregrobust_amd import _lib, models, sparse_conv
-    text = _header()
-    syms = sorted(set(re.findall(r"\b(umereg_[a-z0-9_]+)\s*\(", text)))
-    assert syms == ["umereg_featnet_forward_f16", "umereg_sparse_conv_f16"] and sorted(models.FEATNET_F16_SIGNATURES) == syms
-    lib = models.load_native()
-    for name in syms:
-        assert hasattr(lib, name), f"{name} declared in include/umereg_featnet_f16.h but not exported"
-        params = re.search(name + r"\s*\((.*?)\)\s*;", text, re.S).group(1)
-        assert len(params.split(",")) == len(models.FEATNET_F16_SIGNATURES[name][1]), name
+    """(keys, exports, parameter counts, disjointness and the ABI version: tests/test_abi.py, one case per header)"""
+    from umeregrobust_amd import models, sparse_conv
+    text = abi_headers.text("umereg_featnet_f16.h")
+    assert sorted(models.FEATNET_F16_SIGNATURES) == ["umereg_featnet_forward_f16", "umereg_sparse_conv_f16"]
     # the arguments of the f32 entries, one to one
     assert models.FEATNET_F16_SIGNATURES["umereg_featnet_forward_f16"] == models.FEATNET_SIGNATURES["umereg_featnet_forward_f32"]
     assert models.FEATNET_F16_SIGNATURES["umereg_sparse_conv_f16"] == sparse_conv.SPARSE_CONV_SIGNATURES["umereg_sparse_conv_f32"]
-    # the older tables stay what they were, and the ABI version stays
-    assert not set(syms) & (set(_lib.SIGNATURES) | set(models.FEATNET_SIGNATURES) | set(sparse_conv.SPARSE_CONV_SIGNATURES))
-    assert lib.umereg_abi_version() == 2
     assert int(re.search(r"#define UMEREG_FN_ERR_F16_RANGE (\d+)", text).group(1)) == models.ERR_F16_RANGE == 4
     for h in ("umereg.h", "umereg_featnet.h", "umereg_sparse_conv.h"):
         assert "f16.h" not in open(os.path.join(REPO, "include", h)).read()

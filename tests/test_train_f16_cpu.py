@@ -19,7 +19,6 @@ average out over thousands of rows while an f32 sum's do less so.)  M_RMS = 1.7 
 1.41 and 1.99."""
 import inspect
 import os
-import re
 
 import numpy as np
 import pytest
@@ -138,18 +137,12 @@ def test_scale_exponent():
 # ---- 3: the header's host side and the surface ------------------------------------------------------------------------------------
 
 def test_f16_training_table_mirrors_its_header():
-    from umeregrobust_amd import _lib, models, sparse_conv
-    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "umereg_sparse_conv_f16.h")).read(), flags=re.S)
-    syms = sorted(set(re.findall(r"\b(umereg_[a-z0-9_]+)\s*\(", text)))
-    assert syms == ["umereg_sparse_conv_wgrad_f16"] == sorted(sparse_conv.SPARSE_CONV_F16_SIGNATURES)
-    lib = sparse_conv.load_native()
-    assert hasattr(lib, syms[0])
-    params = re.search(syms[0] + r"\s*\((.*?)\)\s*;", text, re.S).group(1)
-    assert len(params.split(",")) == len(sparse_conv.SPARSE_CONV_F16_SIGNATURES[syms[0]][1]) == 15
+    """(keys, exports, parameter counts, disjointness and the ABI version: tests/test_abi.py, one case per header)"""
+    from umeregrobust_amd import sparse_conv
+    syms = ["umereg_sparse_conv_wgrad_f16"]
+    assert syms == sorted(sparse_conv.SPARSE_CONV_F16_SIGNATURES)
+    assert len(sparse_conv.SPARSE_CONV_F16_SIGNATURES[syms[0]][1]) == 15
     assert sparse_conv.SPARSE_CONV_F16_SIGNATURES[syms[0]] == sparse_conv.SPARSE_CONV_SIGNATURES["umereg_sparse_conv_wgrad_f32"]
-    assert not set(syms) & (set(_lib.SIGNATURES) | set(models.FEATNET_SIGNATURES) | set(models.FEATNET_F16_SIGNATURES)
-                            | set(sparse_conv.SPARSE_CONV_SIGNATURES))
-    assert lib.umereg_abi_version() == 2
     assert "umereg_sparse_conv_f16.h" in open(os.path.join(REPO, "include", "umereg_featnet_f16.h")).read()
 
 

@@ -8,43 +8,27 @@ Like scipy's, the rows come out ascending, and where the optimum is unique the a
 assignment of the same total may come out (lowest column index first, see the header).  `maximize` is not built.  A matrix with a
 NaN or an infinite cost raises ValueError, as scipy does -- that check is the one device -> host read of a call (four bytes per
 matrix).  `linear_sum_assignment_raw` takes caller-owned outputs and workspace and never waits for the device."""
-import ctypes
-
 import torch
 
 from . import _lib
 
-c_void_p, c_int, c_size_t, c_int64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int64
-
-# name -> (restype, argtypes); mirrors include/umereg_assign.h one to one
-ASSIGN_SIGNATURES = {
-    "umereg_assign_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
-    "umereg_linear_sum_assignment": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
-                                             c_void_p, c_size_t, c_void_p]),
-}
-
-
-def load_native():
-    """libumereg.so with the entry points of include/umereg_assign.h typed (raises without the built library)."""
-    return _lib.load_typed(ASSIGN_SIGNATURES)
+ASSIGN_SIGNATURES = _lib.TABLES["umereg_assign.h"]
+load_native = _lib.load
 
 
 def workspace_bytes(batch, n_rows, n_cols):
-    return int(load_native().umereg_assign_workspace_bytes(int(batch), int(n_rows), int(n_cols)))
+    return int(_lib.load().umereg_assign_workspace_bytes(int(batch), int(n_rows), int(n_cols)))
 
 
 def linear_sum_assignment_raw(cost, out_pairs, out_total, out_status, workspace):
     """Enqueue one batch on the current stream.  cost: float32 device tensor [b, n, m], n <= m, unit last stride, read through its
     row and batch strides; out_pairs i64 [b, n, 2]; out_total f64 [b] or None; out_status i32 [b]; workspace uint8 of
     >= workspace_bytes(b, n, m)."""
-    lib = load_native()
     b, n, m = cost.shape
     row_stride = cost.stride(1) if n > 1 else max(cost.stride(1), m)
-    with torch.cuda.device(cost.device):
-        rc = lib.umereg_linear_sum_assignment(cost.data_ptr(), b, n, m, row_stride, cost.stride(0) if b > 1 else 0, out_pairs.data_ptr(),
-                                              None if out_total is None else out_total.data_ptr(), out_status.data_ptr(),
-                                              workspace.data_ptr(), workspace.numel(), torch.cuda.current_stream(cost.device).cuda_stream)
-    _lib.check(rc, "umereg_linear_sum_assignment")
+    _lib.call(cost.device, _lib.load().umereg_linear_sum_assignment, cost.data_ptr(), b, n, m, row_stride,
+              cost.stride(0) if b > 1 else 0, out_pairs.data_ptr(), _lib.ptr(out_total), out_status.data_ptr(), workspace.data_ptr(),
+              workspace.numel(), _lib.stream_ptr(cost.device))
 
 
 def _passes_as_it_lies(c):

@@ -9,92 +9,57 @@ train mode, the running statistics in eval mode.  Gradients reach x, the residua
 the two statistic vectors (the backward recomputes the ReLU mask from y and never stores the masked gradient).  Two launches per
 forward and two per backward in train mode; every sum is fp64 over a fixed tree (deterministic bit for bit).  Everything runs on
 the current stream and nothing waits for the device.  No CPU fallback: CPU tensors raise."""
-import ctypes
-
 import torch
 
 from . import _lib
 
-c_void_p, c_int, c_size_t, c_double = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_double
-
-# name -> (restype, argtypes); mirrors include/umereg_bn_act.h one to one
-BN_ACT_SIGNATURES = {
-    "umereg_bn_act_scratch_bytes": (c_size_t, [c_int, c_int]),
-    "umereg_bn_act_forward_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                          c_int, c_int, c_double, c_double, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
-                                          c_void_p]),
-    "umereg_bn_act_backward_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                           c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
-                                           c_void_p]),
-    "umereg_grad_scale_scratch_bytes": (c_size_t, [c_size_t]),
-    "umereg_grad_scale_f32": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-}
+BN_ACT_SIGNATURES = _lib.TABLES["umereg_bn_act.h"]
+load_native = _lib.load
 
 MAX_CH = 256        # UMEREG_BN_ACT_MAX_CH
 
 
-def load_native():
-    """libumereg.so with the entry points of include/umereg_bn_act.h typed (raises without the built library)."""
-    return _lib.load_typed(BN_ACT_SIGNATURES)
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
+_ptr, _stream = _lib.ptr, _lib.stream_ptr
 
 
 def _rows(t, what):
-    if t.device.type != "cuda":
-        raise RuntimeError(f"batch_norm_act: {what} on the CPU; umeregrobust_amd has no CPU fallback (move the input to the GPU)")
-    if t.dtype != torch.float32 or t.dim() != 2:
-        raise ValueError(f"batch_norm_act: {what} must be f32 [rows, channels], got {t.dtype} {tuple(t.shape)}")
-    if t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < t.shape[1] or t.data_ptr() % 16:
-        t = t.contiguous()
-    return t
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+    return _lib.rows(t, "batch_norm_act", what)
 
 
 def scratch_bytes(n, C):
-    return int(load_native().umereg_bn_act_scratch_bytes(int(n), int(C)))
+    return int(_lib.load().umereg_bn_act_scratch_bytes(int(n), int(C)))
 
 
 def forward_raw(x, residual, gamma, beta, running_mean, running_var, num_batches_tracked, train, relu, eps, momentum):
     """One forward through the C ABI -> (y, stats [2, C]: the mean and invstd used).  Train mode updates the running statistics
     in place (pass None for all three to track nothing)."""
-    lib = load_native()
+    lib = _lib.load()
     n, C = x.shape
     y = torch.empty(n, C, dtype=torch.float32, device=x.device)
     stats = torch.empty(2, C, dtype=torch.float32, device=x.device)
     scratch = torch.empty(max(scratch_bytes(n, C), 16), dtype=torch.uint8, device=x.device) if train else None
-    with torch.cuda.device(x.device):
-        rc = lib.umereg_bn_act_forward_f32(x.data_ptr(), x.stride(0), _ptr(residual), 0 if residual is None else residual.stride(0), n, C,
-                                           gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean), _ptr(running_var),
-                                           _ptr(num_batches_tracked), int(bool(train)), int(bool(relu)), float(eps), float(momentum),
-                                           y.data_ptr(), C, stats[0].data_ptr(), stats[1].data_ptr(), _ptr(scratch),
-                                           0 if scratch is None else scratch.numel(), _stream(x.device))
-    _lib.check(rc, "umereg_bn_act_forward_f32")
+    _lib.call(x.device, lib.umereg_bn_act_forward_f32, x.data_ptr(), x.stride(0), _ptr(residual),
+              0 if residual is None else residual.stride(0), n, C, gamma.data_ptr(), beta.data_ptr(), _ptr(running_mean), _ptr(running_var),
+              _ptr(num_batches_tracked), int(bool(train)), int(bool(relu)), float(eps), float(momentum), y.data_ptr(), C,
+              stats[0].data_ptr(), stats[1].data_ptr(), _ptr(scratch), 0 if scratch is None else scratch.numel(), _stream(x.device))
     return y, stats
 
 
 def backward_raw(dy, x, y, gamma, stats, train, relu, need_dx=True, need_dres=False, need_params=True):
     """One backward through the C ABI -> (dx, dres, dgamma, dbeta); what is not asked for is None (train mode always forms the
     parameter sums: dx depends on them)."""
-    lib = load_native()
+    lib = _lib.load()
     n, C = x.shape
     need_params = bool(need_params or train)
     dx = torch.empty(n, C, dtype=torch.float32, device=x.device) if need_dx else None
     dres = torch.empty(n, C, dtype=torch.float32, device=x.device) if need_dres else None
     dparams = torch.empty(2, C, dtype=torch.float32, device=x.device) if need_params else None
     scratch = torch.empty(max(scratch_bytes(n, C), 16), dtype=torch.uint8, device=x.device) if need_params else None
-    with torch.cuda.device(x.device):
-        rc = lib.umereg_bn_act_backward_f32(dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), _ptr(y) if relu else None,
-                                            y.stride(0) if relu else 0, n, C, gamma.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(),
-                                            int(bool(train)), int(bool(relu)), _ptr(dx), C, _ptr(dres), C,
-                                            dparams[0].data_ptr() if need_params else None, dparams[1].data_ptr() if need_params else None,
-                                            _ptr(scratch), 0 if scratch is None else scratch.numel(), _stream(x.device))
-    _lib.check(rc, "umereg_bn_act_backward_f32")
+    _lib.call(x.device, lib.umereg_bn_act_backward_f32, dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0),
+              _ptr(y) if relu else None, y.stride(0) if relu else 0, n, C, gamma.data_ptr(), stats[0].data_ptr(), stats[1].data_ptr(),
+              int(bool(train)), int(bool(relu)), _ptr(dx), C, _ptr(dres), C, dparams[0].data_ptr() if need_params else None,
+              dparams[1].data_ptr() if need_params else None, _ptr(scratch), 0 if scratch is None else scratch.numel(),
+              _stream(x.device))
     return dx, dres, (dparams[0] if need_params else None), (dparams[1] if need_params else None)
 
 
@@ -140,8 +105,7 @@ def batch_norm_act(x, bn, residual=None, relu=False):
         raise ValueError("batch_norm_act: momentum=None (the cumulative average) is not supported; give BatchNorm1d a number")
     if not bn.affine or not bn.track_running_stats:
         raise ValueError("batch_norm_act: BatchNorm1d must be affine and track its running statistics")
-    if x.device.type != "cuda" or bn.weight.device.type != "cuda" or (residual is not None and residual.device.type != "cuda"):
-        raise RuntimeError("batch_norm_act: CPU tensors given; umeregrobust_amd has no CPU fallback (move the input to the GPU)")
+    _lib.on_gpu("batch_norm_act", x, bn.weight, *(() if residual is None else (residual,)))
     if x.dim() != 2 or x.shape[1] != bn.num_features or x.shape[1] % 32 or not 32 <= x.shape[1] <= MAX_CH:
         raise ValueError(f"batch_norm_act: x must be [rows, {bn.num_features}] with a channel count that is a multiple of 32 up to "
                          f"{MAX_CH}, got {tuple(x.shape)}")
@@ -178,8 +142,7 @@ class _Relu(torch.autograd.Function):
 
 def relu(x):
     """max(x, 0) for f32 [rows, C] on the GPU (C a multiple of 32 up to 256), forward and backward on the kernels of this module."""
-    if x.device.type != "cuda":
-        raise RuntimeError("relu: CPU tensors given; umeregrobust_amd has no CPU fallback (move the input to the GPU)")
+    _lib.on_gpu("relu", x)
     if x.dim() != 2 or x.shape[0] == 0 or x.shape[1] % 32 or not 32 <= x.shape[1] <= MAX_CH:
         raise ValueError(f"relu: x must be a non-empty [rows, C] with C a multiple of 32 up to {MAX_CH}, got {tuple(x.shape)}")
     return _Relu.apply(x)
@@ -188,11 +151,10 @@ def relu(x):
 def grad_scale_device(dy):
     """`sparse_conv.grad_scale` as two kernels (include/umereg_bn_act.h): -> (e, 2^e, 2^-e) as 0-dim tensors on dy's device
     (int32, f32, f32), the same contract bit for bit; one reduction of max |dy|, no host sync."""
-    if dy.device.type != "cuda":
-        raise RuntimeError("grad_scale_device: CPU tensors given; umeregrobust_amd has no CPU fallback (move the input to the GPU)")
+    _lib.on_gpu("grad_scale_device", dy)
     if dy.dtype != torch.float32:
         raise ValueError(f"grad_scale_device: dy must be f32, got {dy.dtype}")
-    lib = load_native()
+    lib = _lib.load()
     dy = dy.detach()
     dy = dy.contiguous()
     if dy.data_ptr() % 16:
@@ -203,8 +165,6 @@ def grad_scale_device(dy):
         raise ValueError(f"grad_scale_device: {count} elements not supported")
     buf = torch.empty(4 + need // 4, dtype=torch.int32, device=dy.device)      # the three scalars, one pad word, the partials
     base = buf.data_ptr()
-    with torch.cuda.device(dy.device):
-        rc = lib.umereg_grad_scale_f32(dy.data_ptr() if count else None, count, base, base + 4, base + 8, base + 16, need,
-                                       _stream(dy.device))
-    _lib.check(rc, "umereg_grad_scale_f32")
+    _lib.call(dy.device, lib.umereg_grad_scale_f32, dy.data_ptr() if count else None, count, base, base + 4, base + 8, base + 16, need,
+              _stream(dy.device))
     return buf[0], buf[1:2].view(torch.float32)[0], buf[2:3].view(torch.float32)[0]

@@ -11,39 +11,22 @@ equals the host collate's, bit for bit.  Cloud sizes are known from shapes, so a
 `umereg_collate_element` call per element is enqueued, then ONE device -> host read fetches the survivor counts that the match
 draws need.  Match semantics are exact and stated in the header.  `collate_element_raw` takes caller-owned outputs and
 workspace and never waits for the device."""
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
 from .datasets.kitti_dataset import _refuse_gpu_in_worker
 
-c_void_p, c_int, c_size_t, c_int64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int64
-
-# name -> (restype, argtypes); mirrors include/umereg_collate.h one to one
-COLLATE_SIGNATURES = {
-    "umereg_collate_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
-    "umereg_collate_element": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
-                                       c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
-                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-}
+COLLATE_SIGNATURES = _lib.TABLES["umereg_collate.h"]
+load_native = _lib.load
+_ptr = _lib.ptr
 
 # the dtypes the kernel gathers; a field of another dtype (a cache written elsewhere) is gathered with torch indexing instead
 KERNEL_DTYPES = {"pts": torch.float32, "seg": torch.int64, "coords": torch.int32}
 
 
-def load_native():
-    """libumereg.so with the entry points of include/umereg_collate.h typed (raises without the built library)."""
-    return _lib.load_typed(COLLATE_SIGNATURES)
-
-
 def workspace_bytes(ns, nt, n_matches):
-    return int(load_native().umereg_collate_workspace_bytes(int(ns), int(nt), int(n_matches)))
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+    return int(_lib.load().umereg_collate_workspace_bytes(int(ns), int(nt), int(n_matches)))
 
 
 def collate_element_raw(src, ns, tgt, nt, matches, keep_src, keep_tgt, b, out_src, out_tgt, out_matches, out_count, workspace):
@@ -52,16 +35,11 @@ def collate_element_raw(src, ns, tgt, nt, matches, keep_src, keep_tgt, b, out_sr
     keep_src / keep_tgt i64; out_src = (pts [n,3], seg [n], coords i32 [n,4], pts_tform [n,3]) and out_tgt = (pts, seg, coords): this
     element's slices of the batched outputs (None where the input is None); out_matches i64 [min(m, n_src, n_tgt), 2]; out_count
     i32 [2] (rows, error flag); workspace uint8 of >= workspace_bytes(ns, nt, m)."""
-    lib = load_native()
     m = matches.shape[0]
-    with torch.cuda.device(keep_src.device):
-        rc = lib.umereg_collate_element(*[_ptr(t) for t in src], int(ns), *[_ptr(t) for t in tgt], int(nt),
-                                        matches.data_ptr() if m else None, m, keep_src.data_ptr(), keep_src.shape[0],
-                                        keep_tgt.data_ptr(), keep_tgt.shape[0], int(b), *[_ptr(t) for t in out_src],
-                                        *[_ptr(t) for t in out_tgt], out_matches.data_ptr() if out_matches.shape[0] else None,
-                                        out_count.data_ptr(), workspace.data_ptr(), workspace.numel(),
-                                        torch.cuda.current_stream(keep_src.device).cuda_stream)
-    _lib.check(rc, "umereg_collate_element")
+    _lib.call(keep_src.device, _lib.load().umereg_collate_element, *[_ptr(t) for t in src], int(ns), *[_ptr(t) for t in tgt], int(nt),
+              matches.data_ptr() if m else None, m, keep_src.data_ptr(), keep_src.shape[0], keep_tgt.data_ptr(), keep_tgt.shape[0], int(b),
+              *[_ptr(t) for t in out_src], *[_ptr(t) for t in out_tgt], out_matches.data_ptr() if out_matches.shape[0] else None,
+              out_count.data_ptr(), workspace.data_ptr(), workspace.numel(), _lib.stream_ptr(keep_src.device))
 
 
 def _up(t, dev):

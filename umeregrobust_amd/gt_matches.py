@@ -8,33 +8,14 @@ The semantics are exact and stated in the header (fp32 transform in a fixed orde
 `d2 < radius * radius`).  Both calls read the number of rows with ONE device -> host read (like `ops.voxel_first_index`) and
 raise RuntimeError when a coordinate is NaN, infinite or (targets) beyond 2^20 m.  The `*_raw` forms take caller-owned outputs and
 workspace and never wait for the device."""
-import ctypes
-
 import torch
 
 from . import _lib
 
-c_void_p, c_int, c_size_t, c_double = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_double
-
-# name -> (restype, argtypes); mirrors include/umereg_gt_matches.h one to one
-GT_MATCH_SIGNATURES = {
-    "umereg_gt_matches_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "umereg_gt_matches_one_side_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_void_p, c_void_p, c_void_p,
-                                               c_size_t, c_void_p]),
-    "umereg_gt_matches_mutual_f32": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_double, c_void_p, c_void_p,
-                                             c_void_p, c_size_t, c_void_p]),
-}
+GT_MATCH_SIGNATURES = _lib.TABLES["umereg_gt_matches.h"]
+load_native = _lib.load
 
 MAX_COORD = 1048576.0       # UMEREG_GT_MATCHES_MAX_COORD
-
-
-def load_native():
-    """libumereg.so with the entry points of include/umereg_gt_matches.h typed (raises without the built library)."""
-    return _lib.load_typed(GT_MATCH_SIGNATURES)
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
 
 
 def _cloud(who, name, t):
@@ -57,29 +38,22 @@ def _tform(who, name, T, dev):
 
 
 def workspace_bytes(n_src, n_tgt, mutual=False):
-    return int(load_native().umereg_gt_matches_workspace_bytes(int(n_src), int(n_tgt), int(bool(mutual))))
+    return int(_lib.load().umereg_gt_matches_workspace_bytes(int(n_src), int(n_tgt), int(bool(mutual))))
 
 
 def one_side_raw(src, tgt, T, radius, out_rows, out_count, workspace):
     """Enqueue the one-side search on the current stream.  src [n,3], tgt [m,3] f32 contiguous, T f32 [4,4] or None, out_rows
     int64 [n,2], out_count int32 [2] (rows, error flag), workspace uint8 of >= workspace_bytes(n, m): all on one device."""
-    lib = load_native()
-    with torch.cuda.device(src.device):
-        rc = lib.umereg_gt_matches_one_side_f32(src.data_ptr(), src.shape[0], tgt.data_ptr(), tgt.shape[0],
-                                                None if T is None else T.data_ptr(), float(radius), out_rows.data_ptr(),
-                                                out_count.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(src.device))
-    _lib.check(rc, "umereg_gt_matches_one_side_f32")
+    _lib.call(src.device, _lib.load().umereg_gt_matches_one_side_f32, src.data_ptr(), src.shape[0], tgt.data_ptr(), tgt.shape[0],
+              _lib.ptr(T), float(radius), out_rows.data_ptr(), out_count.data_ptr(), workspace.data_ptr(), workspace.numel(),
+              _lib.stream_ptr(src.device))
 
 
 def mutual_raw(src, tgt, T, T_inv, radius, out_rows, out_count, workspace):
     """Enqueue the mutual search on the current stream (arguments as one_side_raw; workspace_bytes(n, m, mutual=True))."""
-    lib = load_native()
-    with torch.cuda.device(src.device):
-        rc = lib.umereg_gt_matches_mutual_f32(src.data_ptr(), src.shape[0], tgt.data_ptr(), tgt.shape[0],
-                                              None if T is None else T.data_ptr(), None if T_inv is None else T_inv.data_ptr(),
-                                              float(radius), out_rows.data_ptr(), out_count.data_ptr(), workspace.data_ptr(),
-                                              workspace.numel(), _stream(src.device))
-    _lib.check(rc, "umereg_gt_matches_mutual_f32")
+    _lib.call(src.device, _lib.load().umereg_gt_matches_mutual_f32, src.data_ptr(), src.shape[0], tgt.data_ptr(), tgt.shape[0],
+              _lib.ptr(T), _lib.ptr(T_inv), float(radius), out_rows.data_ptr(), out_count.data_ptr(), workspace.data_ptr(),
+              workspace.numel(), _lib.stream_ptr(src.device))
 
 
 def _run(who, src, tgt, T, T_inv, radius, is_mutual):

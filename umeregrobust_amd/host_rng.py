@@ -85,23 +85,23 @@ def choice_noreplace(rng, n, size, p):
     # numpy's legacy RandomState wraps an MT19937 bit generator whose state struct {uint32 key[624]; int pos;}
     # is exposed through the documented BitGenerator.ctypes interface: advance it in place, under its lock
     bitgen = _mt19937_of(rng)
-    if bitgen is not None:
-        addr = _state_address(bitgen)
-        with bitgen.lock:
-            rc = lib.umereg_host_choice_mt19937(addr, addr + 624 * 4, p.ctypes.data, is_f32, n, size,
-                                                found.ctypes.data, work_p, seen_p, None)
-    else:
-        st = rng.get_state()
-        if st[0] != "MT19937":
-            return rng.choice(n, size, replace=False, p=p)
-        key = st[1]
-        pos[0] = st[2]
-        rc = lib.umereg_host_choice_mt19937(key.ctypes.data, pos_p, p.ctypes.data, is_f32, n, size,
-                                            found.ctypes.data, work_p, seen_p, None)
-        if rc == 0:
+    try:
+        if bitgen is not None:
+            addr = _state_address(bitgen)
+            with bitgen.lock:
+                _lib.checked(lib.umereg_host_choice_mt19937, addr, addr + 624 * 4, p.ctypes.data, is_f32, n, size, found.ctypes.data,
+                             work_p, seen_p, None)
+        else:
+            st = rng.get_state()
+            if st[0] != "MT19937":
+                return rng.choice(n, size, replace=False, p=p)
+            key = st[1]
+            pos[0] = st[2]
+            _lib.checked(lib.umereg_host_choice_mt19937, key.ctypes.data, pos_p, p.ctypes.data, is_f32, n, size, found.ctypes.data,
+                         work_p, seen_p, None)
             rng.set_state((st[0], key, int(pos[0]), st[3], st[4]))
-    if rc != 0:
-        raise ValueError(_ERRORS.get(rc, "umereg_host_choice_mt19937 failed"))
+    except _lib.NativeCallError as e:       # the entry's codes 1 / 2 / 3 are numpy's argument errors: raise what numpy raises
+        raise ValueError(_ERRORS.get(e.code, "umereg_host_choice_mt19937 failed")) from None
     return found
 
 
@@ -123,10 +123,11 @@ def choice_uniform_noreplace(rng, n, size):
         perm = _perm_scratch[n] = np.empty(n, dtype=np.int64)
     out = np.empty(size, dtype=np.int64)
     addr = _state_address(bitgen)
-    with bitgen.lock:
-        rc = lib.umereg_host_permutation_mt19937(addr, addr + 624 * 4, n, size, perm.ctypes.data, out.ctypes.data)
-    if rc != 0:
-        raise ValueError("umereg_host_permutation_mt19937 failed")
+    try:
+        with bitgen.lock:
+            _lib.checked(lib.umereg_host_permutation_mt19937, addr, addr + 624 * 4, n, size, perm.ctypes.data, out.ctypes.data)
+    except _lib.NativeCallError:
+        raise ValueError("umereg_host_permutation_mt19937 failed") from None
     return out
 
 

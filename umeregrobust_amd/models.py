@@ -67,25 +67,9 @@ from torch import nn
 from . import _lib
 from .sparse import SparseTensor
 
-c_void_p, c_int, c_size_t = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-
-# name -> (restype, argtypes); mirrors include/umereg_featnet.h one to one
-FEATNET_SIGNATURES = {
-    "umereg_featnet_params_count": (c_size_t, []),
-    "umereg_featnet_layer_info": (c_int, [c_int, c_void_p]),
-    "umereg_featnet_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "umereg_featnet_buffer": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p]),
-    "umereg_featnet_build_maps": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "umereg_featnet_forward_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                           c_void_p]),
-}
-
-# name -> (restype, argtypes); mirrors include/umereg_featnet_f16.h one to one
-FEATNET_F16_SIGNATURES = {
-    "umereg_featnet_forward_f16": FEATNET_SIGNATURES["umereg_featnet_forward_f32"],
-    "umereg_sparse_conv_f16": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
-                                       c_void_p, c_void_p, c_int, c_int, c_void_p]),
-}
+FEATNET_SIGNATURES = _lib.TABLES["umereg_featnet.h"]
+FEATNET_F16_SIGNATURES = _lib.TABLES["umereg_featnet_f16.h"]
+load_native = _lib.load
 
 # include/umereg_featnet.h
 N_LAYERS, OUT_CHANNELS, N_STATUS, MAX_BATCH = 20, 32, 8, 127
@@ -109,13 +93,6 @@ LAYERS = (
     ("mlp1", None), ("final", None))
 
 
-def load_native():
-    """libumereg.so with the entry points of include/umereg_featnet.h and umereg_featnet_f16.h typed (raises without the built
-    library)."""
-    _lib.load_typed(FEATNET_SIGNATURES)
-    return _lib.load_typed(FEATNET_F16_SIGNATURES)
-
-
 def check_precision(precision):
     """-> `precision`, one of PRECISIONS ("f32"; "f16": f16 operands, f32 accumulation, inference only); else ValueError"""
     if precision not in PRECISIONS:
@@ -132,24 +109,23 @@ def check_conv_mode(conv_mode):
 
 def layer_info():
     """[(K, C_in, C_out, offset of W, offset of scale)] of the packed parameter block, from the library."""
-    lib = load_native()
+    lib = _lib.load()
     info = (ctypes.c_int32 * 5)()
     out = []
     for i in range(N_LAYERS):
-        _lib.check(lib.umereg_featnet_layer_info(i, ctypes.addressof(info)), "featnet_layer_info")
+        _lib.checked(lib.umereg_featnet_layer_info, i, ctypes.addressof(info))
         out.append(tuple(info))
     return out
 
 
 def workspace_bytes(n, batch):
-    return int(load_native().umereg_featnet_workspace_bytes(int(n), int(batch)))
+    return int(_lib.load().umereg_featnet_workspace_bytes(int(n), int(batch)))
 
 
 def buffer_view(ws, n, batch, which, rows, dtype=torch.float32):
     """A [rows, cols] view of workspace buffer `which` (include/umereg_featnet.h, UMEREG_FN_*)."""
     off, cols = ctypes.c_size_t(), ctypes.c_int32()
-    _lib.check(load_native().umereg_featnet_buffer(int(n), int(batch), int(which), ctypes.addressof(off), ctypes.addressof(cols)),
-               "featnet_buffer")
+    _lib.checked(_lib.load().umereg_featnet_buffer, int(n), int(batch), int(which), ctypes.addressof(off), ctypes.addressof(cols))
     esz = torch.empty(0, dtype=dtype).element_size()
     return ws[off.value:off.value + rows * cols.value * esz].view(dtype).view(rows, cols.value)
 
@@ -160,25 +136,20 @@ def forward_raw(coords, feat, batch, params, ws, out, status, precision="f32", c
     (include/umereg_sparse_conv_pairs.h) in the chosen precision, same buffers, same values."""
     check_precision(precision)
     check_conv_mode(conv_mode)
-    lib = load_native()
-    n = coords.shape[0]
-    args = (coords.data_ptr(), feat.data_ptr(), int(n), int(batch), params.data_ptr(), out.data_ptr(), status.data_ptr(), ws.data_ptr(),
-            ws.numel(), torch.cuda.current_stream(coords.device).cuda_stream)
+    lib = _lib.load()
+    f16 = precision == "f16"
     if conv_mode == "pairs":
-        from . import sparse_conv
-        rc = sparse_conv.load_native().umereg_featnet_forward_pairs(*args, int(precision == "f16"))
-    elif precision == "f16":
-        rc = lib.umereg_featnet_forward_f16(*args)
+        fn, mode = lib.umereg_featnet_forward_pairs, (int(f16),)
     else:
-        rc = lib.umereg_featnet_forward_f32(*args)
-    _lib.check(rc, "featnet_forward")
+        fn, mode = (lib.umereg_featnet_forward_f16 if f16 else lib.umereg_featnet_forward_f32), ()
+    _lib.call(coords.device, fn, coords.data_ptr(), feat.data_ptr(), int(coords.shape[0]), int(batch), params.data_ptr(), out.data_ptr(),
+              status.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(coords.device), *mode)
 
 
 def build_maps_raw(coords, batch, ws, status):
     """The coordinate maps alone (the first half of forward_raw), on the current stream; no host sync."""
-    rc = load_native().umereg_featnet_build_maps(coords.data_ptr(), int(coords.shape[0]), int(batch), status.data_ptr(), ws.data_ptr(),
-                                                 ws.numel(), torch.cuda.current_stream(coords.device).cuda_stream)
-    _lib.check(rc, "featnet_build_maps")
+    _lib.call(coords.device, _lib.load().umereg_featnet_build_maps, coords.data_ptr(), int(coords.shape[0]), int(batch),
+              status.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(coords.device))
 
 
 def check_status(status, precision="f32"):
@@ -275,7 +246,7 @@ class ResUNetSmall2(nn.Module):
             return self._packed
         info = layer_info()
         dev = self.conv1.kernel.device
-        total = int(load_native().umereg_featnet_params_count())
+        total = int(_lib.load().umereg_featnet_params_count())
         block = torch.zeros(total, dtype=torch.float64, device=dev)
         mods = dict(self.named_modules())
         with torch.no_grad():
@@ -323,8 +294,7 @@ class ResUNetSmall2(nn.Module):
                                    "(or build it with trainable=True)")
             if needs_grad:
                 raise RuntimeError("ResUNetSmall2 has no backward pass: run it under torch.no_grad() (or build it with trainable=True)")
-        if F.device.type != "cuda" or C.device.type != "cuda":
-            raise RuntimeError("ResUNetSmall2: CPU tensors given; umeregrobust_amd has no CPU fallback (move the input to the GPU)")
+        _lib.on_gpu("ResUNetSmall2", F, C)
         if self.training or needs_grad:
             return self._forward_layers(x, debug)
         params = self.packed_parameters()

@@ -23,8 +23,7 @@ MatchOpts = _lib.MatchOpts   # per-call matcher options (umereg_match_opts): Mat
 _workspaces = {}
 
 
-def _stream_ptr(device):
-    return torch.cuda.current_stream(device).cuda_stream
+_stream_ptr, _ptr = _lib.stream_ptr, _lib.ptr
 
 
 def _workspace(device, nbytes, tag):
@@ -61,10 +60,6 @@ def _dev(t, name, dtype=torch.float32):
     return t.contiguous()
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def ball_query(p1, p2, lengths1=None, lengths2=None, K=500, radius=0.2, return_nn=True, fma=False):
     """pytorch3d.ops.ball_query drop-in (reference evaluate.py:51; utils/loc_utils.py:383-384).
     p1 [B,n1,3], p2 [B,n2,3] -> (dists [B,n1,K] f32 0-pad, idx [B,n1,K] i64 -1-pad, knn [B,n1,K,3] | None).
@@ -89,10 +84,8 @@ def ball_query(p1, p2, lengths1=None, lengths2=None, K=500, radius=0.2, return_n
         return BallQuery(dists, idx, nn)
     need = lib.umereg_ball_query_workspace_bytes(B, n2)
     ws = _workspace(dev, need, "bq")
-    with torch.cuda.device(dev):
-        rc = lib.umereg_ball_query_ex_f32(_ptr(p1), _ptr(p2), _ptr(l1), _ptr(l2), B, n1, n2, int(K), float(radius), BALL_FMA if fma else 0,
-                                          _ptr(idx), _ptr(dists), _ptr(nn), _ptr(ws), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "umereg_ball_query_ex_f32")
+    _lib.call(dev, lib.umereg_ball_query_ex_f32, _ptr(p1), _ptr(p2), _ptr(l1), _ptr(l2), B, n1, n2, int(K), float(radius),
+              BALL_FMA if fma else 0, _ptr(idx), _ptr(dists), _ptr(nn), _ptr(ws), ws.numel(), _stream_ptr(dev))
     return BallQuery(dists, idx, nn)
 
 
@@ -164,20 +157,15 @@ def ume_moments(pts, kpts, feat, K, radius, return_count=False, return_idx=False
         need = lib.umereg_ume_moments_workspace_bytes(B, N)
         ws = _workspace(dev, need, "mom")
         with torch.cuda.device(dev):
-            rc = lib.umereg_pack_points_f32(_ptr(pts), B, N, float(radius), _ptr(ws), ws.numel(), _stream_ptr(dev))
-            _lib.check(rc, "umereg_pack_points_f32")
+            _lib.checked(lib.umereg_pack_points_f32, _ptr(pts), B, N, float(radius), _ptr(ws), ws.numel(), _stream_ptr(dev))
             ordered = int(ORDER_KEYPOINTS and 64 <= n <= (N + 255) // 256 * 256)
             if ordered:
-                rc = lib.umereg_ume_keypoint_order(_ptr(ws), _ptr(kpts), _ptr(kp_index), B, N, n, float(radius),
-                                                   _stream_ptr(dev))
-                _lib.check(rc, "umereg_ume_keypoint_order")
+                _lib.checked(lib.umereg_ume_keypoint_order, _ptr(ws), _ptr(kpts), _ptr(kp_index), B, N, n, float(radius), _stream_ptr(dev))
             ev = _timed(timing, dev)
-            rc = lib.umereg_ume_moments_packed_f32(_ptr(ws), _ptr(kpts), _ptr(kp_index), _ptr(feat), B, N, n, d, int(K),
-                                                   float(radius), ordered | (0 if normalize else MOMENTS_RAW) |
-                                                   (MOMENTS_ACC_F32 if acc == "f32" else MOMENTS_ACC_VALU if acc == "f64valu" else 0) |
-                                                   (MOMENTS_FMA_DIST if fma_dist else 0), _ptr(F), _ptr(cnt), _ptr(nidx),
-                                                   _stream_ptr(dev))
-            _lib.check(rc, "umereg_ume_moments_packed_f32")
+            _lib.checked(lib.umereg_ume_moments_packed_f32, _ptr(ws), _ptr(kpts), _ptr(kp_index), _ptr(feat), B, N, n, d, int(K),
+                         float(radius), ordered | (0 if normalize else MOMENTS_RAW) |
+                         (MOMENTS_ACC_F32 if acc == "f32" else MOMENTS_ACC_VALU if acc == "f64valu" else 0) |
+                         (MOMENTS_FMA_DIST if fma_dist else 0), _ptr(F), _ptr(cnt), _ptr(nidx), _stream_ptr(dev))
             _timed_end(timing, ev, dev)
     out = (F,)
     if return_count:
@@ -197,9 +185,7 @@ def ume_orthobasis(ume, layout=QLAYOUT_PLAIN):
     dev = ume.device
     nfloat = lib.umereg_qbasis_bytes(n, layout) // 4
     Q = torch.empty((nfloat,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.umereg_ume_orthobasis_f32(_ptr(ume), n, int(layout), _ptr(Q), _stream_ptr(dev))
-    _lib.check(rc, "umereg_ume_orthobasis_f32")
+    _lib.call(dev, lib.umereg_ume_orthobasis_f32, _ptr(ume), n, int(layout), _ptr(Q), _stream_ptr(dev))
     return Q.view(n, 32, 4) if layout == QLAYOUT_PLAIN else Q
 
 
@@ -241,24 +227,22 @@ def _dist_q(ume1, ume2, want_D, want_match, timing, precision="f32", opts=None):
     st = _stream_ptr(dev)
     with torch.cuda.device(dev):
         for b in range(B):
-            _lib.check(lib.umereg_ume_orthobasis_f32(_ptr(ume1[b]), n1, lay_a, base, st), "umereg_ume_orthobasis_f32")
-            _lib.check(lib.umereg_ume_orthobasis_f32(_ptr(ume2[b]), n2, lay_b, base + qa, st), "umereg_ume_orthobasis_f32")
+            _lib.checked(lib.umereg_ume_orthobasis_f32, _ptr(ume1[b]), n1, lay_a, base, st)
+            _lib.checked(lib.umereg_ume_orthobasis_f32, _ptr(ume2[b]), n2, lay_b, base + qa, st)
             if refine:
-                _lib.check(lib.umereg_ume_match_reset_f16(base + qa + qb, scratch, n1, n2, st), "umereg_ume_match_reset_f16")
+                _lib.checked(lib.umereg_ume_match_reset_f16, base + qa + qb, scratch, n1, n2, st)
             ev = _timed(timing, dev)
             if refine:
                 # the two stages of umereg_ume_match_q_f16r; `timing` brackets the coarse (dominant) stage
-                rc = lib.umereg_ume_match_coarse_f16_ex(base, base + qa, n1, n2, base + qa + qb, scratch, op, st)
-                _lib.check(rc, "umereg_ume_match_coarse_f16")
+                _lib.checked(lib.umereg_ume_match_coarse_f16_ex, base, base + qa, n1, n2, base + qa + qb, scratch, op, st)
                 _timed_end(timing, ev, dev)
                 timing = getattr(timing, "refine", None)
                 ev = _timed(timing, dev)
-                rc = lib.umereg_ume_match_refine_f16_ex(base, base + qa, n1, n2, base + qa + qb, scratch, _ptr(m[b]), _ptr(d[b]), op, st)
+                _lib.checked(lib.umereg_ume_match_refine_f16_ex, base, base + qa, n1, n2, base + qa + qb, scratch, _ptr(m[b]), _ptr(d[b]),
+                             op, st)
             else:
-                rc = dist_fn(base, base + qa, n1, n2, _ptr(D[b]) if want_D else None,
-                             _ptr(m[b]) if want_match else None, _ptr(d[b]) if want_match else None,
-                             base + qa + qb if want_match else None, st)
-            _lib.check(rc, "umereg_ume_dist_q")
+                _lib.checked(dist_fn, base, base + qa, n1, n2, _ptr(D[b]) if want_D else None, _ptr(m[b]) if want_match else None,
+                             _ptr(d[b]) if want_match else None, base + qa + qb if want_match else None, st)
             _timed_end(timing, ev, dev)
     return D, m, d
 
@@ -286,9 +270,7 @@ def ume_cdist_onecall(ume1, ume2):
     dev = ume1.device
     D = torch.empty((B, n1, n2), dtype=torch.float32, device=dev)
     ws = _workspace(dev, lib.umereg_ume_cdist_workspace_bytes(B, n1, n2), "dist1")
-    with torch.cuda.device(dev):
-        rc = lib.umereg_ume_cdist_f32(_ptr(ume1), _ptr(ume2), B, n1, n2, _ptr(D), _ptr(ws), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "umereg_ume_cdist_f32")
+    _lib.call(dev, lib.umereg_ume_cdist_f32, _ptr(ume1), _ptr(ume2), B, n1, n2, _ptr(D), _ptr(ws), ws.numel(), _stream_ptr(dev))
     return D
 
 
@@ -303,10 +285,7 @@ def ume_match_onecall(ume1, ume2):
     m = torch.empty((B, n1), dtype=torch.int64, device=dev)
     d = torch.empty((B, n1), dtype=torch.float32, device=dev)
     ws = _workspace(dev, lib.umereg_ume_match_workspace_bytes(B, n1, n2), "dist1")
-    with torch.cuda.device(dev):
-        rc = lib.umereg_ume_match_f32(_ptr(ume1), _ptr(ume2), B, n1, n2, _ptr(m), _ptr(d), _ptr(ws), ws.numel(),
-                                      _stream_ptr(dev))
-    _lib.check(rc, "umereg_ume_match_f32")
+    _lib.call(dev, lib.umereg_ume_match_f32, _ptr(ume1), _ptr(ume2), B, n1, n2, _ptr(m), _ptr(d), _ptr(ws), ws.numel(), _stream_ptr(dev))
     return m, d
 
 
@@ -319,10 +298,8 @@ def ume_moments_onecall(pts, kpts, feat, K, radius):
     dev = pts.device
     F = torch.empty((B, n, feat.shape[2], 4), dtype=torch.float32, device=dev)
     ws = _workspace(dev, lib.umereg_ume_moments_workspace_bytes(B, N), "mom1")
-    with torch.cuda.device(dev):
-        rc = lib.umereg_ume_moments_f32(_ptr(pts), _ptr(kpts), _ptr(feat), B, N, n, feat.shape[2], int(K), float(radius),
-                                        _ptr(F), None, None, _ptr(ws), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "umereg_ume_moments_f32")
+    _lib.call(dev, lib.umereg_ume_moments_f32, _ptr(pts), _ptr(kpts), _ptr(feat), B, N, n, feat.shape[2], int(K), float(radius), _ptr(F),
+              None, None, _ptr(ws), ws.numel(), _stream_ptr(dev))
     return F
 
 
@@ -332,9 +309,7 @@ def match_prob(ume_d, tau):
     ume_d = _dev(ume_d, "ume_d").view(-1)
     prob = torch.empty_like(ume_d)
     dev = ume_d.device
-    with torch.cuda.device(dev):
-        rc = lib.umereg_match_prob_f32(_ptr(ume_d), ume_d.numel(), float(tau), _ptr(prob), _stream_ptr(dev))
-    _lib.check(rc, "umereg_match_prob_f32")
+    _lib.call(dev, lib.umereg_match_prob_f32, _ptr(ume_d), ume_d.numel(), float(tau), _ptr(prob), _stream_ptr(dev))
     return prob
 
 
@@ -361,10 +336,8 @@ def rtume_solve(G, H, g_index=None, h_index=None, with_dist=False, h_of_g=None):
     T = torch.empty((n, 4, 4), dtype=torch.float32, device=dev)
     D = torch.empty((n,), dtype=torch.float32, device=dev) if with_dist else None
     if n > 0:
-        with torch.cuda.device(dev):
-            rc = lib.umereg_rtume_solve_f32(_ptr(G), _ptr(H), _ptr(gi), _ptr(hi), _ptr(hg), G.shape[0], H.shape[0], n,
-                                            _ptr(T), _ptr(D), _stream_ptr(dev))
-        _lib.check(rc, "umereg_rtume_solve_f32")
+        _lib.call(dev, lib.umereg_rtume_solve_f32, _ptr(G), _ptr(H), _ptr(gi), _ptr(hi), _ptr(hg), G.shape[0], H.shape[0], n, _ptr(T),
+                  _ptr(D), _stream_ptr(dev))
     return T, D
 
 
@@ -377,9 +350,7 @@ def rre_deg(R, R_hat):
     b = R.shape[0]
     out = torch.empty((b,), dtype=torch.float32, device=R.device)
     if b > 0:
-        with torch.cuda.device(R.device):
-            rc = lib.umereg_rre_deg_f32(_ptr(R), _ptr(R_hat), b, _ptr(out), _stream_ptr(R.device))
-        _lib.check(rc, "umereg_rre_deg_f32")
+        _lib.call(R.device, lib.umereg_rre_deg_f32, _ptr(R), _ptr(R_hat), b, _ptr(out), _stream_ptr(R.device))
     return out
 
 
@@ -398,9 +369,7 @@ def hypothesis_gates(T, gt_tform, counts, return_errors=False):
     rre = torch.empty((n,), dtype=torch.float32, device=dev) if return_errors else None
     rte = torch.empty((n,), dtype=torch.float32, device=dev) if return_errors else None
     if n > 0:
-        with torch.cuda.device(dev):
-            rc = lib.umereg_hypothesis_gates_f32(_ptr(T), _ptr(gt), n, _ptr(counts), _ptr(rre), _ptr(rte), _stream_ptr(dev))
-        _lib.check(rc, "umereg_hypothesis_gates_f32")
+        _lib.call(dev, lib.umereg_hypothesis_gates_f32, _ptr(T), _ptr(gt), n, _ptr(counts), _ptr(rre), _ptr(rte), _stream_ptr(dev))
     return (rre, rte) if return_errors else None
 
 
@@ -421,9 +390,8 @@ def _voxel_first_index_launch(pts, voxel, cnt):
         cnt.zero_()
         return idx
     ws = _workspace(dev, lib.umereg_voxel_first_index_workspace_bytes(n), "voxel")
-    with torch.cuda.device(dev):
-        rc = lib.umereg_voxel_first_index_f32(_ptr(pts), n, float(voxel), _ptr(idx), _ptr(cnt), _ptr(ws), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "umereg_voxel_first_index_f32")
+    _lib.call(dev, lib.umereg_voxel_first_index_f32, _ptr(pts), n, float(voxel), _ptr(idx), _ptr(cnt), _ptr(ws), ws.numel(),
+              _stream_ptr(dev))
     return idx
 
 
@@ -487,10 +455,8 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, K=1, return_nn=False, **_ig
     idx = torch.empty((B, n1, K), dtype=torch.int64, device=dev)
     if n1 > 0:
         ws = _workspace(dev, lib.umereg_knn_workspace_bytes(B, n2), "knn")
-        with torch.cuda.device(dev):
-            rc = lib.umereg_knn_points_f32(_ptr(p1), _ptr(p2), B, n1, n2, int(K), _ptr(dists), _ptr(idx), _ptr(ws),
-                                           ws.numel(), _stream_ptr(dev))
-        _lib.check(rc, "umereg_knn_points_f32")
+        _lib.call(dev, lib.umereg_knn_points_f32, _ptr(p1), _ptr(p2), B, n1, n2, int(K), _ptr(dists), _ptr(idx), _ptr(ws), ws.numel(),
+                  _stream_ptr(dev))
     nn = None
     if return_nn:
         nn = torch.gather(p2.unsqueeze(1).expand(-1, n1, -1, -1), 2, idx.unsqueeze(-1).expand(-1, -1, -1, 3))
@@ -510,10 +476,8 @@ def nn1_pair(q_src, q_tgt, p_src, p_tgt):
     i_s = torch.empty(qs.shape[0], dtype=torch.int64, device=dev)
     i_t = torch.empty(qt.shape[0], dtype=torch.int64, device=dev)
     ws = _workspace(dev, lib.umereg_nn1_pair_workspace_bytes(ps.shape[0], pt.shape[0]), "nn1pair")
-    with torch.cuda.device(dev):
-        rc = lib.umereg_nn1_pair_f32(_ptr(qs), _ptr(qt), _ptr(ps), _ptr(pt), qs.shape[0], qt.shape[0], ps.shape[0], pt.shape[0],
-                                     _ptr(i_s), _ptr(i_t), None, None, _ptr(ws), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "umereg_nn1_pair_f32")
+    _lib.call(dev, lib.umereg_nn1_pair_f32, _ptr(qs), _ptr(qt), _ptr(ps), _ptr(pt), qs.shape[0], qt.shape[0], ps.shape[0], pt.shape[0],
+              _ptr(i_s), _ptr(i_t), None, None, _ptr(ws), ws.numel(), _stream_ptr(dev))
     return i_s, i_t
 
 
@@ -530,10 +494,8 @@ def feature_spatial_var(pts, feat, knn=10):
     dev = pts.device
     out = torch.empty((B, N), dtype=torch.float32, device=dev)
     ws = _workspace(dev, lib.umereg_knn_workspace_bytes(B, N), "knn")
-    with torch.cuda.device(dev):
-        rc = lib.umereg_feature_spatial_var_f32(_ptr(pts), _ptr(feat), B, N, feat.shape[2], int(knn), _ptr(out), _ptr(ws),
-                                                ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "umereg_feature_spatial_var_f32")
+    _lib.call(dev, lib.umereg_feature_spatial_var_f32, _ptr(pts), _ptr(feat), B, N, feat.shape[2], int(knn), _ptr(out), _ptr(ws),
+              ws.numel(), _stream_ptr(dev))
     return out
 
 
@@ -549,10 +511,8 @@ def corr_weighted_features(src_feat, tgt_feat, src_w, tgt_w):
     dev = sf.device
     so, to = torch.empty_like(sf), torch.empty_like(tf)
     ws = _workspace(dev, 64 * 32 * 8 + 256, "corrw")
-    with torch.cuda.device(dev):
-        rc = lib.umereg_corr_weighted_features_f32(_ptr(sf), _ptr(tf), _ptr(sw), _ptr(tw), sf.shape[0], tf.shape[0],
-                                                   _ptr(so), _ptr(to), _ptr(ws), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "umereg_corr_weighted_features_f32")
+    _lib.call(dev, lib.umereg_corr_weighted_features_f32, _ptr(sf), _ptr(tf), _ptr(sw), _ptr(tw), sf.shape[0], tf.shape[0], _ptr(so),
+              _ptr(to), _ptr(ws), ws.numel(), _stream_ptr(dev))
     return so, to
 
 
@@ -581,9 +541,8 @@ def corr_scores(src_pts, tgt_pts, src_wfeat, tgt_wfeat, T, K=20, sigma=0.05, tim
         ws = _workspace(dev, lib.umereg_corr_workspace_bytes_ex(Ns, Nt, M, int(flags)), "corr")
         with torch.cuda.device(dev):
             ev = _timed(timing, dev)
-            rc = lib.umereg_corr_scores_ex_f32(_ptr(sp), _ptr(tp), _ptr(sf), _ptr(tf), _ptr(T), Ns, Nt, M, int(K),
-                                               float(sigma), int(flags), _ptr(scores), _ptr(ws), ws.numel(), _stream_ptr(dev))
-            _lib.check(rc, "umereg_corr_scores_ex_f32")
+            _lib.checked(lib.umereg_corr_scores_ex_f32, _ptr(sp), _ptr(tp), _ptr(sf), _ptr(tf), _ptr(T), Ns, Nt, M, int(K), float(sigma),
+                         int(flags), _ptr(scores), _ptr(ws), ws.numel(), _stream_ptr(dev))
             _timed_end(timing, ev, dev)
     return scores
 
@@ -605,10 +564,8 @@ def corr_scores_profile(src_pts, tgt_pts, src_wfeat, tgt_wfeat, T, K=20, sigma=0
     scores = torch.empty((M,), dtype=torch.float32, device=dev)
     ws = _workspace(dev, lib.umereg_corr_workspace_bytes_ex(Ns, Nt, M, int(flags)), "corr")
     ms = (ctypes.c_float * len(CORR_STAGES))()
-    with torch.cuda.device(dev):
-        rc = lib.umereg_corr_scores_profile_f32(_ptr(sp), _ptr(tp), _ptr(sf), _ptr(tf), _ptr(T), Ns, Nt, M, int(K), float(sigma),
-                                                int(flags), _ptr(scores), _ptr(ws), ws.numel(), _stream_ptr(dev), ms)
-    _lib.check(rc, "umereg_corr_scores_profile_f32")
+    _lib.call(dev, lib.umereg_corr_scores_profile_f32, _ptr(sp), _ptr(tp), _ptr(sf), _ptr(tf), _ptr(T), Ns, Nt, M, int(K), float(sigma),
+              int(flags), _ptr(scores), _ptr(ws), ws.numel(), _stream_ptr(dev), ms)
     off = lib.umereg_corr_workspace_bytes_ex(Ns, Nt, M, CORR_NO_LATTICE)      # = where the lattice header starts
     header = (ws[off:off + 256].view(torch.int32).cpu().numpy().astype("int64") & 0xffffffff) if ws.numel() >= off + 256 else None
     return scores, {k: float(v) for k, v in zip(CORR_STAGES, ms)}, header
@@ -624,9 +581,7 @@ def corr_select_best(scores, T):
     dev = scores.device
     out = torch.empty((4, 4), dtype=torch.float32, device=dev)
     idx = torch.empty((1,), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        rc = lib.umereg_corr_select_best_f32(_ptr(scores), _ptr(T), scores.shape[0], _ptr(out), _ptr(idx), _stream_ptr(dev))
-    _lib.check(rc, "umereg_corr_select_best_f32")
+    _lib.call(dev, lib.umereg_corr_select_best_f32, _ptr(scores), _ptr(T), scores.shape[0], _ptr(out), _ptr(idx), _stream_ptr(dev))
     return out, idx
 
 
@@ -660,13 +615,10 @@ def icp_point_to_point(src_pts, tgt_pts, T_init, max_correspondence_distance=0.2
     iters = np.zeros(1, dtype=np.int32)
     # (a workspace of its own: an IcpJob in flight on this stream keeps its search grid in "icp" / "icpN" across result())
     ws = _workspace(dev, lib.umereg_icp_workspace_bytes(n, m), "icp_sync")
-    with torch.cuda.device(dev):
-        fn = lib.umereg_icp_point_to_point_dev_f32 if on_dev else lib.umereg_icp_point_to_point_f32
-        rc = fn(_ptr(sp), _ptr(tp), n, m, T_init.data_ptr() if on_dev else T0.ctypes.data, float(max_correspondence_distance),
-                int(max_iteration), float(relative_fitness), float(relative_rmse),
-                T.ctypes.data, out.ctypes.data, out.ctypes.data + 8, iters.ctypes.data,
-                _ptr(ws), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "umereg_icp_point_to_point_f32")
+    fn = lib.umereg_icp_point_to_point_dev_f32 if on_dev else lib.umereg_icp_point_to_point_f32
+    _lib.call(dev, fn, _ptr(sp), _ptr(tp), n, m, T_init.data_ptr() if on_dev else T0.ctypes.data, float(max_correspondence_distance),
+              int(max_iteration), float(relative_fitness), float(relative_rmse), T.ctypes.data, out.ctypes.data, out.ctypes.data + 8,
+              iters.ctypes.data, _ptr(ws), ws.numel(), _stream_ptr(dev))
     return SimpleNamespace(transformation=T, fitness=float(out[0]), inlier_rmse=float(out[1]), iterations=int(iters[0]))
 
 
@@ -744,11 +696,9 @@ class IcpJob:
     def _enqueue(self, first, iterations):
         lib = _lib.load()
         d, it, rf, rr = self.par
-        with torch.cuda.device(self.dev):
-            rc = lib.umereg_icp_enqueue_f32(_ptr(self.sp), _ptr(self.tp), self.sp.shape[0], self.tp.shape[0], _ptr(self.T0), d, it, rf, rr,
-                                            1 if first else 0, int(iterations), self.state.data_ptr(), _ptr(self.ws), self.ws.numel(),
-                                            self.stream.cuda_stream)
-        _lib.check(rc, "umereg_icp_enqueue_f32")
+        _lib.call(self.dev, lib.umereg_icp_enqueue_f32, _ptr(self.sp), _ptr(self.tp), self.sp.shape[0], self.tp.shape[0], _ptr(self.T0), d,
+                  it, rf, rr, 1 if first else 0, int(iterations), self.state.data_ptr(), _ptr(self.ws), self.ws.numel(),
+                  self.stream.cuda_stream)
         self.launched += iterations
         self.event.record(self.stream)
 
@@ -766,9 +716,8 @@ class IcpJob:
         try:
             while True:
                 self.event.synchronize()
-                rc = lib.umereg_icp_state_decode(self.state.data_ptr(), T.ctypes.data, out.ctypes.data, out.ctypes.data + 8, iters.ctypes.data,
-                                                 iters.ctypes.data + 4)
-                _lib.check(rc, "umereg_icp_state_decode")
+                _lib.checked(lib.umereg_icp_state_decode, self.state.data_ptr(), T.ctypes.data, out.ctypes.data, out.ctypes.data + 8,
+                             iters.ctypes.data, iters.ctypes.data + 4)
                 if iters[1] or self.launched > self.par[1] + 1:
                     break
                 self._enqueue(False, 8)
@@ -794,9 +743,7 @@ def ume_svdvals(ume):
     n = ume.numel() // 128
     sv = torch.empty(ume.shape[:-2] + (4,), dtype=torch.float32, device=ume.device)
     if n > 0:
-        with torch.cuda.device(ume.device):
-            rc = lib.umereg_ume_svdvals_f32(_ptr(ume), n, _ptr(sv), _stream_ptr(ume.device))
-        _lib.check(rc, "umereg_ume_svdvals_f32")
+        _lib.call(ume.device, lib.umereg_ume_svdvals_f32, _ptr(ume), n, _ptr(sv), _stream_ptr(ume.device))
     return sv
 
 
@@ -822,11 +769,8 @@ def pair_match(pts, feat, kp_index, K, radius, tau=None, opts=None):
     if lib.umereg_pair_match_workspace_bytes_ex(N, n, op) == 0:
         _lib.check(-1, "umereg_pair_match_workspace_bytes_ex")
     ws = _workspace(dev, lib.umereg_pair_match_workspace_bytes_ex(N, n, op), "pair")
-    with torch.cuda.device(dev):
-        rc = lib.umereg_pair_match_ex_f32(_ptr(pts), _ptr(feat), _ptr(kp_index), N, n, int(K), float(radius),
-                                          float(tau) if tau is not None else 0.0, _ptr(F), _ptr(m), _ptr(d), _ptr(prob),
-                                          _ptr(ws), ws.numel(), op, _stream_ptr(dev))
-    _lib.check(rc, "umereg_pair_match_ex_f32")
+    _lib.call(dev, lib.umereg_pair_match_ex_f32, _ptr(pts), _ptr(feat), _ptr(kp_index), N, n, int(K), float(radius),
+              float(tau) if tau is not None else 0.0, _ptr(F), _ptr(m), _ptr(d), _ptr(prob), _ptr(ws), ws.numel(), op, _stream_ptr(dev))
     return F, m, d, prob
 
 
@@ -871,11 +815,9 @@ def pair_match_ragged(src_pts, tgt_pts, src_feat, tgt_feat, src_kp, tgt_kp, K, r
     if need == 0:
         _lib.check(-1, "umereg_pair_match_workspace_bytes_ex")
     ws = _workspace(dev, need, "pair")
-    with torch.cuda.device(dev):
-        rc = lib.umereg_pair_match_ragged_f32(_ptr(sp), _ptr(tp), _ptr(sf), _ptr(tf), _ptr(sk), _ptr(tk), Ns, Nt, n, int(K), float(radius),
-                                              float(tau) if tau is not None else 0.0, _ptr(F), _ptr(m), _ptr(d), _ptr(prob),
-                                              _ptr(ws), ws.numel(), op, _stream_ptr(dev))
-    _lib.check(rc, "umereg_pair_match_ragged_f32")
+    _lib.call(dev, lib.umereg_pair_match_ragged_f32, _ptr(sp), _ptr(tp), _ptr(sf), _ptr(tf), _ptr(sk), _ptr(tk), Ns, Nt, n, int(K),
+              float(radius), float(tau) if tau is not None else 0.0, _ptr(F), _ptr(m), _ptr(d), _ptr(prob), _ptr(ws), ws.numel(), op,
+              _stream_ptr(dev))
     return F, m, d, prob
 
 
@@ -883,9 +825,9 @@ class _PairGraph:
     """What the two graph classes below share: the outputs F, m, d, prob and the workspace the captured chain writes (owned by the
     object), the capture itself, the continuation after the host draw and the lifetime of the native handle."""
 
-    def _capture(self, dev, N, n, tau, opts, create, what):
+    def _capture(self, dev, N, n, tau, opts, create):
         """Outputs and workspace of a chain sized for clouds of N points and n keypoints, then the capture:
-        create(lib, op, capture stream, handle reference) -> return code of the native entry `what`."""
+        create(lib, op, capture stream, handle reference) -> (the native entry, its arguments)."""
         import ctypes
         lib = self._lib = _lib.load()
         self.dev, self.opts = dev, opts
@@ -901,23 +843,20 @@ class _PairGraph:
         handle = ctypes.c_void_p()
         cap = torch.cuda.Stream(dev)                     # capture needs a non-default stream; nothing runs on it
         cap.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.device(dev):
-            rc = create(lib, op, cap.cuda_stream, ctypes.byref(handle))
-        _lib.check(rc, what)
+        fn, *args = create(lib, op, cap.cuda_stream, ctypes.byref(handle))
+        _lib.call(dev, fn, *args)
         self.handle = handle
 
     def solve(self, cond_host_ptr, n_cond, cond_dev, T_out, stream_ptr):
         """evaluate.py:238-254 after the host draw, from this graph's outputs (see umereg_pair_match_graph_solve)."""
-        rc = self._lib.umereg_pair_match_graph_solve(self.handle, cond_host_ptr or None, int(n_cond), cond_dev.data_ptr() if cond_dev is not None else None,
-                                                     T_out.data_ptr(), stream_ptr)
-        if rc:
-            _lib.check(rc, "umereg_pair_match_graph_solve")
+        _lib.checked(self._lib.umereg_pair_match_graph_solve, self.handle, cond_host_ptr or None, int(n_cond), _ptr(cond_dev),
+                     T_out.data_ptr(), stream_ptr)
 
     def __del__(self):
         try:
-            if getattr(self, "handle", None):
-                self._lib.umereg_pair_match_graph_destroy(self.handle)
-                self.handle = None
+            handle, self.handle = getattr(self, "handle", None), None
+            if handle:
+                _lib.checked(self._lib.umereg_pair_match_graph_destroy, handle)
         except Exception:   # noqa: BLE001  (interpreter shutdown)
             pass
 
@@ -932,10 +871,9 @@ class PairMatchCapGraph(_PairGraph):
         self.capacity, self.n_kp = int(capacity), int(n_kp)
         self.params = (int(K), float(radius), None if tau is None else float(tau), None if opts is None else opts.key())
         self._capture(torch.device(device), self.capacity, self.n_kp, tau, opts, lambda lib, op, cap, handle:
-                      lib.umereg_pair_match_graph_create_cap(self.capacity, self.n_kp, int(K), float(radius), float(tau) if tau is not None else 0.0,
-                                                             _ptr(self.F), _ptr(self.m), _ptr(self.d), _ptr(self.prob), _ptr(self.ws),
-                                                             self.ws.numel(), op, cap, handle),
-                      "umereg_pair_match_graph_create_cap")
+                      (lib.umereg_pair_match_graph_create_cap, self.capacity, self.n_kp, int(K), float(radius),
+                       float(tau) if tau is not None else 0.0, _ptr(self.F), _ptr(self.m), _ptr(self.d), _ptr(self.prob), _ptr(self.ws),
+                       self.ws.numel(), op, cap, handle))
 
     def fits(self, n_src, n_tgt, n_kp, K, radius, tau, opts=None):
         """True if a replay of this graph computes a1..a5 of a pair of these sizes with these parameters."""
@@ -945,17 +883,13 @@ class PairMatchCapGraph(_PairGraph):
     def launch(self, src_pts, tgt_pts, src_feat, tgt_feat, src_kp, tgt_kp, prob_host_ptr, stream_ptr):
         """Replay for this pair on an explicit stream (+ asynchronous copy of the probabilities into pinned host memory: address or
         0).  Tensors as pair_match_ragged takes them; nothing is copied, no torch stream / device context is touched."""
-        rc = self._lib.umereg_pair_match_graph_launch_ragged(self.handle, src_pts.data_ptr(), tgt_pts.data_ptr(), src_feat.data_ptr(),
-                                                             tgt_feat.data_ptr(), src_kp.data_ptr(), tgt_kp.data_ptr(),
-                                                             src_pts.shape[0], tgt_pts.shape[0], prob_host_ptr or None, stream_ptr)
-        if rc:
-            _lib.check(rc, "umereg_pair_match_graph_launch_ragged")
+        _lib.checked(self._lib.umereg_pair_match_graph_launch_ragged, self.handle, src_pts.data_ptr(), tgt_pts.data_ptr(),
+                     src_feat.data_ptr(), tgt_feat.data_ptr(), src_kp.data_ptr(), tgt_kp.data_ptr(), src_pts.shape[0], tgt_pts.shape[0],
+                     prob_host_ptr or None, stream_ptr)
 
     def launch_native(self, na, prob_host_ptr, stream_ptr):
         """launch() from a pre-marshalled argument tuple (evaluate.PairBatch.native(): six device addresses, N_src, N_tgt)."""
-        rc = self._lib.umereg_pair_match_graph_launch_ragged(self.handle, *na, prob_host_ptr or None, stream_ptr)
-        if rc:
-            _lib.check(rc, "umereg_pair_match_graph_launch_ragged")
+        _lib.checked(self._lib.umereg_pair_match_graph_launch_ragged, self.handle, *na, prob_host_ptr or None, stream_ptr)
 
 
 class PairMatchGraph(_PairGraph):
@@ -979,10 +913,9 @@ class PairMatchGraph(_PairGraph):
         # from the old buffers / parameters (see `matches`)
         self.signature = self.signature_of(self.pts, self.feat, self.kp_index, K, radius, tau, opts)
         self._capture(self.pts.device, N, n, tau, opts, lambda lib, op, cap, handle:
-                      lib.umereg_pair_match_graph_create_ex(_ptr(self.pts), _ptr(self.feat), _ptr(self.kp_index), N, n, int(K), float(radius),
-                                                            float(tau) if tau is not None else 0.0, _ptr(self.F), _ptr(self.m), _ptr(self.d),
-                                                            _ptr(self.prob), _ptr(self.ws), self.ws.numel(), op, cap, handle),
-                      "umereg_pair_match_graph_create_ex")
+                      (lib.umereg_pair_match_graph_create_ex, _ptr(self.pts), _ptr(self.feat), _ptr(self.kp_index), N, n, int(K), float(radius),
+                       float(tau) if tau is not None else 0.0, _ptr(self.F), _ptr(self.m), _ptr(self.d), _ptr(self.prob), _ptr(self.ws),
+                       self.ws.numel(), op, cap, handle))
 
     @staticmethod
     def signature_of(pts, feat, kp_index, K, radius, tau, opts=None):
@@ -995,17 +928,13 @@ class PairMatchGraph(_PairGraph):
         return self.handle is not None and self.signature == self.signature_of(pts, feat, kp_index, K, radius, tau, opts)
 
     def launch(self):
-        with torch.cuda.device(self.dev):
-            rc = self._lib.umereg_pair_match_graph_launch(self.handle, _stream_ptr(self.dev))
-        _lib.check(rc, "umereg_pair_match_graph_launch")
+        _lib.call(self.dev, self._lib.umereg_pair_match_graph_launch, self.handle, _stream_ptr(self.dev))
         return self.F, self.m, self.d, self.prob
 
     def launch_ex(self, prob_host_ptr, stream_ptr):
         """Replay on an explicit stream + asynchronous copy of the probabilities into pinned host memory (address or 0).
         No torch stream / device context is touched: ~20 us of host time less than launch() under `with torch.cuda.stream`."""
-        rc = self._lib.umereg_pair_match_graph_launch_ex(self.handle, prob_host_ptr or None, stream_ptr)
-        if rc:
-            _lib.check(rc, "umereg_pair_match_graph_launch_ex")
+        _lib.checked(self._lib.umereg_pair_match_graph_launch_ex, self.handle, prob_host_ptr or None, stream_ptr)
 
     def launch_from(self, pts, feat, kp_index, prob_host_ptr, stream_ptr):
         """Replay for another pair of the same shape: its inputs (contiguous f32 / int64 device tensors) are copied device to
@@ -1015,11 +944,9 @@ class PairMatchGraph(_PairGraph):
             if t.shape != mine.shape or t.dtype != mine.dtype or not t.is_contiguous() or t.device != mine.device:
                 raise ValueError(f"PairMatchGraph.launch_from: {name} must be a contiguous {mine.dtype} tensor of shape {tuple(mine.shape)} "
                                  f"on {mine.device} (got {t.dtype}, {tuple(t.shape)}, {t.device})")
-        rc = self._lib.umereg_pair_match_graph_launch_from(self.handle, pts.data_ptr(), feat.data_ptr(), kp_index.data_ptr(),
-                                                           prob_host_ptr or None, stream_ptr)
-        if rc:
-            _lib.check(rc, "umereg_pair_match_graph_launch_from")
+        _lib.checked(self._lib.umereg_pair_match_graph_launch_from, self.handle, pts.data_ptr(), feat.data_ptr(), kp_index.data_ptr(),
+                     prob_host_ptr or None, stream_ptr)
 
 
-# scipy.optimize.linear_sum_assignment on the device (include/umereg_assign.h, typed by its own table in assign.py)
+# scipy.optimize.linear_sum_assignment on the device (include/umereg_assign.h; assign.py)
 from .assign import linear_sum_assignment  # noqa: E402,F401

@@ -15,9 +15,8 @@ the transformed source (`rotate_rows`), the same calls the augmentation of a cac
 The surface reconstruction of `lidar_point_cloud_completion` (NKSR, :511-533) is not part of this library; its label-transfer
 half is (`copy_labels_nearest`), and `complete_cloud` joins a caller-supplied `completion_fn(pts) -> new_pts` to it.
 
-The entry points of include/umereg_scan_prep.h are typed by the table below; `scan_prep_raw` takes caller-owned outputs and
+The entry points of include/umereg_scan_prep.h are typed by `_lib.TABLES`; `scan_prep_raw` takes caller-owned outputs and
 workspace and never waits for the device."""
-import ctypes
 import os
 from contextlib import nullcontext
 
@@ -27,14 +26,8 @@ import torch
 from . import _lib
 from .datasets.kitti_dataset import _refuse_gpu_in_worker, quantize_on_device, rotate_rows
 
-c_void_p, c_int, c_size_t, c_int64, c_float = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int64, ctypes.c_float
-
-# name -> (restype, argtypes); mirrors include/umereg_scan_prep.h one to one
-SCAN_PREP_SIGNATURES = {
-    "umereg_scan_prep_workspace_bytes": (c_size_t, [c_int64]),
-    "umereg_scan_prep_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64, c_float, c_float, c_void_p, c_void_p,
-                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-}
+SCAN_PREP_SIGNATURES = _lib.TABLES["umereg_scan_prep.h"]
+load_native = _lib.load
 
 SCAN_SEM16, SCAN_KEEP_UNLABELED = 1, 2                       # UMEREG_SCAN_* flags
 ERR_KEY_RANGE, ERR_KEY_UNMAPPED = 1, 2                       # UMEREG_SCAN_ERR_* bits
@@ -46,13 +39,8 @@ NUSCENES_EGO_BOX = (2.5, 1.0)                                # nuscenes_dataset.
 LABEL_COPY_DIST_THR = 3.0                                    # SemanticKITTIDataset.LABEL_COPY_DIST_THR
 
 
-def load_native():
-    """libumereg.so with the entry points of include/umereg_scan_prep.h typed (raises without the built library)."""
-    return _lib.load_typed(SCAN_PREP_SIGNATURES)
-
-
 def workspace_bytes(n):
-    return int(load_native().umereg_scan_prep_workspace_bytes(int(n)))
+    return int(_lib.load().umereg_scan_prep_workspace_bytes(int(n)))
 
 
 # ---- host readers -------------------------------------------------------------------------------------------------------------
@@ -125,15 +113,11 @@ def scan_prep_raw(scan, labels, lut, flags, ego_box, out_pts, out_seg, out_index
     """Enqueue one `umereg_scan_prep_f32` on the current stream.  scan f32 [n,3|4] contiguous; labels int32 [n] holding the u32
     words, or None; lut int32 [k] or None; ego_box (hx, hy) or None; out_pts f32 [n,3], out_seg i64 [n], out_index i64 [n] or None,
     out_count i32 [2] (kept, error bits), workspace uint8 of >= workspace_bytes(n): all on one device."""
-    lib = load_native()
     hx, hy = (0.0, 0.0) if ego_box is None else ego_box
-    p = lambda t: None if t is None else t.data_ptr()        # noqa: E731
-    with torch.cuda.device(scan.device):
-        rc = lib.umereg_scan_prep_f32(scan.data_ptr(), scan.shape[0], scan.shape[1], p(labels), int(flags), p(lut),
-                                      0 if lut is None else lut.shape[0], float(hx), float(hy), out_pts.data_ptr(), out_seg.data_ptr(),
-                                      p(out_index), out_count.data_ptr(), workspace.data_ptr(), workspace.numel(),
-                                      torch.cuda.current_stream(scan.device).cuda_stream)
-    _lib.check(rc, "umereg_scan_prep_f32")
+    p = _lib.ptr
+    _lib.call(scan.device, _lib.load().umereg_scan_prep_f32, scan.data_ptr(), scan.shape[0], scan.shape[1], p(labels), int(flags), p(lut),
+              0 if lut is None else lut.shape[0], float(hx), float(hy), out_pts.data_ptr(), out_seg.data_ptr(), p(out_index),
+              out_count.data_ptr(), workspace.data_ptr(), workspace.numel(), _lib.stream_ptr(scan.device))
 
 
 def _device(device):

@@ -8,33 +8,15 @@ forms the forward's quantities again in fp64 and differentiates the rotation its
 SVD has it), so repeated singular values are harmless.  A pair of singular directions whose signed values sum to no more than
 MIN_GAP times the largest contributes nothing (include/umereg_rtume_grad.h states the convention).  The backward is deterministic
 bit for bit, runs on the current stream and never waits for the device."""
-import ctypes
-
 import torch
 
 from . import _lib, ops
 
-c_void_p, c_int = ctypes.c_void_p, ctypes.c_int
-
-# name -> (restype, argtypes); mirrors include/umereg_rtume_grad.h one to one
-RTUME_GRAD_SIGNATURES = {
-    "umereg_rtume_solve_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
-}
+RTUME_GRAD_SIGNATURES = _lib.TABLES["umereg_rtume_grad.h"]
+load_native = _lib.load
+_on_gpu = _lib.on_gpu
 
 MIN_GAP = 1e-8      # UMEREG_RTUME_BWD_MIN_GAP: s'_i + s'_j <= MIN_GAP * s1 -> the pair (i, j) has no gradient
-
-
-def load_native():
-    """libumereg.so with the entry point of include/umereg_rtume_grad.h typed (raises without the built library)."""
-    return _lib.load_typed(RTUME_GRAD_SIGNATURES)
-
-
-def _on_gpu(who, *tensors):
-    for t in tensors:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: expected torch tensors, got {type(t).__name__}")
-        if t.device.type != "cuda":
-            raise RuntimeError(f"{who}: CPU tensors given; umeregrobust_amd has no CPU fallback (move the input to the GPU)")
 
 
 def _check_shapes(who, G, H):
@@ -44,7 +26,7 @@ def _check_shapes(who, G, H):
 
 def rtume_bwd_raw(G, H, dT, need_g=True, need_h=True):
     """(dG, dH) of T = rtume_solve(G, H) for upstream dT [n, 4, 4]; a side that is not needed is None."""
-    lib = load_native()
+    lib = _lib.load()
     _on_gpu("rtume_solve backward", G, H, dT)
     _check_shapes("rtume_solve backward", G, H)
     n = G.shape[0]
@@ -55,10 +37,8 @@ def rtume_bwd_raw(G, H, dT, need_g=True, need_h=True):
     dH = torch.empty_like(H) if need_h else None
     if n == 0 or not (need_g or need_h):
         return dG, dH
-    with torch.cuda.device(G.device):
-        rc = lib.umereg_rtume_solve_bwd_f32(G.data_ptr(), H.data_ptr(), dT.data_ptr(), n, dG.data_ptr() if need_g else None,
-                                            dH.data_ptr() if need_h else None, torch.cuda.current_stream(G.device).cuda_stream)
-    _lib.check(rc, "umereg_rtume_solve_bwd_f32")
+    _lib.call(G.device, lib.umereg_rtume_solve_bwd_f32, G.data_ptr(), H.data_ptr(), dT.data_ptr(), n, dG.data_ptr() if need_g else None,
+              dH.data_ptr() if need_h else None, _lib.stream_ptr(G.device))
     return dG, dH
 
 

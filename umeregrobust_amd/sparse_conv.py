@@ -18,51 +18,19 @@ gradient is scaled by 2^e (`grad_scale`: e computed on the device, no host sync)
 [2^14, 2^15) before it is rounded; the scaled gradient feeds both gradients and 2^-e is applied to the results (the input
 gradient's epilogue scale, one multiplication of dW).  The saved input is the f32 the forward rounded, so dW is the exact
 straight-through gradient of the forward.  Inputs, kernels, outputs and gradients are f32 tensors in both precisions."""
-import ctypes
-
 import torch
 
 from . import _lib
 from . import models as _models
 
-c_void_p, c_int, c_size_t = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-
-# name -> (restype, argtypes); mirrors include/umereg_sparse_conv.h one to one
-SPARSE_CONV_SIGNATURES = {
-    "umereg_sparse_conv_f32": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
-                                       c_void_p, c_void_p, c_int, c_int, c_void_p]),
-    "umereg_sparse_conv1_f32": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "umereg_sparse_conv_repack_f32": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "umereg_sparse_conv_wgrad_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "umereg_sparse_conv_wgrad_segments": (c_int, [c_int, c_int, c_int]),
-    "umereg_sparse_conv_wgrad_f32": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
-                                             c_void_p, c_void_p, c_size_t, c_void_p]),
-}
-
-# name -> (restype, argtypes); mirrors include/umereg_sparse_conv_f16.h one to one
-SPARSE_CONV_F16_SIGNATURES = {
-    "umereg_sparse_conv_wgrad_f16": SPARSE_CONV_SIGNATURES["umereg_sparse_conv_wgrad_f32"],
-}
-
-# name -> (restype, argtypes); mirrors include/umereg_sparse_conv_pairs.h one to one: the arguments of the union engine's entries + int f16
-SPARSE_CONV_PAIRS_SIGNATURES = {
-    "umereg_featnet_forward_pairs": (c_int, _models.FEATNET_SIGNATURES["umereg_featnet_forward_f32"][1] + [c_int]),
-    "umereg_sparse_conv_pairs": (c_int, SPARSE_CONV_SIGNATURES["umereg_sparse_conv_f32"][1] + [c_int]),
-}
-
+SPARSE_CONV_SIGNATURES = _lib.TABLES["umereg_sparse_conv.h"]
+SPARSE_CONV_F16_SIGNATURES = _lib.TABLES["umereg_sparse_conv_f16.h"]
+SPARSE_CONV_PAIRS_SIGNATURES = _lib.TABLES["umereg_sparse_conv_pairs.h"]
+load_native = _lib.load
 N_TABLES, MAX_CH = 13, 256
 # input channels per launch of the plain convolution: a longer contraction runs as slices accumulated in order (two-level
 # summation; one chain over 27 x 256 products carries about twice the rounding error of eight chains over 27 x 32)
 SLICE = 32
-
-
-def load_native():
-    """libumereg.so with the entry points of include/umereg_sparse_conv.h, umereg_sparse_conv_f16.h and
-    umereg_sparse_conv_pairs.h (and of umereg_featnet.h) typed (raises without the built library)."""
-    _models.load_native()
-    _lib.load_typed(SPARSE_CONV_SIGNATURES)
-    _lib.load_typed(SPARSE_CONV_PAIRS_SIGNATURES)
-    return _lib.load_typed(SPARSE_CONV_F16_SIGNATURES)
 
 
 def out_level(table):
@@ -82,10 +50,6 @@ def adjoint(table):
     return (table + 4, False) if table < 9 else (table - 4, False)
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 class CoordinateMaps:
     """The five levels and 13 neighbour tables of one coordinate set (int32 [n, 4]: batch index, x, y, z; on the GPU), built
     once with umereg_featnet_build_maps.  Owns the workspace the tables live in -- keep it alive until the backward pass is
@@ -93,9 +57,7 @@ class CoordinateMaps:
     host sync; duplicate or out-of-range coordinates raise here); `perm`: int64 [n], the input row of level-0 row j."""
 
     def __init__(self, coords, batch):
-        if coords.device.type != "cuda":
-            raise RuntimeError("CoordinateMaps: CPU tensors given; umeregrobust_amd has no CPU fallback (move the input to the GPU)")
-        load_native()
+        _lib.on_gpu("CoordinateMaps", coords)
         self.coords = coords.to(torch.int32).contiguous()
         self.n, self.batch, self.device = int(coords.shape[0]), int(batch), coords.device
         if self.n == 0:
@@ -123,14 +85,12 @@ class CoordinateMaps:
         return self._scratch
 
 
-def _rows(t, what):
-    if t.device.type != "cuda":
-        raise RuntimeError(f"sparse_conv: {what} on the CPU; umeregrobust_amd has no CPU fallback")
-    if t.dtype != torch.float32 or t.dim() != 2:
-        raise ValueError(f"sparse_conv: {what} must be f32 [rows, channels], got {t.dtype} {tuple(t.shape)}")
-    if t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < t.shape[1] or t.data_ptr() % 16:
-        t = t.contiguous()
-    return t
+def _launch(lib, pairs, f16, dev, *args):
+    """one launch of the 27-offset convolution on the chosen engine: `args` are the sixteen arguments the three entries share"""
+    if pairs:
+        _lib.call(dev, lib.umereg_sparse_conv_pairs, *args, int(f16))
+    else:
+        _lib.call(dev, lib.umereg_sparse_conv_f16 if f16 else lib.umereg_sparse_conv_f32, *args)
 
 
 def conv_raw(x, kernel, maps, table, transpose=False, mirror=False, precision="f32", scale=None, conv_mode="union"):
@@ -143,8 +103,8 @@ def conv_raw(x, kernel, maps, table, transpose=False, mirror=False, precision="f
     the same values bit for bit (the 1x1 layer runs the union engine's kernel either way)."""
     _models.check_precision(precision)
     pairs = _models.check_conv_mode(conv_mode) == "pairs"
-    lib = load_native()
-    x = _rows(x, "input")
+    lib = _lib.load()
+    x = _lib.rows(x, "sparse_conv", "input")
     if precision == "f16":
         return _conv_f16(lib, x, kernel, maps, table, transpose, mirror, scale, pairs)
     if scale is not None:
@@ -162,10 +122,9 @@ def conv_raw(x, kernel, maps, table, transpose=False, mirror=False, precision="f
     else:
         kernel = kernel.contiguous()
     for s in range(cin // step):
-        args = (maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, table, x.data_ptr() + 4 * s * step, x.stride(0),
-                kernel.data_ptr() + 4 * s * 27 * step * cout, step, cout, maps.ones.data_ptr(), maps.zeros.data_ptr(), out.data_ptr(),
-                cout, int(s > 0), _stream(x.device))
-        _lib.check(lib.umereg_sparse_conv_pairs(*args, 0) if pairs else lib.umereg_sparse_conv_f32(*args), "sparse_conv")
+        _launch(lib, pairs, False, x.device, maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, table,
+                x.data_ptr() + 4 * s * step, x.stride(0), kernel.data_ptr() + 4 * s * 27 * step * cout, step, cout, maps.ones.data_ptr(),
+                maps.zeros.data_ptr(), out.data_ptr(), cout, int(s > 0), _lib.stream_ptr(x.device))
     return out
 
 
@@ -193,35 +152,35 @@ def _conv_f16(lib, x, kernel, maps, table, transpose, mirror, scale=None, pairs=
         scale = maps.ones
     elif scale.dtype != torch.float32 or scale.device != x.device or scale.dim() != 1 or scale.numel() < cout or not scale.is_contiguous():
         raise ValueError(f"sparse_conv: scale must be contiguous f32 [>= {cout}] on {x.device}")
-    args = (maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, table, x.data_ptr(), x.stride(0), kernel.data_ptr(), cin,
-            cout, scale.data_ptr(), maps.zeros.data_ptr(), out.data_ptr(), cout, 0, _stream(x.device))
-    _lib.check(lib.umereg_sparse_conv_pairs(*args, 1) if pairs else lib.umereg_sparse_conv_f16(*args), "sparse_conv_f16")
+    _launch(lib, pairs, True, x.device, maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, table, x.data_ptr(),
+            x.stride(0), kernel.data_ptr(), cin, cout, scale.data_ptr(), maps.zeros.data_ptr(), out.data_ptr(), cout, 0,
+            _lib.stream_ptr(x.device))
     return out
 
 
 def conv1_raw(feat, kernel, maps):
     """conv1: feat f32 [n, 1] in INPUT row order, kernel [27, 1, 32] -> [rows of level 0, 32] in level-0 order"""
-    lib = load_native()
+    lib = _lib.load()
     feat = feat.contiguous()
     if feat.shape != (maps.n, 1) or tuple(kernel.shape) != (27, 1, 32):
         raise ValueError(f"sparse_conv1: features [{maps.n}, 1] and a [27, 1, 32] kernel, got {tuple(feat.shape)} / {tuple(kernel.shape)}")
     out = torch.empty(maps.n, 32, dtype=torch.float32, device=feat.device)
     kernel = kernel.contiguous()
-    _lib.check(lib.umereg_sparse_conv1_f32(maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, feat.data_ptr(),
-                                           kernel.data_ptr(), maps.ones.data_ptr(), maps.zeros.data_ptr(), out.data_ptr(),
-                                           _stream(feat.device)), "sparse_conv1")
+    _lib.call(feat.device, lib.umereg_sparse_conv1_f32, maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n,
+              feat.data_ptr(), kernel.data_ptr(), maps.ones.data_ptr(), maps.zeros.data_ptr(), out.data_ptr(),
+              _lib.stream_ptr(feat.device))
     return out
 
 
 def repack_raw(kernel, transpose, mirror, slice):
     """[27, C_in, C_out] -> R / slice blocks [27, slice, C] of M (M[k'] = kernel[k]^T if `transpose` else kernel[k]; R, C its rows
     and columns; k' = 26 - k if `mirror`), as one flat tensor (include/umereg_sparse_conv.h)"""
-    lib = load_native()
+    lib = _lib.load()
     K, cin, cout = kernel.shape
     kernel = kernel.contiguous()
     out = torch.empty(K * cin * cout, dtype=torch.float32, device=kernel.device)
-    _lib.check(lib.umereg_sparse_conv_repack_f32(kernel.data_ptr(), cin, cout, int(bool(transpose)), int(bool(mirror)), int(slice),
-                                                 out.data_ptr(), _stream(kernel.device)), "sparse_conv_repack")
+    _lib.call(kernel.device, lib.umereg_sparse_conv_repack_f32, kernel.data_ptr(), cin, cout, int(bool(transpose)), int(bool(mirror)),
+              int(slice), out.data_ptr(), _lib.stream_ptr(kernel.device))
     return out
 
 
@@ -230,12 +189,12 @@ def wgrad_raw(x, dy, maps, table, precision="f32"):
     precision="f16" (include/umereg_sparse_conv_f16.h): x and dy rounded to f16, sums in f32, C_in a multiple of 32; dy as it is
     given -- the caller scales it (`grad_scale`) and unscales the result."""
     _models.check_precision(precision)
-    lib = load_native()
-    dy = _rows(dy, "output gradient")
+    lib = _lib.load()
+    dy = _lib.rows(dy, "sparse_conv", "output gradient")
     if x.shape[1] == 1:
         x = x.contiguous()
     else:
-        x = _rows(x, "input")
+        x = _lib.rows(x, "sparse_conv", "input")
     cin, cout = x.shape[1], dy.shape[1]
     if x.shape[0] != maps.sizes[in_level(table)] or dy.shape[0] != maps.sizes[out_level(table)]:
         raise ValueError(f"sparse_conv_wgrad: table {table}: {x.shape[0]} input rows / {dy.shape[0]} gradient rows")
@@ -245,9 +204,8 @@ def wgrad_raw(x, dy, maps, table, precision="f32"):
     scratch = maps.scratch(need)
     dw = torch.empty(27, cin, cout, dtype=torch.float32, device=x.device)
     fn = lib.umereg_sparse_conv_wgrad_f16 if precision == "f16" else lib.umereg_sparse_conv_wgrad_f32
-    _lib.check(fn(maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, table, x.data_ptr(), x.stride(0), cin,
-                  dy.data_ptr(), dy.stride(0), cout, dw.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream(x.device)),
-               "sparse_conv_wgrad" if precision == "f32" else "sparse_conv_wgrad_f16")
+    _lib.call(x.device, fn, maps.ws.data_ptr(), maps.ws.numel(), maps.status.data_ptr(), maps.n, table, x.data_ptr(), x.stride(0), cin,
+              dy.data_ptr(), dy.stride(0), cout, dw.data_ptr(), scratch.data_ptr(), scratch.numel(), _lib.stream_ptr(x.device))
     return dw
 
 
@@ -344,8 +302,7 @@ def sparse_conv(x, kernel, maps, table, precision="f32", fused_scale=False, conv
     _models.check_conv_mode(conv_mode)
     if not 0 <= table < N_TABLES:
         raise ValueError(f"sparse_conv: table {table} outside [0, {N_TABLES})")
-    if x.device.type != "cuda" or kernel.device.type != "cuda":
-        raise RuntimeError("sparse_conv: CPU tensors given; umeregrobust_amd has no CPU fallback (move the input to the GPU)")
+    _lib.on_gpu("sparse_conv", x, kernel)
     if kernel.dim() != 3 or kernel.shape[0] != 27:
         raise ValueError(f"sparse_conv: kernel must be [27, C_in, C_out], got {tuple(kernel.shape)}")
     if kernel.shape[1] == 1:
@@ -416,7 +373,6 @@ def linear(x, W, precision="f32", maps=None, fused_scale=False):
     if precision == "f16":
         if maps is None:
             raise ValueError("linear: precision='f16' runs on the HIP convolution and needs the CoordinateMaps of its rows (maps=...)")
-        if x.device.type != "cuda" or W.device.type != "cuda":
-            raise RuntimeError("linear: CPU tensors given; umeregrobust_amd has no CPU fallback (move the input to the GPU)")
+        _lib.on_gpu("linear", x, W)
         return _LinearF16.apply(x, W, maps, bool(fused_scale))
     return _Linear.apply(x, W)

@@ -29,9 +29,8 @@ def run_side_by_side(a, b, spin_ms=SPIN_MS):
     lib = _lib.load()
     out = ctypes.c_int(0)
     ms = ctypes.c_float(0.0)
-    with torch.cuda.device(a.device):
-        rc = lib.umereg_streams_run_side_by_side(a.cuda_stream, b.cuda_stream, float(spin_ms), ctypes.byref(out), ctypes.byref(ms))
-    _lib.check(rc, "umereg_streams_run_side_by_side")
+    _lib.call(a.device, lib.umereg_streams_run_side_by_side, a.cuda_stream, b.cuda_stream, float(spin_ms), ctypes.byref(out),
+              ctypes.byref(ms))
     return bool(out.value)
 
 

@@ -8,43 +8,16 @@ Forward values are those of `ops.ume_moments` / `ops.ume_cdist` (the same calls)
 neighbour lists the forward wrote (`return_idx=True`), never a second ball search; the distance's backward reads the D the
 forward returned.  A pair with D <= D_MIN has no gradient and contributes nothing (torch's cdist backward gives 0 there too).
 Both backward passes are deterministic bit for bit, run on the current stream and never wait for the device."""
-import ctypes
-
 import torch
 
 from . import _lib, ops
 
-c_void_p, c_int, c_size_t = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
-
-# name -> (restype, argtypes); mirrors include/umereg_ume_grad.h one to one
-UME_GRAD_SIGNATURES = {
-    "umereg_ume_moments_bwd_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
-    "umereg_ume_moments_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
-                                           c_void_p, c_size_t, c_void_p]),
-    "umereg_ume_cdist_bwd_scratch_bytes": (c_size_t, [c_int, c_int]),
-    "umereg_ume_cdist_bwd_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
-                                         c_void_p]),
-}
+UME_GRAD_SIGNATURES = _lib.TABLES["umereg_ume_grad.h"]
+load_native = _lib.load
+_on_gpu = _lib.on_gpu
 
 D_MIN = 4e-3        # UMEREG_UME_CDIST_BWD_DMIN: at or below it a pair has no gradient (the forward's noise floor at D = 0)
 MAX_K = 7680        # UMEREG_UME_GRAD_MAX_K
-
-
-def load_native():
-    """libumereg.so with the entry points of include/umereg_ume_grad.h typed (raises without the built library)."""
-    return _lib.load_typed(UME_GRAD_SIGNATURES)
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _on_gpu(who, *tensors):
-    for t in tensors:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{who}: expected torch tensors, got {type(t).__name__}")
-        if t.device.type != "cuda":
-            raise RuntimeError(f"{who}: CPU tensors given; umeregrobust_amd has no CPU fallback (move the input to the GPU)")
 
 
 def _scratch(dev, nbytes):
@@ -54,7 +27,7 @@ def _scratch(dev, nbytes):
 def moments_bwd_raw(pts, feat, nn_idx, F, dF, normalize=True, scratch=None):
     """dfeat f32 [B, N, 32] of the moments whose forward wrote `nn_idx` (int64 [B, n, K]) and `F`; dF: f32 [B, n, 32, 4].
     `feat` and `F` are read by the normalised form only."""
-    lib = load_native()
+    lib = _lib.load()
     _on_gpu("ume_moments backward", pts, nn_idx, dF)
     pts, dF = pts.float().contiguous(), dF.float().contiguous()
     nn_idx = nn_idx.contiguous()
@@ -76,17 +49,15 @@ def moments_bwd_raw(pts, feat, nn_idx, F, dF, normalize=True, scratch=None):
         raise ValueError(f"ume_moments backward: sizes B = {B}, N = {N}, n = {n} not supported")
     if scratch is None:
         scratch = _scratch(pts.device, need)
-    with torch.cuda.device(pts.device):
-        rc = lib.umereg_ume_moments_bwd_f32(pts.data_ptr(), feat.data_ptr() if normalize else None, nn_idx.data_ptr(),
-                                            F.data_ptr() if normalize else None, dF.data_ptr(), B, N, n, K, int(bool(normalize)),
-                                            dfeat.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream(pts.device))
-    _lib.check(rc, "umereg_ume_moments_bwd_f32")
+    _lib.call(pts.device, lib.umereg_ume_moments_bwd_f32, pts.data_ptr(), feat.data_ptr() if normalize else None, nn_idx.data_ptr(),
+              F.data_ptr() if normalize else None, dF.data_ptr(), B, N, n, K, int(bool(normalize)), dfeat.data_ptr(), scratch.data_ptr(),
+              scratch.numel(), _lib.stream_ptr(pts.device))
     return dfeat
 
 
 def cdist_bwd_raw(ume1, ume2, D, dD, need1=True, need2=True, scratch=None):
     """(dume1, dume2) of D = ume_cdist(ume1, ume2) for upstream dD; a side that is not needed is None.  ume [B, n, 32, 4]."""
-    lib = load_native()
+    lib = _lib.load()
     _on_gpu("ume_cdist backward", ume1, ume2, D, dD)
     ume1, ume2 = ume1.float().contiguous(), ume2.float().contiguous()
     D, dD = D.float().contiguous(), dD.float().contiguous()
@@ -103,13 +74,11 @@ def cdist_bwd_raw(ume1, ume2, D, dD, need1=True, need2=True, scratch=None):
         raise ValueError(f"ume_cdist backward: sizes n1 = {n1}, n2 = {n2} not supported")
     if scratch is None:
         scratch = _scratch(ume1.device, need)
-    st = _stream(ume1.device)
+    st = _lib.stream_ptr(ume1.device)
     with torch.cuda.device(ume1.device):
         for b in range(B):      # one launch chain per batch element, like the forward; the scratch is reused in stream order
-            rc = lib.umereg_ume_cdist_bwd_f32(ume1[b].data_ptr(), ume2[b].data_ptr(), D[b].data_ptr(), dD[b].data_ptr(), n1, n2,
-                                              d1[b].data_ptr() if need1 else None, d2[b].data_ptr() if need2 else None,
-                                              scratch.data_ptr(), scratch.numel(), st)
-            _lib.check(rc, "umereg_ume_cdist_bwd_f32")
+            _lib.checked(lib.umereg_ume_cdist_bwd_f32, ume1[b].data_ptr(), ume2[b].data_ptr(), D[b].data_ptr(), dD[b].data_ptr(), n1, n2,
+                         d1[b].data_ptr() if need1 else None, d2[b].data_ptr() if need2 else None, scratch.data_ptr(), scratch.numel(), st)
     return d1, d2
 
 
