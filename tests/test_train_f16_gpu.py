@@ -19,6 +19,7 @@ import test_featnet_f16_gpu as f16g
 import test_featnet_gpu as fg
 import test_sparse_grad_gpu as sg
 import test_train_f16_cpu as tc
+from wgrad_cases import block_of, line          # (shared with tests/test_wgrad_edges_gpu.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -173,19 +174,6 @@ def test_backward_scaling_works_and_is_exact(gpu, op):
 
 
 # ---- 4: groups of 16, empty offsets, one and two segments ---------------------------------------------------------------------------
-
-def line(m):
-    return np.stack([np.zeros(m, np.int64), np.arange(m) - 5, np.full(m, 3), np.full(m, -2)], 1)
-
-
-def block_of(n):
-    """n level-0 rows: a dense 16 x 8 x 8 block, and beyond 1024 isolated points far away"""
-    g = np.stack(np.meshgrid(np.arange(16), np.arange(8), np.arange(8), indexing="ij"), -1).reshape(-1, 3)
-    far = np.stack([1000 + 50 * np.arange(n - 1024), np.zeros(n - 1024, np.int64), np.zeros(n - 1024, np.int64)], 1)
-    c = np.concatenate([g, far]).astype(np.int64)
-    c = c[np.random.default_rng(n).permutation(len(c))]
-    return np.concatenate([np.zeros((len(c), 1), np.int64), c], 1)
-
 
 EDGE_CLOUDS = {**{f"line{m}": (lambda m=m: line(m)) for m in (1, 2, 16, 17, 18, 33)}, "isolated": lambda: fg.edge_cloud("isolated"),
                "rows1024": lambda: block_of(1024), "rows1025": lambda: block_of(1025)}
