@@ -49,11 +49,12 @@ def solve_grads(G, H, dT):
     return T.detach(), a.grad, b.grad
 
 
-def solve_grads_closed_form(G, H, dT, min_gap=0.0):
+def solve_grads_closed_form(G, H, dT, min_gap=0.0, parts=None):
     """(dG, dH) of <solve(G, H), dT>: product and quotient rules by hand, and for the rotation R = U V'^T (V' = V diag(1, 1, d),
     s' = (s1, s2, d s3)):  C = U^T gR V',  Y_ij = (C_ij - C_ji) / (s'_i + s'_j),  gA = U Y V'^T; pairs with
-    s'_i + s'_j <= min_gap * s1 get Y_ij = 0."""
-    mg, mh, g, h, mg_square, mg_mh, wlc, wrc, left, right = _parts(G, H)
+    s'_i + s'_j <= min_gap * s1 get Y_ij = 0.  `parts`: a stand-in for `_parts` (a test of the tests: a deliberately wrong
+    restatement must be told from this one)."""
+    mg, mh, g, h, mg_square, mg_mh, wlc, wrc, left, right = (parts or _parts)(G, H)
     A = left.transpose(1, 2) @ right
     U, S, Vh = torch.linalg.svd(A)
     d = torch.sign(torch.det(U @ Vh))

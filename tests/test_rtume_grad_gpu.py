@@ -4,7 +4,8 @@ across the convention at the rotation's singularity, twice between guard bands, 
 (tests/golden/g15_cube_registration.npz) and the trainer's `ume + reg` through the whole graph.
 
 Yardsticks: tests/cube_loss_ref.py in fp64 is the truth; the SAME helper in fp32 on the CPU sets every gate
-(max |gpu - fp64| <= 4 max |fp32 helper - fp64| per tensor, ume_grad_ref.gate); never the GPU's own output."""
+(max |gpu - fp64| <= 4 max |fp32 helper - fp64| per tensor, ume_grad_ref.gate, and per hypothesis in `check_solve`,
+rtume_grad_cases.row_gate); never the GPU's own output."""
 import functools
 import os
 
@@ -13,6 +14,7 @@ import pytest
 import torch
 
 import cube_loss_ref as cref
+import rtume_grad_cases as rc
 import ume_grad_ref as uref
 from test_abi_guard import Guard
 
@@ -49,6 +51,9 @@ def check_solve(gpu, n, thin):
     assert float((T.cpu().double() - truth[0]).abs().max()) <= 4 * float((yard[0].double() - truth[0]).abs().max())
     uref.gate(dG, truth[1], yard[1], f"dG n={n} thin={thin}")
     uref.gate(dH, truth[2], yard[2], f"dH n={n} thin={thin}")
+    # and per hypothesis: every 32 x 4 gradient on its own scale (tests/rtume_grad_cases.py; the edges: test_rtume_grad_edges_gpu.py)
+    rc.row_gate(dG, truth[1], yard[1], f"dG n={n} thin={thin}")
+    rc.row_gate(dH, truth[2], yard[2], f"dH n={n} thin={thin}")
     return s1_s3, flips
 
 

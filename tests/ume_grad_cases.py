@@ -254,14 +254,14 @@ def row_stats(got, truth, yard, groups=None):
     return {k: (float(e_gpu[m].median()), float(e_gpu[m].max()), float(e_cpu[m].median()), float(e_cpu[m].max())) for k, m in groups.items()}
 
 
-def row_gate(got, truth, yard, name, groups=None, bar=None, log=print):
+def row_gate(got, truth, yard, name, groups=None, bar=None, log=print, tag="ume ladder"):
     """Every row's relative error of `got` (the GPU's) <= 4 x the largest row-relative error of `yard` (the fp32 helper on the CPU)
     over the same rows; `groups`: {name: bool mask over the rows}, each judged against its own rows.  `bar`: a second, absolute
-    bound on the GPU's row-relative error.  Prints what it saw and returns the largest ratio."""
+    bound on the GPU's row-relative error.  Prints what it saw under `tag` and returns the largest ratio."""
     worst = 0.0
     for k, (g_med, g_max, c_med, c_max) in row_stats(got, truth, yard, groups).items():
         ratio = g_max / c_max if c_max > 0 else (0.0 if g_max == 0 else float("inf"))
-        log(f"[ume ladder] {name} {k}: gpu row-rel median {g_med:.2e} max {g_max:.2e} | fp32 helper median {c_med:.2e} max {c_max:.2e} | "
+        log(f"[{tag}] {name} {k}: gpu row-rel median {g_med:.2e} max {g_max:.2e} | fp32 helper median {c_med:.2e} max {c_max:.2e} | "
             f"ratio {ratio:.3f}" + ("" if bar is None else f" | bar {bar:.2e}: {g_max / bar:.3f} of it"))
         assert np.isfinite(g_max), f"{name} {k}"
         assert g_max <= 4 * c_max, f"{name} {k}: a row at {g_max:.3e} > 4 x {c_max:.3e}"
