@@ -34,7 +34,10 @@ is computed, the order in which the host RNG is consumed and everything that is 
 
 `--device-assignment` (`run(..., device_assignment=True)`) gives the validation epoch's inlier ratio the device solver
 (`calc_inliear_ratio(..., assignment="device")`): the distance matrices of a validation batch stay on the GPU and are solved side
-by side instead of one after another by scipy on the host.  Off by default."""
+by side instead of one after another by scipy on the host.  Off by default.
+
+`--fused-pointwise` (`run(..., fused_pointwise=True)`) computes the point-wise term with `pw_loss.MyInfoNCELossNoSeg`: one fused HIP
+forward and backward (csrc/infonce_api.h) instead of the torch statements of `loss.MyInfoNCELossNoSeg`.  Off by default."""
 import argparse
 import json
 import os
@@ -51,6 +54,7 @@ from .collate import batch_collate_fn_dset_device
 from .datasets.kitti_dataset import CachedPairDataset, batch_collate_fn_dset
 from .loss import MyInfoNCELossNoSeg
 from .models import ResUNetSmall2
+from .pw_loss import MyInfoNCELossNoSeg as FusedInfoNCELossNoSeg
 from .sparse import SparseTensor
 from .ume_loss import UMEContrastiveLoss
 from .utils.eval_utils import calc_inliear_ratio
@@ -430,7 +434,7 @@ def make_loaders(args, synthetic=0, synthetic_points=3000, device_collate=False)
 
 
 def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=None, device_collate=False, device_assignment=False,
-        train_precision="f32", fused_norm=False, conv_mode="union"):
+        train_precision="f32", fused_norm=False, conv_mode="union", fused_pointwise=False):
     """train_coloring.py:263-437 -> the run directory.  Quirks kept: every "best" file stores the validation TOTAL loss; the
     UME and point-wise "best" follow the total (eval_one_epoch returns it three times); without the registration loss the validation
     registration loss is 0.0, so `best_reg_loss` (from inf) is written once, after the first epoch, and `best_mCHR` (from 0.0) never.
@@ -440,7 +444,9 @@ def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=
     are the same either way); a non-finite loss then raises FloatingPointError.
     fused_norm: batch norm, residual and ReLU of the layer-wise path on the kernels of include/umereg_bn_act.h (models.py; the same
     parameters and checkpoint keys).
-    conv_mode: "union", or "pairs" for the pair-compacted engine of the 27-offset convolutions (models.py; the same values bit for bit)."""
+    conv_mode: "union", or "pairs" for the pair-compacted engine of the 27-offset convolutions (models.py; the same values bit for bit).
+    fused_pointwise: the point-wise loss is `pw_loss.MyInfoNCELossNoSeg`, the fused HIP forward and backward of csrc/infonce_api.h, in
+    place of the torch statements of `loss.MyInfoNCELossNoSeg` (same constructor and call; values agree to fp32 rounding)."""
     torch.manual_seed(args.random_seed)
     np.random.seed(args.random_seed)
     device = torch.device(args.device)
@@ -453,7 +459,8 @@ def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=
     dloader_train, dloader_valid = make_loaders(args, synthetic, synthetic_points, device_collate)
     model = ResUNetSmall2(in_channels=1, out_channels=args.out_channels, trainable=True, train_precision=train_precision,
                           fused_norm=fused_norm, conv_mode=conv_mode).to(device)
-    point_wise_loss_fn = MyInfoNCELossNoSeg(num_samples=args.num_pw_samples, tau=args.tau, neg_euclid_dist=NEG_EUCLID_DIST)
+    pw_class = FusedInfoNCELossNoSeg if fused_pointwise else MyInfoNCELossNoSeg
+    point_wise_loss_fn = pw_class(num_samples=args.num_pw_samples, tau=args.tau, neg_euclid_dist=NEG_EUCLID_DIST)
     ctx = TrainContext(args)
     optimizer = optim.Adam(model.parameters(), lr=args.lr, weight_decay=WEIGHT_DECAY)
     start_epoch = resume(args.resume_train_path, model, optimizer, device) if args.resume_train_path != '' else 0
@@ -504,6 +511,8 @@ def main(argv=None):
                         help="run the network's batch norm, residual and ReLU (and the f16 gradient scale) on the fused HIP kernels")
     parser.add_argument('--conv-mode', choices=['union', 'pairs'], default='union',
                         help="engine of the network's 27-offset convolutions, forward and input gradient (pairs: pair-compacted; same values)")
+    parser.add_argument('--fused-pointwise', action='store_true',
+                        help="run the point-wise InfoNCE loss, forward and backward, on the fused HIP kernels (pw_loss.MyInfoNCELossNoSeg)")
     cli = parser.parse_args(argv)
     over = {k: v for k, v in (("cache_data_path", cli.cache), ("num_epochs", cli.epochs), ("batch_size", cli.batch_size),
                               ("output_path", cli.output_path), ("resume_train_path", cli.resume)) if v is not None}
@@ -515,7 +524,7 @@ def main(argv=None):
     print(f"Train {args.dataset} config: {cli.config_path or 'built-in defaults'}")
     out = run(args, synthetic=cli.synthetic, synthetic_points=cli.synthetic_points, device_collate=cli.device_collate,
               device_assignment=cli.device_assignment, train_precision=cli.train_precision, fused_norm=cli.fused_norm,
-              conv_mode=cli.conv_mode)
+              conv_mode=cli.conv_mode, fused_pointwise=cli.fused_pointwise)
     print(f"run directory: {out}")
     return out
 
