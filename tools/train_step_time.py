@@ -74,7 +74,7 @@ class timed:
         self.b.record()
 
 
-def step_phases(points, batch, steps, warmup, dev, train_precision="f32", fused_norm=False, fused_pointwise=False):
+def step_phases(points, batch, steps, warmup, dev, train_precision="f32", fused_norm=False, fused_pointwise=False, device_keypoints=False):
     from umeregrobust_amd import train_coloring as tc
     from umeregrobust_amd.datasets.kitti_dataset import augmented_item, batch_collate_fn_dset, read_cached_pair, write_cached_pair
     from umeregrobust_amd.loss import MyInfoNCELossNoSeg
@@ -93,7 +93,7 @@ def step_phases(points, batch, steps, warmup, dev, train_precision="f32", fused_
         from umeregrobust_amd.pw_loss import MyInfoNCELossNoSeg             # noqa: F811  (the fused class, same constructor)
     pw = MyInfoNCELossNoSeg(num_samples=args.num_pw_samples, tau=args.tau, neg_euclid_dist=tc.NEG_EUCLID_DIST)
     opt = torch.optim.Adam(model.parameters(), lr=args.lr, weight_decay=0.0)
-    ctx = tc.TrainContext(args)
+    ctx = tc.TrainContext(args, selection="device" if device_keypoints else "torch")
     ph = Phases()
     n_pts = None
     for _ in range(warmup + steps):
@@ -131,7 +131,7 @@ def step_phases(points, batch, steps, warmup, dev, train_precision="f32", fused_
     per_item = {"aug_to_device": 2, "aug_thinning": 2, "aug_grid_points": 2, "aug_matches": 1, "aug_to_host": 1, "item_read_host": 1,
                 "aug_item_wall_host": 1}
     per_step = {k: round(v * per_item.get(k, 0) * batch, 4) if k in per_item else v for k, v in med.items()}
-    return {"kind": "phases", "train_precision": train_precision, "fused_norm": bool(fused_norm), "fused_pointwise": bool(fused_pointwise), "points": points, "batch": batch, "steps": steps, "warmup": warmup, "collated_src_tgt_matches": n_pts,
+    return {"kind": "phases", "train_precision": train_precision, "fused_norm": bool(fused_norm), "fused_pointwise": bool(fused_pointwise), "device_keypoints": bool(device_keypoints), "points": points, "batch": batch, "steps": steps, "warmup": warmup, "collated_src_tgt_matches": n_pts,
             "keypoints": int(su.shape[1]), "median_ms_per_call": med, "median_ms_per_step": per_step}
 
 
@@ -280,6 +280,7 @@ def main():
     ap.add_argument("--train-precision", default="f32", choices=["f32", "f16"], help="operand precision of the network in the phases lines")
     ap.add_argument("--fused-norm", action="store_true", help="the network of the phases lines with fused_norm=True (include/umereg_bn_act.h)")
     ap.add_argument("--fused-pointwise", action="store_true", help="the point-wise loss of the phases lines on pw_loss.MyInfoNCELossNoSeg")
+    ap.add_argument("--device-keypoints", action="store_true", help="the UME loss of the phases lines with selection=\"device\" (csrc/gt_keypoints_api.h)")
     ap.add_argument("--phases-only", action="store_true", help="skip the match-kernel comparison")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -298,7 +299,7 @@ def main():
             f.write(json.dumps(line) + "\n")
             f.flush()
         for batch in a.batches:
-            line = step_phases(a.points, batch, a.steps, a.warmup, dev, a.train_precision, a.fused_norm, a.fused_pointwise)
+            line = step_phases(a.points, batch, a.steps, a.warmup, dev, a.train_precision, a.fused_norm, a.fused_pointwise, a.device_keypoints)
             print(json.dumps(line), flush=True)
             f.write(json.dumps(line) + "\n")
             f.flush()

@@ -96,7 +96,8 @@ def make_config(name="kitti", yaml_path=None, **overrides):
 class TrainContext:
     """What the reference's train / eval functions read from module globals (train_coloring.py:263-322), made explicit."""
 
-    def __init__(self, args, ume_loss_fn=None, registration_loss_fn=None):
+    def __init__(self, args, ume_loss_fn=None, registration_loss_fn=None, selection="torch"):
+        self.selection = selection      # engine of the keypoint generator, training and validation (gt_keypoints)
         self.device = torch.device(args.device)
         self.use_ume_loss, self.use_reg_loss = bool(args.use_ume_loss), bool(args.use_reg_loss)
         self.pw_loss_weight, self.ume_loss_weight, self.reg_loss_weight = args.pw_loss_weight, args.ume_loss_weight, args.reg_loss_weight
@@ -106,7 +107,7 @@ class TrainContext:
         self.ume_r_nn, self.ume_max_nn, self.ume_min_nn = args.ume_r_nn, args.ume_max_nn, args.ume_min_nn
         # :380-389 (the reference passes no flat_labels: keypoints are drawn from every class)
         self.ume_loss_fn = ume_loss_fn or UMEContrastiveLoss(num_samples=args.ume_n_samples, max_nn=args.ume_max_nn, min_nn=args.ume_min_nn,
-                                                             nn_r=args.ume_r_nn, tau=args.tau_ume, tau_neg=args.tau_ume_neg)
+                                                             nn_r=args.ume_r_nn, tau=args.tau_ume, tau_neg=args.tau_ume_neg).with_selection(selection)
         self.registration_loss_fn = registration_loss_fn or CubeRegistrationLoss(
             rtume_max_nn=args.ume_max_nn, rtume_r_nn=args.ume_r_nn, nn_inter_ratio_thr=args.reg_loss_intersection_thr,
             cube_scale=args.reg_loss_cube_r)
@@ -303,7 +304,7 @@ def eval_one_epoch(epoch, data_loader, model, loss_func, summary_writer, ctx, as
                 tgt_inputs = dict(pts=batch.tgt_pts[valid], seg=[valid], feat=tgt_feat[valid])
                 ratio = calc_inliear_ratio(src_inputs, tgt_inputs, batch.src_pts_tform, batch.gt_tform[valid], ctx.ume_r_nn, ctx.ume_max_nn,
                                            ctx.ume_min_nn, eval_num_kpts=ctx.eval_num_kpts, inlear_thr=ctx.eval_inlear_thr,
-                                           assignment=assignment)
+                                           assignment=assignment, selection=ctx.selection)
                 sums.add(inlier_ratio=ratio.mean())
         if (i + 1) % 10 == 0:
             print(" | ".join(f"{k} {sums.get(k) / (i + 1):.4f}" for k in ("total", "pointwise", "ume", "reg")) +
@@ -434,7 +435,7 @@ def make_loaders(args, synthetic=0, synthetic_points=3000, device_collate=False)
 
 
 def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=None, device_collate=False, device_assignment=False,
-        train_precision="f32", fused_norm=False, conv_mode="union", fused_pointwise=False):
+        train_precision="f32", fused_norm=False, conv_mode="union", fused_pointwise=False, device_keypoints=False):
     """train_coloring.py:263-437 -> the run directory.  Quirks kept: every "best" file stores the validation TOTAL loss; the
     UME and point-wise "best" follow the total (eval_one_epoch returns it three times); without the registration loss the validation
     registration loss is 0.0, so `best_reg_loss` (from inf) is written once, after the first epoch, and `best_mCHR` (from 0.0) never.
@@ -446,7 +447,9 @@ def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=
     parameters and checkpoint keys).
     conv_mode: "union", or "pairs" for the pair-compacted engine of the 27-offset convolutions (models.py; the same values bit for bit).
     fused_pointwise: the point-wise loss is `pw_loss.MyInfoNCELossNoSeg`, the fused HIP forward and backward of csrc/infonce_api.h, in
-    place of the torch statements of `loss.MyInfoNCELossNoSeg` (same constructor and call; values agree to fp32 rounding)."""
+    place of the torch statements of `loss.MyInfoNCELossNoSeg` (same constructor and call; values agree to fp32 rounding).
+    device_keypoints: the ground-truth-driven keypoints of the UME loss and of the validation inlier ratio are selected on the device
+    (`generate_ume_from_keypoints2(..., selection="device")`, csrc/gt_keypoints_api.h; the same keypoints and values bit for bit)."""
     torch.manual_seed(args.random_seed)
     np.random.seed(args.random_seed)
     device = torch.device(args.device)
@@ -461,7 +464,7 @@ def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=
                           fused_norm=fused_norm, conv_mode=conv_mode).to(device)
     pw_class = FusedInfoNCELossNoSeg if fused_pointwise else MyInfoNCELossNoSeg
     point_wise_loss_fn = pw_class(num_samples=args.num_pw_samples, tau=args.tau, neg_euclid_dist=NEG_EUCLID_DIST)
-    ctx = TrainContext(args)
+    ctx = TrainContext(args, selection="device" if device_keypoints else "torch")
     optimizer = optim.Adam(model.parameters(), lr=args.lr, weight_decay=WEIGHT_DECAY)
     start_epoch = resume(args.resume_train_path, model, optimizer, device) if args.resume_train_path != '' else 0
     create_params_dict(args, run_name, out_path, model)
@@ -513,6 +516,8 @@ def main(argv=None):
                         help="engine of the network's 27-offset convolutions, forward and input gradient (pairs: pair-compacted; same values)")
     parser.add_argument('--fused-pointwise', action='store_true',
                         help="run the point-wise InfoNCE loss, forward and backward, on the fused HIP kernels (pw_loss.MyInfoNCELossNoSeg)")
+    parser.add_argument('--device-keypoints', action='store_true',
+                        help="select the UME loss's and the inlier ratio's keypoints on the GPU (lazy density test, one host read; same values)")
     cli = parser.parse_args(argv)
     over = {k: v for k, v in (("cache_data_path", cli.cache), ("num_epochs", cli.epochs), ("batch_size", cli.batch_size),
                               ("output_path", cli.output_path), ("resume_train_path", cli.resume)) if v is not None}
@@ -524,7 +529,7 @@ def main(argv=None):
     print(f"Train {args.dataset} config: {cli.config_path or 'built-in defaults'}")
     out = run(args, synthetic=cli.synthetic, synthetic_points=cli.synthetic_points, device_collate=cli.device_collate,
               device_assignment=cli.device_assignment, train_precision=cli.train_precision, fused_norm=cli.fused_norm,
-              conv_mode=cli.conv_mode, fused_pointwise=cli.fused_pointwise)
+              conv_mode=cli.conv_mode, fused_pointwise=cli.fused_pointwise, device_keypoints=cli.device_keypoints)
     print(f"run directory: {out}")
     return out
 

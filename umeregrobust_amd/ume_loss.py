@@ -15,7 +15,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import ops, ume_grad
+from . import gt_keypoints, ops, ume_grad
 from .utils.loc_utils import generate_ume_from_keypoints2
 
 
@@ -27,6 +27,7 @@ class UMEContrastiveLoss(nn.Module):
     def __init__(self, num_samples=1024, max_nn=5000, min_nn=1000, nn_r=10, tau=0.1, tau_neg=0.1, hd_labels_flag=False,
                  flat_labels=[], nn_intersection_r=0.6, svd_thr=1e-5):
         super().__init__()
+        self.selection = "torch"        # the keypoint generator's engine; `with_selection` changes it (the constructor is the reference's)
         self.n_samples = num_samples
         self.max_nn = max_nn
         self.min_nn = min_nn
@@ -38,6 +39,13 @@ class UMEContrastiveLoss(nn.Module):
         self.nn_intersection_r = nn_intersection_r
         self.svd_thr = svd_thr
 
+    def with_selection(self, selection):
+        """selection="torch" | "device": the engine of generate_ume_from_keypoints2 (same keypoints and values either way); -> self.
+        Anything else is a ValueError.  Not a constructor argument: the constructor's signature stays the reference's."""
+        gt_keypoints.check_selection("UMEContrastiveLoss", selection)
+        self.selection = selection
+        return self
+
     def forward(self, velo_pts, velo_seg, velo_feat, ref_pts, ref_feat, gt_tform):
         for t in (velo_pts, velo_seg, velo_feat, ref_pts, ref_feat, gt_tform):
             if t.device.type != "cuda":
@@ -47,7 +55,7 @@ class UMEContrastiveLoss(nn.Module):
                 generate_ume_from_keypoints2(velo_pts, velo_seg, velo_feat.detach(), ref_pts, ref_feat.detach(), gt_tform,
                                              num_samples=self.n_samples, max_nn=self.max_nn, min_nn=self.min_nn, nn_r=self.nn_r,
                                              flat_labels=self.flat_labels, normalized_ume=True,
-                                             nn_intersection_r=self.nn_intersection_r)
+                                             nn_intersection_r=self.nn_intersection_r, selection=self.selection)
             # valid UME matrices (loss.py:83-97): all four singular values above the threshold, in both clouds
             valid = ((ops.ume_svdvals(F_velo) > self.svd_thr).sum(dim=-1) == 4) & ((ops.ume_svdvals(F_ref) > self.svd_thr).sum(dim=-1) == 4)
             invalid_keypoints_velo = torch.zeros_like(F_velo[0, :, 0, 0]).bool()

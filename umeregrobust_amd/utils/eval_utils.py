@@ -12,18 +12,22 @@ def relative_rotation_error(R, R_hat):
 
 
 def calc_inliear_ratio(src_inputs, tgt_inputs, src_pts_tform, gt_tform, ume_r_nn, ume_max_nn, ume_min_nn, eval_num_kpts,
-                       keypoints_ignore_segments=[], inlear_thr=0.6, nn_inter_thr=0.6, svd_thr=1e-5, assignment="host"):
+                       keypoints_ignore_segments=[], inlear_thr=0.6, nn_inter_thr=0.6, svd_thr=1e-5, assignment="host",
+                       selection="torch"):
     """reference utils/eval_utils.py:8-57: inlier ratio of the UME descriptor matching between ground-truth-driven keypoints.
     src_inputs / tgt_inputs: dicts with 'pts', 'seg', 'feat'.  assignment: "host" = the Hungarian matching on the host with
-    scipy, like the reference; "device" = ops.linear_sum_assignment, the distance matrices never leave the GPU."""
+    scipy, like the reference; "device" = ops.linear_sum_assignment, the distance matrices never leave the GPU.  selection: "torch" or
+    "device", the engine of generate_ume_from_keypoints2 (same keypoints either way)."""
     if assignment not in ("host", "device"):
         raise ValueError(f"calc_inliear_ratio: assignment must be 'host' or 'device', got {assignment!r}")
+    from ..gt_keypoints import check_selection
+    check_selection("calc_inliear_ratio", selection)
     from .loc_utils import generate_ume_from_keypoints2, ume_cdist
     opts = dict(nn_r=ume_r_nn, max_nn=ume_max_nn, min_nn=ume_min_nn, num_samples=eval_num_kpts,
                 flat_labels=keypoints_ignore_segments, nn_intersection_r=nn_inter_thr)
     F_src, F_tgt, kp_src, kp_tgt, _, _ = generate_ume_from_keypoints2(
         src_inputs['pts'], src_inputs['seg'], src_inputs['feat'], tgt_inputs['pts'], tgt_inputs['feat'], gt_tform,
-        **opts)
+        selection=selection, **opts)
 
     # :30-38 - a keypoint column survives only if both of its moment matrices have rank 4 in every batch entry
     # (the reference indexes the keep-mask by column only, so one bad entry removes the column everywhere).

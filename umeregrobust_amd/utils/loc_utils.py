@@ -9,7 +9,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import gt_keypoints, ops
 from ..ops import ball_query, knn_points  # noqa: F401  (re-exports of the pytorch3d replacements)
 
 
@@ -32,7 +32,7 @@ def batch_estimate_transform_ume_old(G, H):
 
 def generate_ume_from_keypoints2(velo_pts, velo_seg, velo_feat, ref_pts, ref_feat, gt_tform,
                                  nn_r=10, max_nn=5000, min_nn=1000, num_samples=1024, flat_labels=[9],
-                                 normalized_ume=False, nn_intersection_r=0.6):
+                                 normalized_ume=False, nn_intersection_r=0.6, selection="torch"):
     """reference utils/loc_utils.py:86-188.  Ground-truth-driven keypoints: source points that are not of a
     flat class (:93), overlap the target under gt_tform (:96-101) and have >= min_nn neighbours within nn_r
     (:111-126) -- the first `num_samples` of them in the reference's (descending-index) order -- with the
@@ -42,7 +42,15 @@ def generate_ume_from_keypoints2(velo_pts, velo_seg, velo_feat, ref_pts, ref_fea
     Same outputs as the reference; the [bs,N,max_nn,3] neighbour tensor it builds for EVERY candidate (:113-116)
     is replaced by the fused count + moment kernel, neighbour lists are only formed for the selected keypoints.
     Limits of the native search: max_nn <= 7680 (the reference default 5000 is inside; above it the C ABI returns
-    UMEREG_EINVAL, raised here as RuntimeError)."""
+    UMEREG_EINVAL, raised here as RuntimeError).
+
+    selection: "torch" (default) -- the statements below; "device" -- the same six outputs, bit for bit, with the candidate list, the
+    density test and the ordered pick on the HIP kernels of gt_keypoints (no moment matrix of a candidate that is not selected, no sort,
+    one device-to-host read per call instead of four).  Anything else is a ValueError before a tensor is touched."""
+    gt_keypoints.check_selection("generate_ume_from_keypoints2", selection)
+    if selection == "device":
+        return gt_keypoints.generate(velo_pts, velo_seg, velo_feat, ref_pts, ref_feat, gt_tform, nn_r, max_nn, min_nn, num_samples,
+                                     flat_labels, normalized_ume, nn_intersection_r)
     bs, velo_pc_size, dim_size = velo_feat.shape
     dev = velo_pts.device
     non_floor_mask = (velo_seg != torch.tensor(flat_labels, device=velo_seg.device)).all(dim=-1).flatten(1)     # :93
