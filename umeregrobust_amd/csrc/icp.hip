@@ -17,12 +17,26 @@
 //                    sum |p'-q|^2} per workgroup (fixed reduction order => deterministic);
 //   icp_step_kernel  one workgroup: totals, convergence test, 3x3 polar rotation, T <- update * T.
 // Once `done` is set the remaining queued launches return immediately.
+//
+// Point to plane (opt-in, icp_plane_api.h; open3d's TransformationEstimationPointToPlane): the same loop, search and stop rule -- the
+// kernels are templates with one search body and two accumulations.  With n_q the normal of the matched target point (looked up by the
+// ORIGINAL index the packed table carries in .w), r = (p' - q) . n_q and J = [p' x n_q, n_q], the evaluation sums {n, sum |p'-q|^2,
+// the 21 upper entries of sum J J^T, the 6 of sum J r} (29 instead of 17, the same reduction tree) and the step solves
+// (sum J J^T) x = -(sum J r) through a 6x6 Jacobi eigen-decomposition (icp_plane_math.h: eigenvalues <= 1e-12 lambda_max count as
+// zero; open3d uses Eigen's LDLT, the two differ on rank-deficient systems only), update = [Rz(x2) Ry(x1) Rx(x0) | x3..5].
 #include "grid.h"
+#include "icp_plane_api.h"
+#include "icp_plane_math.h"
 #include "polar.h"
 
 namespace umereg {
 
-constexpr int kIcpSums = 17;   // n, p'(3), q(3), q p'^T (9), e2
+// point to point: n, p'(3), q(3), q p'^T (9), e2;  point to plane: n, e2, J J^T upper (21), J r (6)
+template <bool kPlane>
+struct IcpSums {
+    static constexpr int kCount = kPlane ? 29 : 17;
+    static constexpr int kE2 = kPlane ? 1 : 16;
+};
 constexpr int kIcpWG = 256;
 
 struct IcpState {
@@ -45,10 +59,13 @@ struct IcpState {
 constexpr int kIcpLanes = 8;
 constexpr int kIcpThreads = 256;
 constexpr int kIcpBlock = 64;
+template <bool kPlane>
 __global__ __launch_bounds__(kIcpThreads) void icp_eval_kernel(const float* __restrict__ src, int n_src,
                                                                const char* __restrict__ ws, int n_tgt, float max_dist,
-                                                               const IcpState* __restrict__ state, double* __restrict__ partial)
+                                                               const IcpState* __restrict__ state, double* __restrict__ partial,
+                                                               const float* __restrict__ normals)
 {
+    constexpr int kIcpSums = IcpSums<kPlane>::kCount;
     __shared__ double red[kIcpThreads / kWave][kIcpSums];
     if (state->done) return;
     const GridWs w = grid_ws(n_tgt);
@@ -105,13 +122,32 @@ __global__ __launch_bounds__(kIcpThreads) void icp_eval_kernel(const float* __re
         if (live && sub == 0 && m != ~0ull && bd2 < max_dist * max_dist) {
             const double tx = bx, ty = by, tz = bz;
             const double ex = qx - tx, ey = qy - ty, ez = qz - tz;
-            s[0] += 1.0;
-            s[1] += qx; s[2] += qy; s[3] += qz;
-            s[4] += tx; s[5] += ty; s[6] += tz;
-            s[7] += tx * qx;  s[8] += tx * qy;  s[9] += tx * qz;
-            s[10] += ty * qx; s[11] += ty * qy; s[12] += ty * qz;
-            s[13] += tz * qx; s[14] += tz * qy; s[15] += tz * qz;
-            s[16] += ex * ex + ey * ey + ez * ez;
+            if constexpr (!kPlane) {
+                s[0] += 1.0;
+                s[1] += qx; s[2] += qy; s[3] += qz;
+                s[4] += tx; s[5] += ty; s[6] += tz;
+                s[7] += tx * qx;  s[8] += tx * qy;  s[9] += tx * qz;
+                s[10] += ty * qx; s[11] += ty * qy; s[12] += ty * qz;
+                s[13] += tz * qx; s[14] += tz * qy; s[15] += tz * qz;
+                s[16] += ex * ex + ey * ey + ez * ez;
+            } else {
+                // the matched point's normal, by the original index the key carries (a real point: its distance passed the cut)
+                const unsigned int oi = (unsigned int)(m & 0xffffffffull);
+                if (oi < (unsigned int)n_tgt) {
+                    const double nx = normals[3 * (size_t)oi + 0], ny = normals[3 * (size_t)oi + 1], nz = normals[3 * (size_t)oi + 2];
+                    const double r = ex * nx + ey * ny + ez * nz;
+                    const double J[6] = {qy * nz - qz * ny, qz * nx - qx * nz, qx * ny - qy * nx, nx, ny, nz};
+                    s[0] += 1.0;
+                    s[1] += ex * ex + ey * ey + ez * ez;
+                    int k = 2;
+#pragma unroll
+                    for (int a = 0; a < 6; ++a)
+#pragma unroll
+                        for (int b = a; b < 6; ++b) s[k++] += J[a] * J[b];
+#pragma unroll
+                    for (int a = 0; a < 6; ++a) s[23 + a] += J[a] * r;
+                }
+            }
         }
     }
 #pragma unroll
@@ -129,10 +165,12 @@ __global__ __launch_bounds__(kIcpThreads) void icp_eval_kernel(const float* __re
     }
 }
 
+template <bool kPlane>
 __global__ __launch_bounds__(kIcpWG) void icp_step_kernel(const double* __restrict__ partial, int n_blocks, int n_src,
                                                            int max_iter, double rel_fitness, double rel_rmse,
                                                            IcpState* __restrict__ state)
 {
+    constexpr int kIcpSums = IcpSums<kPlane>::kCount;
     __shared__ double tot[kIcpSums];
     __shared__ double red[kIcpWG / kWave][kIcpSums];
     if (state->done) return;
@@ -161,7 +199,7 @@ __global__ __launch_bounds__(kIcpWG) void icp_step_kernel(const double* __restri
     if (threadIdx.x != 0) return;
     const double n = tot[0];
     const double fitness = n / (double)n_src;
-    const double rmse = n > 0.0 ? sqrt(tot[16] / n) : 0.0;
+    const double rmse = n > 0.0 ? sqrt(tot[IcpSums<kPlane>::kE2] / n) : 0.0;
     state->fitness = fitness;
     state->rmse = rmse;
     if (state->have_prev && fabs(state->prev_fitness - fitness) < rel_fitness && fabs(state->prev_rmse - rmse) < rel_rmse) {
@@ -172,19 +210,31 @@ __global__ __launch_bounds__(kIcpWG) void icp_step_kernel(const double* __restri
         state->done = 1;
         return;
     }
-    // update = umeyama(p' -> q) without scaling; no correspondences: identity (open3d returns I)
+    // update = umeyama(p' -> q) without scaling (point to plane: the solve of the normal equations); no correspondences:
+    // identity (open3d returns I)
     if (n > 0.0) {
-        const double mp[3] = {tot[1] / n, tot[2] / n, tot[3] / n};
-        const double mq[3] = {tot[4] / n, tot[5] / n, tot[6] / n};
-        double A[3][3], R[3][3];
+        double R[3][3], t[3];
+        if constexpr (!kPlane) {
+            const double mp[3] = {tot[1] / n, tot[2] / n, tot[3] / n};
+            const double mq[3] = {tot[4] / n, tot[5] / n, tot[6] / n};
+            double A[3][3];
 #pragma unroll
-        for (int a = 0; a < 3; ++a)
+            for (int a = 0; a < 3; ++a)
 #pragma unroll
-            for (int b = 0; b < 3; ++b) A[a][b] = tot[7 + 3 * a + b] / n - mq[a] * mp[b];
-        polar_rotation(A, R);
-        const double t[3] = {mq[0] - (R[0][0] * mp[0] + R[0][1] * mp[1] + R[0][2] * mp[2]),
-                             mq[1] - (R[1][0] * mp[0] + R[1][1] * mp[1] + R[1][2] * mp[2]),
-                             mq[2] - (R[2][0] * mp[0] + R[2][1] * mp[1] + R[2][2] * mp[2])};
+                for (int b = 0; b < 3; ++b) A[a][b] = tot[7 + 3 * a + b] / n - mq[a] * mp[b];
+            polar_rotation(A, R);
+            t[0] = mq[0] - (R[0][0] * mp[0] + R[0][1] * mp[1] + R[0][2] * mp[2]);
+            t[1] = mq[1] - (R[1][0] * mp[0] + R[1][1] * mp[1] + R[1][2] * mp[2]);
+            t[2] = mq[2] - (R[2][0] * mp[0] + R[2][1] * mp[1] + R[2][2] * mp[2]);
+        } else {
+            double au[21], b[6], x[6];
+#pragma unroll
+            for (int k = 0; k < 21; ++k) au[k] = tot[2 + k];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) b[k] = tot[23 + k];
+            plane_solve(au, b, x);
+            euler_update(x, R, t);
+        }
         double Tn[16];
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -227,11 +277,18 @@ __global__ void icp_init_dev_kernel(IcpState* __restrict__ state, const float* _
     }
 }
 
-static size_t icp_extra_bytes(int n_src)
+static size_t icp_extra_bytes(int n_src, int sums)
 {
     const size_t n_blocks = ((size_t)n_src + kIcpBlock - 1) / kIcpBlock;
-    return align_up(sizeof(IcpState), 256) + align_up(n_blocks * kIcpSums * sizeof(double), 256);
+    return align_up(sizeof(IcpState), 256) + align_up(n_blocks * sums * sizeof(double), 256);
 }
+
+// which estimation a host call runs: point to point (normals == nullptr) or point to plane, and the name its errors carry
+struct IcpMode {
+    const float* normals;
+    const char* who;
+};
+constexpr IcpMode kIcpPointToPoint = {nullptr, "icp_point_to_point"};
 
 }  // namespace umereg
 
@@ -240,16 +297,22 @@ using namespace umereg;
 UMEREG_API size_t umereg_icp_workspace_bytes(int n_src, int n_tgt)
 {
     if (n_src <= 0 || n_tgt <= 0) return 0;
-    return grid_ws(n_tgt).total + icp_extra_bytes(n_src);
+    return grid_ws(n_tgt).total + icp_extra_bytes(n_src, IcpSums<false>::kCount);
+}
+
+UMEREG_API size_t umereg_icp_plane_workspace_bytes(int n_src, int n_tgt)
+{
+    if (n_src <= 0 || n_tgt <= 0) return 0;
+    return grid_ws(n_tgt).total + icp_extra_bytes(n_src, IcpSums<true>::kCount);
 }
 
 // src f32 [n_src,3], tgt f32 [n_tgt,3] (device); T_init / T_out: HOST double [16] row major; fitness,
 // inlier_rmse, iterations: HOST outputs (may be NULL).  Synchronous with respect to `stream`: the loop's stop
 // test lives on the device, the host polls it once per batch of iterations (4, then 8 at a time).
-static int icp_run(const float* src, const float* tgt, int n_src, int n_tgt, const double* T_init_host, const float* T_init_dev,
-                   float max_correspondence_distance, int max_iteration, double relative_fitness, double relative_rmse,
-                   double* T_out_host, double* fitness_host, double* inlier_rmse_host, int* iterations_host, void* workspace,
-                   size_t workspace_bytes, void* stream);
+static int icp_run(const IcpMode& mode, const float* src, const float* tgt, int n_src, int n_tgt, const double* T_init_host,
+                   const float* T_init_dev, float max_correspondence_distance, int max_iteration, double relative_fitness,
+                   double relative_rmse, double* T_out_host, double* fitness_host, double* inlier_rmse_host, int* iterations_host,
+                   void* workspace, size_t workspace_bytes, void* stream);
 
 UMEREG_API int umereg_icp_point_to_point_f32(const float* src, const float* tgt, int n_src, int n_tgt,
                                              const double* T_init_host, float max_correspondence_distance,
@@ -258,7 +321,7 @@ UMEREG_API int umereg_icp_point_to_point_f32(const float* src, const float* tgt,
                                              int* iterations_host, void* workspace, size_t workspace_bytes, void* stream)
 {
     UMEREG_REQUIRE(T_init_host, "icp_point_to_point: null T_init");
-    return icp_run(src, tgt, n_src, n_tgt, T_init_host, nullptr, max_correspondence_distance, max_iteration, relative_fitness, relative_rmse,
+    return icp_run(kIcpPointToPoint, src, tgt, n_src, n_tgt, T_init_host, nullptr, max_correspondence_distance, max_iteration, relative_fitness, relative_rmse,
                    T_out_host, fitness_host, inlier_rmse_host, iterations_host, workspace, workspace_bytes, stream);
 }
 
@@ -269,21 +332,22 @@ UMEREG_API int umereg_icp_point_to_point_dev_f32(const float* src, const float* 
                                                  int* iterations_host, void* workspace, size_t workspace_bytes, void* stream)
 {
     UMEREG_REQUIRE(T_init_dev, "icp_point_to_point_dev: null T_init");
-    return icp_run(src, tgt, n_src, n_tgt, nullptr, T_init_dev, max_correspondence_distance, max_iteration, relative_fitness, relative_rmse,
+    return icp_run(kIcpPointToPoint, src, tgt, n_src, n_tgt, nullptr, T_init_dev, max_correspondence_distance, max_iteration, relative_fitness, relative_rmse,
                    T_out_host, fitness_host, inlier_rmse_host, iterations_host, workspace, workspace_bytes, stream);
 }
 
 // enqueue only: [first: the target's grid, the initial state] + `iterations` evaluation / update pairs; nothing is waited for
-static int icp_enqueue(const float* src, const float* tgt, int n_src, int n_tgt, const double* T_init_host, const float* T_init_dev,
-                       float max_correspondence_distance, int max_iteration, double relative_fitness, double relative_rmse,
-                       bool first, int iterations, void* workspace, size_t workspace_bytes, hipStream_t st, IcpState** state_out)
+static int icp_enqueue(const IcpMode& mode, const float* src, const float* tgt, int n_src, int n_tgt, const double* T_init_host,
+                       const float* T_init_dev, float max_correspondence_distance, int max_iteration, double relative_fitness,
+                       double relative_rmse, bool first, int iterations, void* workspace, size_t workspace_bytes, hipStream_t st,
+                       IcpState** state_out)
 {
-    UMEREG_REQUIRE(src && tgt, "icp_point_to_point: null pointer");
-    UMEREG_REQUIRE(n_src > 0 && n_tgt > 0, "icp_point_to_point: empty cloud (n_src %d, n_tgt %d)", n_src, n_tgt);
-    UMEREG_REQUIRE(max_correspondence_distance > 0.f && max_iteration >= 0 && iterations >= 0, "icp_point_to_point: bad distance / iteration limit");
+    UMEREG_REQUIRE(src && tgt, "%s: null pointer", mode.who);
+    UMEREG_REQUIRE(n_src > 0 && n_tgt > 0, "%s: empty cloud (n_src %d, n_tgt %d)", mode.who, n_src, n_tgt);
+    UMEREG_REQUIRE(max_correspondence_distance > 0.f && max_iteration >= 0 && iterations >= 0, "%s: bad distance / iteration limit", mode.who);
     if (int rc = check_device()) return rc;
-    const size_t need = umereg_icp_workspace_bytes(n_src, n_tgt);
-    UMEREG_REQUIRE_WORKSPACE("icp_point_to_point", workspace, workspace_bytes, need);
+    const size_t need = mode.normals ? umereg_icp_plane_workspace_bytes(n_src, n_tgt) : umereg_icp_workspace_bytes(n_src, n_tgt);
+    UMEREG_REQUIRE_WORKSPACE(mode.who, workspace, workspace_bytes, need);
     char* ws = (char*)workspace;
     const GridWs w = grid_ws(n_tgt);
     IcpState* state = (IcpState*)(ws + w.total);
@@ -294,7 +358,7 @@ static int icp_enqueue(const float* src, const float* tgt, int n_src, int n_tgt,
             hipLaunchKernelGGL(icp_init_dev_kernel, dim3(1), dim3(64), 0, st, state, T_init_dev);
             UMEREG_CHECK_LAUNCH("icp_init_dev_kernel");
         } else {
-            UMEREG_REQUIRE(T_init_host, "icp_point_to_point: null T_init");
+            UMEREG_REQUIRE(T_init_host, "%s: null T_init", mode.who);
             IcpInit init;
             for (int k = 0; k < 16; ++k) init.T[k] = T_init_host[k];
             hipLaunchKernelGGL(icp_init_kernel, dim3(1), dim3(64), 0, st, state, init);
@@ -303,22 +367,29 @@ static int icp_enqueue(const float* src, const float* tgt, int n_src, int n_tgt,
     }
     const int n_blocks = (n_src + kIcpBlock - 1) / kIcpBlock;
     for (int b = 0; b < iterations; ++b) {
-        hipLaunchKernelGGL(icp_eval_kernel, dim3(n_blocks), dim3(kIcpThreads), 0, st, src, n_src, ws, n_tgt,
-                           max_correspondence_distance, state, partial);
-        hipLaunchKernelGGL(icp_step_kernel, dim3(1), dim3(kIcpWG), 0, st, partial, n_blocks, n_src, max_iteration,
-                           relative_fitness, relative_rmse, state);
+        if (mode.normals) {
+            hipLaunchKernelGGL(icp_eval_kernel<true>, dim3(n_blocks), dim3(kIcpThreads), 0, st, src, n_src, ws, n_tgt,
+                               max_correspondence_distance, state, partial, mode.normals);
+            hipLaunchKernelGGL(icp_step_kernel<true>, dim3(1), dim3(kIcpWG), 0, st, partial, n_blocks, n_src, max_iteration,
+                               relative_fitness, relative_rmse, state);
+        } else {
+            hipLaunchKernelGGL(icp_eval_kernel<false>, dim3(n_blocks), dim3(kIcpThreads), 0, st, src, n_src, ws, n_tgt,
+                               max_correspondence_distance, state, partial, (const float*)nullptr);
+            hipLaunchKernelGGL(icp_step_kernel<false>, dim3(1), dim3(kIcpWG), 0, st, partial, n_blocks, n_src, max_iteration,
+                               relative_fitness, relative_rmse, state);
+        }
     }
     if (iterations) UMEREG_CHECK_LAUNCH("icp kernels");
     *state_out = state;
     return UMEREG_OK;
 }
 
-static int icp_run(const float* src, const float* tgt, int n_src, int n_tgt, const double* T_init_host, const float* T_init_dev,
-                   float max_correspondence_distance, int max_iteration, double relative_fitness, double relative_rmse,
-                   double* T_out_host, double* fitness_host, double* inlier_rmse_host, int* iterations_host, void* workspace,
-                   size_t workspace_bytes, void* stream)
+static int icp_run(const IcpMode& mode, const float* src, const float* tgt, int n_src, int n_tgt, const double* T_init_host,
+                   const float* T_init_dev, float max_correspondence_distance, int max_iteration, double relative_fitness,
+                   double relative_rmse, double* T_out_host, double* fitness_host, double* inlier_rmse_host, int* iterations_host,
+                   void* workspace, size_t workspace_bytes, void* stream)
 {
-    UMEREG_REQUIRE(T_out_host, "icp_point_to_point: null pointer");
+    UMEREG_REQUIRE(T_out_host, "%s: null pointer", mode.who);
     hipStream_t st = (hipStream_t)stream;
     IcpState h;
     memset(&h, 0, sizeof(h));
@@ -328,13 +399,13 @@ static int icp_run(const float* src, const float* tgt, int n_src, int n_tgt, con
         // iteration enqueued beyond the stop is a pair of launches that only finds the flag set
         const int batch = launched == 0 ? 4 : 8;
         IcpState* state = nullptr;
-        if (int rc = icp_enqueue(src, tgt, n_src, n_tgt, T_init_host, T_init_dev, max_correspondence_distance, max_iteration, relative_fitness,
-                                 relative_rmse, launched == 0, batch, workspace, workspace_bytes, st, &state))
+        if (int rc = icp_enqueue(mode, src, tgt, n_src, n_tgt, T_init_host, T_init_dev, max_correspondence_distance, max_iteration,
+                                 relative_fitness, relative_rmse, launched == 0, batch, workspace, workspace_bytes, st, &state))
             return rc;
         launched += batch;
         if (hipMemcpyAsync(&h, state, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess) {
-            set_error("icp_point_to_point: state download failed");
+            set_error("%s: state download failed", mode.who);
             return UMEREG_ELAUNCH;
         }
         if (h.done || launched > max_iteration + 1) break;
@@ -357,11 +428,59 @@ UMEREG_API int umereg_icp_enqueue_f32(const float* src, const float* tgt, int n_
     UMEREG_REQUIRE(!first || T_init_dev, "icp_enqueue: null T_init");
     hipStream_t st = (hipStream_t)stream;
     IcpState* state = nullptr;
-    if (int rc = icp_enqueue(src, tgt, n_src, n_tgt, nullptr, T_init_dev, max_correspondence_distance, max_iteration, relative_fitness,
-                             relative_rmse, first != 0, iterations, workspace, workspace_bytes, st, &state))
+    if (int rc = icp_enqueue(kIcpPointToPoint, src, tgt, n_src, n_tgt, nullptr, T_init_dev, max_correspondence_distance, max_iteration,
+                             relative_fitness, relative_rmse, first != 0, iterations, workspace, workspace_bytes, st, &state))
         return rc;
     if (hipMemcpyAsync(state_host, state, sizeof(IcpState), hipMemcpyDeviceToHost, st) != hipSuccess) {
         set_error("icp_enqueue: state download failed");
+        return UMEREG_ELAUNCH;
+    }
+    return UMEREG_OK;
+}
+
+// ---- point to plane: the same host paths with the target's normals (icp_plane_api.h) ---------------------------------------
+UMEREG_API int umereg_icp_point_to_plane_f32(const float* src, const float* tgt, const float* tgt_normals, int n_src, int n_tgt,
+                                             const double* T_init_host, float max_correspondence_distance, int max_iteration,
+                                             double relative_fitness, double relative_rmse, double* T_out_host, double* fitness_host,
+                                             double* inlier_rmse_host, int* iterations_host, void* workspace, size_t workspace_bytes,
+                                             void* stream)
+{
+    UMEREG_REQUIRE(tgt_normals, "icp_point_to_plane: null normals");
+    UMEREG_REQUIRE(T_init_host, "icp_point_to_plane: null T_init");
+    const IcpMode mode = {tgt_normals, "icp_point_to_plane"};
+    return icp_run(mode, src, tgt, n_src, n_tgt, T_init_host, nullptr, max_correspondence_distance, max_iteration, relative_fitness,
+                   relative_rmse, T_out_host, fitness_host, inlier_rmse_host, iterations_host, workspace, workspace_bytes, stream);
+}
+
+UMEREG_API int umereg_icp_point_to_plane_dev_f32(const float* src, const float* tgt, const float* tgt_normals, int n_src, int n_tgt,
+                                                 const float* T_init_dev, float max_correspondence_distance, int max_iteration,
+                                                 double relative_fitness, double relative_rmse, double* T_out_host,
+                                                 double* fitness_host, double* inlier_rmse_host, int* iterations_host, void* workspace,
+                                                 size_t workspace_bytes, void* stream)
+{
+    UMEREG_REQUIRE(tgt_normals, "icp_point_to_plane_dev: null normals");
+    UMEREG_REQUIRE(T_init_dev, "icp_point_to_plane_dev: null T_init");
+    const IcpMode mode = {tgt_normals, "icp_point_to_plane"};
+    return icp_run(mode, src, tgt, n_src, n_tgt, nullptr, T_init_dev, max_correspondence_distance, max_iteration, relative_fitness,
+                   relative_rmse, T_out_host, fitness_host, inlier_rmse_host, iterations_host, workspace, workspace_bytes, stream);
+}
+
+UMEREG_API int umereg_icp_plane_enqueue_f32(const float* src, const float* tgt, const float* tgt_normals, int n_src, int n_tgt,
+                                            const float* T_init_dev, float max_correspondence_distance, int max_iteration,
+                                            double relative_fitness, double relative_rmse, int first, int iterations, void* state_host,
+                                            void* workspace, size_t workspace_bytes, void* stream)
+{
+    UMEREG_REQUIRE(state_host, "icp_plane_enqueue: null state_host");
+    UMEREG_REQUIRE(tgt_normals, "icp_plane_enqueue: null normals");
+    UMEREG_REQUIRE(!first || T_init_dev, "icp_plane_enqueue: null T_init");
+    hipStream_t st = (hipStream_t)stream;
+    IcpState* state = nullptr;
+    const IcpMode mode = {tgt_normals, "icp_point_to_plane"};
+    if (int rc = icp_enqueue(mode, src, tgt, n_src, n_tgt, nullptr, T_init_dev, max_correspondence_distance, max_iteration,
+                             relative_fitness, relative_rmse, first != 0, iterations, workspace, workspace_bytes, st, &state))
+        return rc;
+    if (hipMemcpyAsync(state_host, state, sizeof(IcpState), hipMemcpyDeviceToHost, st) != hipSuccess) {
+        set_error("icp_plane_enqueue: state download failed");
         return UMEREG_ELAUNCH;
     }
     return UMEREG_OK;

@@ -8,7 +8,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import ops, streams as _streams
+from . import icp_plane, ops, streams as _streams
 from .host_rng import choice_uniform_noreplace
 from .pipeline import (PairBatch, PairResult, RegistrationPipeline, _draw_keypoints, _draw_keypoints_host, _index_tensor,  # noqa: F401
                        _phase_a, _phase_b, _PinnedRing, _ring, _to_host, phase_a_route, register_pair)
@@ -120,9 +120,12 @@ def select_hypothesis(src_pts_raw, tgt_pts_raw, src_pts, tgt_pts, src_feat, tgt_
                    corr_sigma=args.corr_kernel_sigma, args=args, timing=timing, return_tform=return_tform)
 
 
-def refine_registration(R_hat, t_hat, args, pairs, tform_dev=None):
+def refine_registration(R_hat, t_hat, args, pairs, tform_dev=None, estimation=None):
     """reference evaluate.py:63-109 (`refine_registration`): point-to-point ICP from every selected (R_hat, t_hat),
     max correspondence distance 0.2 m, max_iteration=200, then RRE / RTE against the ground truth.
+    estimation (default: args.icp_estimation, else "point_to_point", the reference's): "point_to_plane" refines with
+    ops.icp_point_to_plane on the target's normals (ops.estimate_normals with args.icp_normal_knn = 30 neighbours and
+    args.icp_normal_radius = None), computed once per target cloud.
     The reference re-opens its dataset here; this takes the raw clouds instead:
     pairs = iterable of (src_pts_raw [n,3], tgt_pts_raw [m,3], gt_tform [4,4]).
     tform_dev: optional [P,4,4] float32 DEVICE tensor holding the same (R_hat, t_hat) as 4 x 4 transforms: the ICP then starts from
@@ -131,6 +134,7 @@ def refine_registration(R_hat, t_hat, args, pairs, tform_dev=None):
     T_est_arr, rre_arr, rte_arr = [], [], []
     max_corr = float(getattr(args, "icp_max_correspondence_distance", 0.2))
     max_it = int(getattr(args, "icp_max_iteration", 200))
+    estimation, normal_knn, normal_radius = icp_plane.estimation_of(args, estimation)
     for itr, (src_pts_raw, tgt_pts_raw, gt_tform) in enumerate(pairs):
         if tform_dev is not None:
             tform_hat = tform_dev[itr].contiguous()
@@ -139,7 +143,11 @@ def refine_registration(R_hat, t_hat, args, pairs, tform_dev=None):
             tform_hat[:3, :3] = np.asarray(R_hat[itr].detach().cpu() if isinstance(R_hat[itr], torch.Tensor) else R_hat[itr])
             tform_hat[:3, 3] = np.asarray(t_hat[itr].detach().cpu() if isinstance(t_hat[itr], torch.Tensor) else t_hat[itr])
             tform_hat[3, 3] = 1
-        reg = ops.icp_point_to_point(src_pts_raw, tgt_pts_raw, tform_hat, max_corr, max_it)
+        if estimation == "point_to_plane":
+            normals = ops.estimate_normals(tgt_pts_raw, normal_knn, normal_radius)
+            reg = ops.icp_point_to_plane(src_pts_raw, tgt_pts_raw, normals, tform_hat, max_corr, max_it)
+        else:
+            reg = ops.icp_point_to_point(src_pts_raw, tgt_pts_raw, tform_hat, max_corr, max_it)
         new_tform = torch.from_numpy(reg.transformation).float()
         T_est_arr.append(new_tform)
         gt = gt_tform.detach().cpu().float() if isinstance(gt_tform, torch.Tensor) else torch.as_tensor(gt_tform).float()
@@ -186,6 +194,7 @@ def evaluate_pairs(pairs, args, rng=np.random, refine=True, verbose=False, overl
     refined = []      # per pair: T_est [4,4] (host) when the ICP runs inside the loop
     max_corr = float(getattr(args, "icp_max_correspondence_distance", 0.2))
     max_it = int(getattr(args, "icp_max_iteration", 200))
+    estimation, normal_knn, normal_radius = icp_plane.estimation_of(args)
 
     def read_back(p):
         R_hat, t_hat, st, _keep, T_dev, job, clouds = p     # _keep: the pair's input tensors stay alive until its last kernel is done
@@ -233,7 +242,10 @@ def evaluate_pairs(pairs, args, rng=np.random, refine=True, verbose=False, overl
                                     prob=cl(out.prob), ume_src=cl(out.ume_src), ume_tgt=cl(out.ume_tgt), T_sel=T_dev[0].clone()))
             job = None
             if refine and st is not None and src_raw.is_cuda and src_raw.dtype == torch.float32 and tgt_raw.dtype == torch.float32:
-                job = ops.IcpJob(src_raw, tgt_raw, T_dev[0].contiguous(), max_corr, max_it)                              # :63-96
+                # (point to plane: the target's normals, once per target cloud, on the pair's stream behind the selection like the
+                # chain itself -- opting in adds no host read)
+                normals = ops.estimate_normals(tgt_raw, normal_knn, normal_radius) if estimation == "point_to_plane" else None
+                job = ops.IcpJob(src_raw, tgt_raw, T_dev[0].contiguous(), max_corr, max_it, tgt_normals=normals)          # :63-96
         raw.append(pair["gt_tform"])
         if pending is not None:
             read_back(pending)        # the previous pair's result: its scores ran beside everything above
@@ -357,9 +369,17 @@ def main(argv=None):
                              "that have the neighbour reach the matrix unit; same features; include/umereg_sparse_conv_pairs.h)")
     parser.add_argument("--synthetic", type=int, default=8, help="number of synthetic pairs when no --pairs are given")
     parser.add_argument("--no-refine", action="store_true", help="skip the ICP refinement (evaluate.py:301)")
+    parser.add_argument("--icp-estimation", choices=list(icp_plane.ESTIMATIONS), default="point_to_point",
+                        help="estimation of the ICP refinement: the reference's point to point (default) or point to plane on target "
+                             "normals estimated on the device (csrc/icp_plane_api.h)")
+    parser.add_argument("--icp-normal-knn", type=int, default=icp_plane.DEFAULT_KNN,
+                        help="with --icp-estimation point_to_plane: neighbours per target normal (3 .. 64)")
+    parser.add_argument("--icp-normal-radius", type=float, default=None,
+                        help="with --icp-estimation point_to_plane: hybrid search, neighbours farther than this are dropped")
     cli = parser.parse_args(argv)
     config_path = benchmark_config_path(cli.benchmark)
     args = update_namespace_from_yaml(argparse.Namespace(benchmark=cli.benchmark), config_path)
+    args.icp_estimation, args.icp_normal_knn, args.icp_normal_radius = cli.icp_estimation, cli.icp_normal_knn, cli.icp_normal_radius
     rank, local_rank, world = init_distributed()
     device = torch.device("cuda", local_rank)
     torch.cuda.set_device(device)

@@ -622,6 +622,81 @@ def icp_point_to_point(src_pts, tgt_pts, T_init, max_correspondence_distance=0.2
     return SimpleNamespace(transformation=T, fitness=float(out[0]), inlier_rmse=float(out[1]), iterations=int(iters[0]))
 
 
+def _normals_arg(who, tgt_normals, tp):
+    """tgt_normals as the point-to-plane kernels read it: contiguous f32 [m,3] on the target's device (ValueError otherwise)."""
+    if not isinstance(tgt_normals, torch.Tensor) or tgt_normals.dtype != torch.float32 or tgt_normals.device != tp.device \
+            or tuple(tgt_normals.shape) != tuple(tp.shape):
+        got = (f"{tgt_normals.dtype} {tuple(tgt_normals.shape)} on {tgt_normals.device}" if isinstance(tgt_normals, torch.Tensor)
+               else type(tgt_normals).__name__)
+        raise ValueError(f"{who}: tgt_normals must be a float32 {tuple(tp.shape)} tensor on {tp.device}, got {got}")
+    return tgt_normals.contiguous()
+
+
+def estimate_normals(pts, knn=30, radius=None):
+    """open3d's `estimate_normals` with KDTreeSearchParamKNN(knn) or, with `radius`, KDTreeSearchParamHybrid(radius, knn):
+    pts [n,3] (device f32) -> unit normals [n,3] f32.  The neighbourhood of a point is its min(knn, n) nearest points, itself
+    included (the exact kNN of knn_points; ties -> lower index), without those farther than `radius`; the normal is the eigenvector of
+    the smallest eigenvalue of their fp64 covariance, with its largest component positive (open3d leaves the sign to its eigen-solver;
+    point-to-plane ICP does not depend on it).  Fewer than 3 neighbours or a zero covariance: (0, 0, 1).  3 <= knn <= 64.
+    Enqueued on the current stream; nothing is waited for."""
+    from . import icp_plane
+    knn = icp_plane.check_knn("estimate_normals", knn)
+    if radius is not None and not float(radius) > 0.0:
+        raise ValueError(f"estimate_normals: radius must be positive or None, got {radius!r}")
+    lib = icp_plane.load_native()
+    p = _dev(pts, "pts")
+    if p.dim() != 2 or p.shape[1] != 3:
+        raise ValueError(f"estimate_normals: expected an [n,3] cloud, got {tuple(p.shape)}")
+    n = p.shape[0]
+    dev = p.device
+    out = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    ws = _workspace(dev, lib.umereg_normals_workspace_bytes(n, knn), "normals")
+    _lib.call(dev, lib.umereg_estimate_normals_f32, _ptr(p), n, knn, 0.0 if radius is None else float(radius), _ptr(out), _ptr(ws),
+              ws.numel(), _stream_ptr(dev))
+    return out
+
+
+def icp_point_to_plane(src_pts, tgt_pts, tgt_normals, T_init, max_correspondence_distance=0.2, max_iteration=30,
+                       relative_fitness=1e-6, relative_rmse=1e-6):
+    """Point-to-plane ICP with open3d's registration_icp semantics (TransformationEstimationPointToPlane): the loop, the stop rule,
+    fitness and inlier_rmse of icp_point_to_point, with the update that minimises sum ((p - q) . n_q)^2 linearised in open3d's six
+    parameters.  tgt_normals [m,3] f32 on the device (estimate_normals(tgt_pts)); everything else, and the result, as
+    icp_point_to_point.  One documented deviation from open3d: the 6x6 normal equations are solved through their eigen-decomposition
+    with eigenvalues <= 1e-12 lambda_max treated as zero (open3d: LDLT) -- a single wall or a ground plane gives a finite update
+    that leaves the unconstrained directions alone; full-rank systems get the same solution."""
+    import numpy as np
+    from types import SimpleNamespace
+    from . import icp_plane
+    sp = _dev(src_pts, "src_pts"); tp = _dev(tgt_pts, "tgt_pts")
+    if sp.dim() != 2 or tp.dim() != 2 or sp.shape[1] != 3 or tp.shape[1] != 3:
+        raise ValueError(f"icp_point_to_plane: expected [n,3] clouds, got {tuple(sp.shape)}, {tuple(tp.shape)}")
+    nrm = _normals_arg("icp_point_to_plane", tgt_normals, tp)
+    lib = icp_plane.load_native()
+    if not isinstance(T_init, torch.Tensor):
+        T_init = np.asarray(T_init)
+    on_dev = isinstance(T_init, torch.Tensor) and T_init.is_cuda and T_init.dtype == torch.float32 and T_init.is_contiguous() \
+        and T_init.device == sp.device
+    if tuple(T_init.shape) != (4, 4):
+        raise ValueError("icp_point_to_plane: T_init must be 4x4")
+    T0 = None if on_dev else np.ascontiguousarray(np.asarray(T_init.detach().cpu() if isinstance(T_init, torch.Tensor) else T_init,
+                                                             dtype=np.float64))
+    n, m = sp.shape[0], tp.shape[0]
+    if n == 0 or m == 0:
+        raise ValueError("icp_point_to_plane: empty cloud")
+    dev = sp.device
+    T = np.empty((4, 4), dtype=np.float64)
+    out = np.zeros(2, dtype=np.float64)
+    iters = np.zeros(1, dtype=np.int32)
+    ws = _workspace(dev, lib.umereg_icp_plane_workspace_bytes(n, m), "icp_sync")
+    fn = lib.umereg_icp_point_to_plane_dev_f32 if on_dev else lib.umereg_icp_point_to_plane_f32
+    _lib.call(dev, fn, _ptr(sp), _ptr(tp), _ptr(nrm), n, m, T_init.data_ptr() if on_dev else T0.ctypes.data,
+              float(max_correspondence_distance), int(max_iteration), float(relative_fitness), float(relative_rmse), T.ctypes.data,
+              out.ctypes.data, out.ctypes.data + 8, iters.ctypes.data, _ptr(ws), ws.numel(), _stream_ptr(dev))
+    return SimpleNamespace(transformation=T, fitness=float(out[0]), inlier_rmse=float(out[1]), iterations=int(iters[0]))
+
+
 _icp_pinned = []      # pinned state buffers of finished IcpJobs, for reuse (a pinned allocation costs more than an ICP evaluation)
 _icp_inflight = {}    # (device index, stream) -> workspace tags of the jobs in flight there
 
@@ -632,14 +707,20 @@ class IcpJob:
     an asynchronous copy of the state to pinned host memory) and returns; result() waits for that copy, enqueues further batches in
     the rare case that four updates were not enough, and returns what icp_point_to_point returns.  A loop that keeps two pairs in
     flight (evaluate.evaluate_pairs) starts a pair's ICP right behind its hypothesis selection and collects it one pair later: the
-    refinement costs the host no round trip (reference evaluate.py:301 refines after the loop -- nothing needs it earlier)."""
+    refinement costs the host no round trip (reference evaluate.py:301 refines after the loop -- nothing needs it earlier).
+    tgt_normals (f32 [m,3] on the device, e.g. estimate_normals(tgt_pts) enqueued on the same stream): the point-to-plane chain of
+    icp_point_to_plane instead, with the same workspace-slot and pinned-state discipline."""
 
     def __init__(self, src_pts, tgt_pts, T_init_dev, max_correspondence_distance=0.2, max_iteration=30, relative_fitness=1e-6,
-                 relative_rmse=1e-6):
+                 relative_rmse=1e-6, tgt_normals=None):
         lib = _lib.load()
         self.sp = _dev(src_pts, "src_pts"); self.tp = _dev(tgt_pts, "tgt_pts")
         if self.sp.dim() != 2 or self.tp.dim() != 2 or self.sp.shape[1] != 3 or self.tp.shape[1] != 3:
             raise ValueError(f"IcpJob: expected [n,3] clouds, got {tuple(self.sp.shape)}, {tuple(self.tp.shape)}")
+        self.nrm = None if tgt_normals is None else _normals_arg("IcpJob", tgt_normals, self.tp)
+        if self.nrm is not None:
+            from . import icp_plane
+            lib = icp_plane.load_native()
         if not (isinstance(T_init_dev, torch.Tensor) and T_init_dev.is_cuda and T_init_dev.dtype == torch.float32
                 and T_init_dev.is_contiguous() and tuple(T_init_dev.shape) == (4, 4) and T_init_dev.device == self.sp.device):
             raise ValueError("IcpJob: T_init_dev must be a contiguous float32 [4,4] tensor on the clouds' device")
@@ -657,7 +738,8 @@ class IcpJob:
         self.state = None
         self._res = None
         try:
-            self.ws = _workspace(dev, lib.umereg_icp_workspace_bytes(n, m), "icp" if self.slot == 0 else f"icp{self.slot}")
+            need = lib.umereg_icp_workspace_bytes(n, m) if self.nrm is None else lib.umereg_icp_plane_workspace_bytes(n, m)
+            self.ws = _workspace(dev, need, "icp" if self.slot == 0 else f"icp{self.slot}")
             self.state = _icp_pinned.pop() if _icp_pinned else torch.empty(int(lib.umereg_icp_state_bytes()), dtype=torch.uint8, pin_memory=True)
             self.event = torch.cuda.Event()
             self.launched = 0
@@ -696,9 +778,14 @@ class IcpJob:
     def _enqueue(self, first, iterations):
         lib = _lib.load()
         d, it, rf, rr = self.par
-        _lib.call(self.dev, lib.umereg_icp_enqueue_f32, _ptr(self.sp), _ptr(self.tp), self.sp.shape[0], self.tp.shape[0], _ptr(self.T0), d,
-                  it, rf, rr, 1 if first else 0, int(iterations), self.state.data_ptr(), _ptr(self.ws), self.ws.numel(),
-                  self.stream.cuda_stream)
+        if self.nrm is None:
+            _lib.call(self.dev, lib.umereg_icp_enqueue_f32, _ptr(self.sp), _ptr(self.tp), self.sp.shape[0], self.tp.shape[0], _ptr(self.T0), d,
+                      it, rf, rr, 1 if first else 0, int(iterations), self.state.data_ptr(), _ptr(self.ws), self.ws.numel(),
+                      self.stream.cuda_stream)
+        else:
+            _lib.call(self.dev, lib.umereg_icp_plane_enqueue_f32, _ptr(self.sp), _ptr(self.tp), _ptr(self.nrm), self.sp.shape[0],
+                      self.tp.shape[0], _ptr(self.T0), d, it, rf, rr, 1 if first else 0, int(iterations), self.state.data_ptr(),
+                      _ptr(self.ws), self.ws.numel(), self.stream.cuda_stream)
         self.launched += iterations
         self.event.record(self.stream)
 
