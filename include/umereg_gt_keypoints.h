@@ -1,19 +1,17 @@
-/* gt_keypoints_api.h -- C entries of the device-side selection of ground-truth-driven keypoints (csrc/gt_keypoints.hip): what
+/* umereg_gt_keypoints.h -- C ABI of the device-side selection of ground-truth-driven keypoints (csrc/gt_keypoints.hip): what
  * `utils.loc_utils.generate_ume_from_keypoints2(..., selection="device")` runs in place of the moment matrices of EVERY candidate, the
  * two sorts and the per-keypoint search structures of the default path.
  *
- * The header lives beside the kernels, not under include/ (the public ABI census is pinned); the entries are typed by a module-owned
- * table (umeregrobust_amd/gt_keypoints.py: GT_KEYPOINTS_SIGNATURES).
- *
  * Same conventions as umereg.h: outputs and workspace belong to the caller, every compute entry takes a HIP stream (NULL = the
  * default stream), returns UMEREG_OK or a negative UMEREG_E* code, reports argument errors before it probes for a device, allocates
- * nothing and never waits for the device.  The size query is host arithmetic and returns 0 for arguments the entries refuse.
+ * nothing and never waits for the device.  The size query is host arithmetic and returns 0 for arguments the entries refuse.  The entry
+ * points here are typed by their own table (umeregrobust_amd/gt_keypoints.py: GT_KEYPOINTS_SIGNATURES).
  *
  * Every output is a function of the inputs alone: same bytes in every run, whatever the workspace or the outputs held before.  No
  * word of the workspace is read that the call did not write.  The atomics of the selection (a ticket and a found-counter per batch
  * element) decide how many candidates are TESTED, never which are selected.  No kernel waits for another workgroup. */
-#ifndef UMEREG_GT_KEYPOINTS_API_H
-#define UMEREG_GT_KEYPOINTS_API_H
+#ifndef UMEREG_GT_KEYPOINTS_H
+#define UMEREG_GT_KEYPOINTS_H
 
 #include <stddef.h>
 #include <stdint.h>

@@ -1,18 +1,16 @@
-/* icp_plane_api.h -- C entries of the opt-in point-to-plane refinement: target normals (csrc/normals.hip) and the point-to-plane
+/* umereg_icp_plane.h -- C ABI of the opt-in point-to-plane refinement: target normals (csrc/normals.hip) and the point-to-plane
  * ICP loop (csrc/icp.hip), the counterparts of open3d's
  *     tgt.estimate_normals(KDTreeSearchParamKNN(knn) | KDTreeSearchParamHybrid(radius, knn))
  *     registration_icp(src, tgt, d, T_init, TransformationEstimationPointToPlane(), ICPConvergenceCriteria(max_iteration=...))
  * open3d is not installable here: parity with it stays unpinned, as for the point-to-point loop.
  *
- * The header lives beside the kernels, not under include/ (the public ABI census is pinned); the entries are typed by a module-owned
- * table (umeregrobust_amd/icp_plane.py: ICP_PLANE_SIGNATURES).
- *
  * Same conventions as umereg.h: outputs and workspace belong to the caller, every compute entry takes a HIP stream (NULL = the
  * default stream), returns UMEREG_OK or a negative UMEREG_E* code, reports argument errors before it probes for a device and
  * allocates nothing.  The size queries are host arithmetic and return 0 for arguments the entries refuse.  Every output is a function
- * of the inputs alone: no atomics, fixed reduction trees, no word of the workspace read that the call did not write. */
-#ifndef UMEREG_ICP_PLANE_API_H
-#define UMEREG_ICP_PLANE_API_H
+ * of the inputs alone: no atomics, fixed reduction trees, no word of the workspace read that the call did not write.  The entry points here
+ * are typed by their own table (umeregrobust_amd/icp_plane.py: ICP_PLANE_SIGNATURES). */
+#ifndef UMEREG_ICP_PLANE_H
+#define UMEREG_ICP_PLANE_H
 
 #include <stddef.h>
 #include <stdint.h>

@@ -1,15 +1,13 @@
-/* infonce_api.h -- C entries of the fused InfoNCE point-wise loss, forward and backward (csrc/infonce.hip): what
+/* umereg_infonce.h -- C ABI of the fused InfoNCE point-wise loss, forward and backward (csrc/infonce.hip): what
  * `pw_loss.MyInfoNCELossNoSeg` runs in place of the torch statements of the reference's loss.py:19-46 (the gathers, the cosine
  * similarity, the S x S logit matrix, the cdist mask, the two exp tensors, the concatenation, the sum, the log and the mean, and
  * everything autograd keeps of them).  No S x S tensor is formed, forward or backward.
  *
- * The header lives beside the kernels, not under include/: the public ABI census (thirteen headers) is pinned, and moving this one
- * there is a follow-up.  The entries are typed by a module-owned table (umeregrobust_amd/infonce.py: INFONCE_SIGNATURES).
- *
  * Same conventions as umereg.h / umereg_ume_grad.h: outputs and workspace belong to the caller, every compute entry takes a HIP
  * stream (NULL = the default stream), returns UMEREG_OK or a negative UMEREG_E* code, reports argument errors before it probes for a
  * device, returns UMEREG_ENODEV where no HIP device is visible, allocates nothing and never waits for the device.  The size query is
- * host arithmetic and returns 0 for arguments the compute entries refuse.
+ * host arithmetic and returns 0 for arguments the compute entries refuse.  The entry points here are typed by their own table
+ * (umeregrobust_amd/infonce.py: INFONCE_SIGNATURES).
  *
  * Contract.  Per batch element b and sample s, with i = matches[b][s][0] and j = matches[b][s][1]:
  *     a_s = src_feat[b][i],  x_s = src_pts[b][i],  p_s = tgt_feat[b][j]           (32 channels only)
@@ -27,8 +25,8 @@
  *
  * Both passes are deterministic: every sum runs in one fixed order, there is no floating-point atomic, and no result depends on what
  * the workspace or the outputs held. */
-#ifndef UMEREG_INFONCE_API_H
-#define UMEREG_INFONCE_API_H
+#ifndef UMEREG_INFONCE_H
+#define UMEREG_INFONCE_H
 
 #include <stddef.h>
 #include <stdint.h>

@@ -1,9 +1,11 @@
 """Shared by the CPU tests of the C ABI: what a header under include/ declares, read from its text.
 
     declarations("umereg_assign.h") -> {symbol: number of parameters}, in no particular order
+    return_types("umereg_assign.h") -> {symbol: "int" | "size_t" | "const char*" | whatever else the header writes there}
 
 Comments are stripped first (a comment may name an entry and an argument list).  A declaration is `umereg_<name>(` up to its closing
-parenthesis; `(void)` and `()` count as no parameter, anything else as one parameter per top-level comma plus one."""
+parenthesis; `(void)` and `()` count as no parameter, anything else as one parameter per top-level comma plus one.  Its return type is what stands in front of the name on the
+declaration's line, words one space apart and every `*` attached to the word before it."""
 import os
 import re
 
@@ -25,6 +27,9 @@ HEADERS = {
     "umereg_collate.h": ("collate.COLLATE_SIGNATURES", 2),
     "umereg_assign.h": ("assign.ASSIGN_SIGNATURES", 2),
     "umereg_scan_prep.h": ("raw_scan.SCAN_PREP_SIGNATURES", 2),
+    "umereg_infonce.h": ("infonce.INFONCE_SIGNATURES", 3),
+    "umereg_gt_keypoints.h": ("gt_keypoints.GT_KEYPOINTS_SIGNATURES", 4),
+    "umereg_icp_plane.h": ("icp_plane.ICP_PLANE_SIGNATURES", 6),
 }
 
 
@@ -56,6 +61,18 @@ def _count(plist):
     return n + 1
 
 
+def _names(header):
+    return sorted(set(re.findall(r"\b(umereg_[a-z0-9_]+)\s*\(", text(header))))
+
+
 def declarations(header):
-    names = sorted(set(re.findall(r"\b(umereg_[a-z0-9_]+)\s*\(", text(header))))
-    return {name: _count(params(header, name)) for name in names}
+    return {name: _count(params(header, name)) for name in _names(header)}
+
+
+def return_types(header):
+    src, out = text(header), {}
+    for name in _names(header):
+        m = re.search(r"^([^\n;(){}#]*?)\b" + re.escape(name) + r"\s*\(", src, flags=re.M)
+        assert m and m.group(1).strip(), f"{name}: no return type in front of its declaration in include/{header}"
+        out[name] = re.sub(r"\s*\*", "*", " ".join(m.group(1).split()))
+    return out

@@ -1,4 +1,4 @@
-"""fp64 restatement of the point-to-plane refinement (csrc/icp_plane_api.h), for tests/test_icp_plane_cpu.py and
+"""fp64 restatement of the point-to-plane refinement (include/umereg_icp_plane.h), for tests/test_icp_plane_cpu.py and
 tests/test_icp_plane_gpu.py: normals from numpy's `eigh`, the open3d ICP loop with a thresholded `eigh` solve of the 6x6 normal
 equations.  Correspondences and neighbour lists come from the oracle (oracle.icp_evaluate, oracle.knn_points), which already mirror
 the device's fp32 distance and its tie rule (lower index)."""

@@ -19,33 +19,38 @@ def _alias(attr):
 
 
 def test_library_builds_and_one_table_per_header():
-    """the library builds and loads; include/ holds the thirteen headers, _lib.TABLES one table for each, no symbol in two of them"""
+    """the library builds and loads; include/ holds the sixteen headers, _lib.TABLES one table for each, no symbol in two of them"""
     import umeregrobust_amd
     from umeregrobust_amd import _lib
     assert os.path.exists(umeregrobust_amd.build_native())
-    assert sorted(os.listdir(abi_headers.INCLUDE)) == sorted(abi_headers.HEADERS) == sorted(_lib.TABLES) and len(_lib.TABLES) == 13
+    assert sorted(os.listdir(abi_headers.INCLUDE)) == sorted(abi_headers.HEADERS) == sorted(_lib.TABLES) and len(_lib.TABLES) == 16
     assert _lib.TABLES["umereg.h"] is _lib.SIGNATURES
     names = [name for table in _lib.TABLES.values() for name in table]
-    assert len(names) == len(set(names)) == 113, sorted(n for n in set(names) if names.count(n) > 1)
+    assert len(names) == len(set(names)) == 126, sorted(n for n in set(names) if names.count(n) > 1)
     assert _lib.load().umereg_abi_version() == _lib.ABI_VERSION == 2
+
+
+# what a declaration returns -> the restype its table entry must carry
+RESTYPES = {"size_t": ctypes.c_size_t, "int": ctypes.c_int, "const char*": ctypes.c_char_p}
 
 
 @pytest.mark.parametrize("header", list(abi_headers.HEADERS))
 def test_table_mirrors_its_header_and_every_symbol_is_exported(header):
     """Per header: the table's keys are the header's symbols (their number pinned), the built library exports each, every
-    declaration has as many parameters as the table has argtypes, the module's public alias IS the table, and no symbol of it is
-    in another header's table."""
+    declaration has as many parameters as the table has argtypes and returns what the table's restype says (size_t, int or
+    const char*), the module's public alias IS the table, and no symbol of it is in another header's table."""
     import umeregrobust_amd
     from umeregrobust_amd import _lib
     alias, count = abi_headers.HEADERS[header]
     table = _lib.TABLES[header]
     assert _alias(alias) is table
-    declared = abi_headers.declarations(header)
-    assert sorted(table) == sorted(declared) and len(declared) == count
+    declared, returns = abi_headers.declarations(header), abi_headers.return_types(header)
+    assert sorted(table) == sorted(declared) == sorted(returns) and len(declared) == count
     lib = ctypes.CDLL(umeregrobust_amd.build_native())
     for name, n_params in declared.items():
         assert hasattr(lib, name), f"{name} declared in include/{header} but not exported"
         assert len(table[name][1]) == n_params, name
+        assert table[name][0] is RESTYPES[returns[name]], (name, returns[name])
     for other, theirs in _lib.TABLES.items():
         assert other == header or not set(table) & set(theirs), (header, other)
     assert _lib.load().umereg_abi_version() == _lib.ABI_VERSION == 2
@@ -110,7 +115,7 @@ def test_no_status_entry_is_called_directly():
     make the tensors' device current): nowhere under umeregrobust_amd/ is one called as `lib.umereg_...(`."""
     from umeregrobust_amd import _lib
     status = {name for table in _lib.TABLES.values() for name, (res, _) in table.items() if res is ctypes.c_int} - NOT_A_STATUS
-    assert len(status) == 80 and NOT_A_STATUS <= {n for t in _lib.TABLES.values() for n in t}
+    assert len(status) == 89 and NOT_A_STATUS <= {n for t in _lib.TABLES.values() for n in t}
     pkg, seen = os.path.join(REPO, "umeregrobust_amd"), 0
     for root, _, files in os.walk(pkg):
         for f in files:
@@ -122,7 +127,7 @@ def test_no_status_entry_is_called_directly():
 
 
 def test_load_typed_types_a_table_once_and_names_a_missing_symbol():
-    """_lib.load_typed: what every module's load_native() goes through"""
+    """_lib.load_typed: the loader for a table from outside the package (every module's own load_native is _lib.load)"""
     from umeregrobust_amd import _lib, gt_matches
     lib = _lib.load_typed(gt_matches.GT_MATCH_SIGNATURES)
     assert lib is _lib.load() and lib is gt_matches.load_native()

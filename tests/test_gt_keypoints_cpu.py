@@ -1,8 +1,7 @@
-"""CPU: the device-side keypoint selection without a GPU -- the entries csrc/gt_keypoints_api.h declares against the built library and
-the module's own signature table, their refusals without a device, the `selection=` keyword on its call paths, and the numpy
+"""CPU: the device-side keypoint selection without a GPU -- the header's place in the one ABI (tests/test_abi.py checks
+include/umereg_gt_keypoints.h against its table), the entries' refusals without a device, the `selection=` keyword on its call paths, and the numpy
 restatement the GPU tests judge the kernels by (tests/gt_keypoints_cases.py): pinned against oracle.generate_ume_from_keypoints2 on
 every edge cloud, each of which is shown to sit on the edge it is named for."""
-import ctypes
 import inspect
 import os
 
@@ -15,8 +14,7 @@ import gt_keypoints_cases as gc
 from oracle import oracle as orc
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-API_HEADER = os.path.join(REPO, "umeregrobust_amd", "csrc", "gt_keypoints_api.h")
-ENTRIES = ("umereg_gt_keypoints_workspace_bytes", "umereg_gt_candidates", "umereg_gt_select_f32", "umereg_gt_ball_any_f32")
+API_HEADER = os.path.join(abi_headers.INCLUDE, "umereg_gt_keypoints.h")
 CASES = gc.all_cases()
 
 
@@ -26,21 +24,12 @@ def lib():
     return gt_keypoints.load_native()
 
 
-# ---- 1. exports, table, constants ----------------------------------------------------------------------------------------------------
+# ---- 1. the header's place, constants --------------------------------------------------------------------------------------------------
 
-def test_the_library_exports_what_the_header_declares_and_the_table_mirrors_it(lib):
+def test_the_header_is_one_of_the_sixteen_and_its_table_is_the_package_s(lib):
     from umeregrobust_amd import _build, _lib, gt_keypoints
-    declared = abi_headers.declarations(API_HEADER)
-    assert sorted(declared) == sorted(ENTRIES)
-    for name in declared:
-        assert hasattr(lib, name), f"libumereg.so does not export {name}"
-    assert sorted(gt_keypoints.GT_KEYPOINTS_SIGNATURES) == sorted(declared)
-    for name, n_params in declared.items():
-        assert len(gt_keypoints.GT_KEYPOINTS_SIGNATURES[name][1]) == n_params, name
-    for table in _lib.TABLES.values():
-        assert not set(table) & set(declared)
-    assert gt_keypoints.GT_KEYPOINTS_SIGNATURES["umereg_gt_keypoints_workspace_bytes"][0] is ctypes.c_size_t
-    assert len(os.listdir(abi_headers.INCLUDE)) == 13 == len(_lib.TABLES)          # include/ and TABLES are unchanged
+    assert gt_keypoints.GT_KEYPOINTS_SIGNATURES is _lib.TABLES["umereg_gt_keypoints.h"] and gt_keypoints.load_native is _lib.load
+    assert len(os.listdir(abi_headers.INCLUDE)) == 16 == len(_lib.TABLES)
     assert API_HEADER in _build.headers()                                          # part of the build hash
 
 

@@ -1,6 +1,6 @@
 """CPU: the ground the point-to-plane refinement stands on -- csrc/icp_plane_math.h compiled for the host
-(tests/icp_plane_host.cpp) against numpy, the fp64 restatement (tests/icp_plane_ref.py) on the corner case, the binding table
-against its header, and the refusals of the Python entry points without a GPU.
+(tests/icp_plane_host.cpp) against numpy, the fp64 restatement (tests/icp_plane_ref.py) on the corner case, the header's place in the one ABI
+(tests/test_abi.py checks include/umereg_icp_plane.h against its table), and the refusals of the Python entry points without a GPU.
 
 Bounds (derived, not measured): the arithmetic is fp64 throughout, so an eigenvector errs by ~10 eps / gap ~ 1e-14 where the gap
 (l1 - l0) / l2 >= 0.1 -- 1e-9 rad leaves room for the summation order; a solve of a system with cond <= 1e4 errs by
@@ -12,10 +12,10 @@ import numpy as np
 import pytest
 import torch
 
+import abi_headers
 import icp_plane_ref as ref
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(REPO, "umeregrobust_amd", "csrc", "icp_plane_api.h")
+HEADER = "umereg_icp_plane.h"
 
 
 @pytest.fixture(scope="module")
@@ -150,20 +150,16 @@ def test_restatement_on_the_corner_case():
     assert float((gap < ref.GAP_MIN).mean()) <= ref.GAP_EXCLUDED_MAX
 
 
-# ---- the binding table and the Python surface without a GPU ------------------------------------------------------------------
+# ---- the header's place and the Python surface without a GPU -----------------------------------------------------------------
 
-def test_table_mirrors_its_header():
-    from umeregrobust_amd import _lib, icp_plane
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    protos = {m.group(1): m.group(2) for m in re.finditer(r"\b(umereg_\w+)\s*\(([^)]*)\)\s*;", text)}
-    assert sorted(protos) == sorted(icp_plane.ICP_PLANE_SIGNATURES)
-    for name, (_, argtypes) in icp_plane.ICP_PLANE_SIGNATURES.items():
-        assert len(argtypes) == len(protos[name].split(",")), name
-    # typed by the module, not by the package tables; the public headers do not know them
-    assert not any(name in table for table in _lib.TABLES.values() for name in icp_plane.ICP_PLANE_SIGNATURES)
-    for h in os.listdir(os.path.join(REPO, "include")):
-        assert "icp_point_to_plane" not in open(os.path.join(REPO, "include", h)).read()
+def test_the_header_is_one_of_the_sixteen_and_its_table_is_the_package_s():
+    from umeregrobust_amd import _build, _lib, icp_plane
+    # typed by the package tables; of the public headers this one, and no other, declares the point-to-plane entries
+    assert icp_plane.ICP_PLANE_SIGNATURES is _lib.TABLES[HEADER] and icp_plane.load_native is _lib.load
+    assert len(os.listdir(abi_headers.INCLUDE)) == 16 == len(_lib.TABLES)
+    assert [h for h in sorted(os.listdir(abi_headers.INCLUDE)) if "icp_point_to_plane" in abi_headers.text(h)] == [HEADER]
+    assert os.path.join(abi_headers.INCLUDE, HEADER) in _build.headers()          # part of the build hash
+    text = abi_headers.text(HEADER)
     assert (icp_plane.MIN_KNN, icp_plane.MAX_KNN) == tuple(int(re.search(rf"#define UMEREG_NORMALS_{k}_KNN (\d+)", text).group(1))
                                                            for k in ("MIN", "MAX"))
     lib = icp_plane.load_native()
@@ -178,9 +174,8 @@ def test_entries_check_arguments_before_the_device():
     assert lib.umereg_normals_workspace_bytes(0, 30) == 0 and lib.umereg_normals_workspace_bytes(10, 2) == 0
     assert lib.umereg_normals_workspace_bytes(10, 65) == 0 and lib.umereg_normals_workspace_bytes(10, 30) > 0
     assert lib.umereg_icp_plane_workspace_bytes(0, 5) == 0 and lib.umereg_icp_plane_workspace_bytes(5, 0) == 0
-    base = __import__("umeregrobust_amd")._lib.load()
     # 29 sums per block of 64 source points where point to point has 17 (32 blocks: both partial tables are multiples of 256 bytes)
-    assert lib.umereg_icp_plane_workspace_bytes(2048, 100) - base.umereg_icp_workspace_bytes(2048, 100) == 32 * 12 * 8
+    assert lib.umereg_icp_plane_workspace_bytes(2048, 100) - lib.umereg_icp_workspace_bytes(2048, 100) == 32 * 12 * 8
     assert lib.umereg_estimate_normals_f32(None, 10, 30, 0.0, p, p, 1 << 16, None) == -1
     assert lib.umereg_estimate_normals_f32(p, 0, 30, 0.0, p, p, 1 << 16, None) == -1
     for knn in (2, 65, -1):
@@ -195,7 +190,7 @@ def test_entries_check_arguments_before_the_device():
     assert b"icp_point_to_plane" in lib.umereg_last_error()
     assert lib.umereg_icp_plane_enqueue_f32(p, p, None, 10, 10, p, 0.2, 5, 1e-6, 1e-6, 1, 4, p, p, 1 << 16, None) == -1
     assert lib.umereg_icp_plane_enqueue_f32(p, p, p, 10, 10, p, 0.2, 5, 1e-6, 1e-6, 1, 4, None, p, 1 << 16, None) == -1
-    if base.umereg_device_count(None, 0) == 0:
+    if lib.umereg_device_count(None, 0) == 0:
         assert run() == -2 and lib.umereg_estimate_normals_f32(p, 10, 30, 0.0, p, p, 1 << 16, None) == -2      # UMEREG_ENODEV
 
 

@@ -1,4 +1,4 @@
-"""GPU: the opt-in point-to-plane refinement (csrc/icp_plane_api.h) against its fp64 restatement (tests/icp_plane_ref.py).
+"""GPU: the opt-in point-to-plane refinement (include/umereg_icp_plane.h) against its fp64 restatement (tests/icp_plane_ref.py).
 
 Normals: the library returns f32, so against the fp64 eigenvector the bar is the CPU suite's 1e-9 rad plus the rounding of a unit
 vector to f32, sqrt(3) 2^-25 rad (icp_plane_ref.ANGLE_F32), wherever the gap (l1 - l0) / l2 >= 0.1; at most 2 % of a cloud may fall

@@ -1,7 +1,6 @@
-"""CPU: the fused InfoNCE loss without a GPU -- the entries csrc/infonce_api.h declares against the built library and the module's own
-signature table, their refusals without a device, the Python refusals, and the tile plan (csrc/infonce_plan.h through
+"""CPU: the fused InfoNCE loss without a GPU -- the header's place in the one ABI (tests/test_abi.py checks include/umereg_infonce.h against
+its table), the entries' refusals without a device, the Python refusals, and the tile plan (csrc/infonce_plan.h through
 tests/infonce_plan_host.cpp) against the Python restatement the GPU tests place their edges with (tests/infonce_cases.py)."""
-import ctypes
 import inspect
 import os
 import shutil
@@ -14,8 +13,7 @@ import abi_headers
 import infonce_cases as ic
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-API_HEADER = os.path.join(REPO, "umeregrobust_amd", "csrc", "infonce_api.h")
-ENTRIES = ("umereg_infonce_workspace_bytes", "umereg_infonce_fwd_f32", "umereg_infonce_bwd_f32")
+API_HEADER = os.path.join(abi_headers.INCLUDE, "umereg_infonce.h")
 
 
 @pytest.fixture(scope="module")
@@ -24,22 +22,12 @@ def lib():
     return infonce.load_native()
 
 
-# ---- 1. exports and table ------------------------------------------------------------------------------------------------------------
+# ---- 1. the header's place ------------------------------------------------------------------------------------------------------------
 
-def test_the_library_exports_what_the_header_declares_and_the_table_mirrors_it(lib):
-    from umeregrobust_amd import _lib, infonce
-    declared = abi_headers.declarations(API_HEADER)         # (an absolute path: read where it lies, beside the kernels)
-    assert sorted(declared) == sorted(ENTRIES)
-    for name in declared:
-        assert hasattr(lib, name), f"libumereg.so does not export {name}"
-    assert sorted(infonce.INFONCE_SIGNATURES) == sorted(declared)
-    for name, n_params in declared.items():
-        assert len(infonce.INFONCE_SIGNATURES[name][1]) == n_params, name
-    for table in _lib.TABLES.values():
-        assert not set(table) & set(declared)
-    assert infonce.INFONCE_SIGNATURES["umereg_infonce_workspace_bytes"][0] is ctypes.c_size_t
-    assert len(os.listdir(abi_headers.INCLUDE)) == 13 == len(_lib.TABLES)
-    from umeregrobust_amd import _build
+def test_the_header_is_one_of_the_sixteen_and_its_table_is_the_package_s(lib):
+    from umeregrobust_amd import _build, _lib, infonce
+    assert infonce.INFONCE_SIGNATURES is _lib.TABLES["umereg_infonce.h"] and infonce.load_native is _lib.load
+    assert len(os.listdir(abi_headers.INCLUDE)) == 16 == len(_lib.TABLES)
     assert API_HEADER in _build.headers()                    # part of the build hash
 
 

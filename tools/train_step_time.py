@@ -280,7 +280,7 @@ def main():
     ap.add_argument("--train-precision", default="f32", choices=["f32", "f16"], help="operand precision of the network in the phases lines")
     ap.add_argument("--fused-norm", action="store_true", help="the network of the phases lines with fused_norm=True (include/umereg_bn_act.h)")
     ap.add_argument("--fused-pointwise", action="store_true", help="the point-wise loss of the phases lines on pw_loss.MyInfoNCELossNoSeg")
-    ap.add_argument("--device-keypoints", action="store_true", help="the UME loss of the phases lines with selection=\"device\" (csrc/gt_keypoints_api.h)")
+    ap.add_argument("--device-keypoints", action="store_true", help="the UME loss of the phases lines with selection=\"device\" (include/umereg_gt_keypoints.h)")
     ap.add_argument("--phases-only", action="store_true", help="skip the match-kernel comparison")
     a = ap.parse_args()
     dev = torch.device("cuda:0")

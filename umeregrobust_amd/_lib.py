@@ -225,6 +225,33 @@ _SCAN_PREP = {
                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
+_INFONCE_COMMON = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float]
+_INFONCE = {
+    "umereg_infonce_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "umereg_infonce_fwd_f32": (c_int, _INFONCE_COMMON + [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "umereg_infonce_bwd_f32": (c_int, _INFONCE_COMMON + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
+_GT_KEYPOINTS = {
+    "umereg_gt_keypoints_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "umereg_gt_candidates": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "umereg_gt_select_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_size_t, c_void_p]),
+    "umereg_gt_ball_any_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
+}
+
+_ICP_PLANE = {
+    "umereg_normals_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "umereg_estimate_normals_f32": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "umereg_icp_plane_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "umereg_icp_point_to_plane_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_double, c_double,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "umereg_icp_point_to_plane_dev_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_double,
+                                                  c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "umereg_icp_plane_enqueue_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_double, c_double,
+                                             c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
 # header under include/ -> {name: (restype, argtypes)}: each table mirrors its header one to one, and one .so exports them all
 TABLES = {
     "umereg.h": SIGNATURES,
@@ -240,6 +267,9 @@ TABLES = {
     "umereg_collate.h": _COLLATE,
     "umereg_assign.h": _ASSIGN,
     "umereg_scan_prep.h": _SCAN_PREP,
+    "umereg_infonce.h": _INFONCE,
+    "umereg_gt_keypoints.h": _GT_KEYPOINTS,
+    "umereg_icp_plane.h": _ICP_PLANE,
 }
 
 ABI_VERSION = 2

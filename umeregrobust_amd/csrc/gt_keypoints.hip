@@ -1,5 +1,5 @@
 // gt_keypoints.hip -- device-side selection of the ground-truth-driven keypoints of generate_ume_from_keypoints2 (reference
-// utils/loc_utils.py:86-188) for gfx950; the entries are declared in gt_keypoints_api.h.
+// utils/loc_utils.py:86-188) for gfx950; the entries are declared in umereg_gt_keypoints.h.
 //
 //   candidates  the flagged source points in DESCENDING index order: compact.h's count / scan / scatter over the reversed row
 //   select      the density predicate min(hits, max_nn) >= min_nn, evaluated lazily: one wavefront per candidate over the packed
@@ -12,7 +12,7 @@
 
 #include "ball_search.h"
 #include "compact.h"
-#include "gt_keypoints_api.h"
+#include "umereg_gt_keypoints.h"
 
 namespace umereg {
 

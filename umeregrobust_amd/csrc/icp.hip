@@ -18,14 +18,14 @@
 //   icp_step_kernel  one workgroup: totals, convergence test, 3x3 polar rotation, T <- update * T.
 // Once `done` is set the remaining queued launches return immediately.
 //
-// Point to plane (opt-in, icp_plane_api.h; open3d's TransformationEstimationPointToPlane): the same loop, search and stop rule -- the
+// Point to plane (opt-in, umereg_icp_plane.h; open3d's TransformationEstimationPointToPlane): the same loop, search and stop rule -- the
 // kernels are templates with one search body and two accumulations.  With n_q the normal of the matched target point (looked up by the
 // ORIGINAL index the packed table carries in .w), r = (p' - q) . n_q and J = [p' x n_q, n_q], the evaluation sums {n, sum |p'-q|^2,
 // the 21 upper entries of sum J J^T, the 6 of sum J r} (29 instead of 17, the same reduction tree) and the step solves
 // (sum J J^T) x = -(sum J r) through a 6x6 Jacobi eigen-decomposition (icp_plane_math.h: eigenvalues <= 1e-12 lambda_max count as
 // zero; open3d uses Eigen's LDLT, the two differ on rank-deficient systems only), update = [Rz(x2) Ry(x1) Rx(x0) | x3..5].
 #include "grid.h"
-#include "icp_plane_api.h"
+#include "umereg_icp_plane.h"
 #include "icp_plane_math.h"
 #include "polar.h"
 
@@ -419,26 +419,38 @@ static int icp_run(const IcpMode& mode, const float* src, const float* tgt, int 
 
 UMEREG_API size_t umereg_icp_state_bytes(void) { return sizeof(IcpState); }
 
+// the two enqueue-only entries behind their own null checks: icp_enqueue, then the asynchronous download of the state; `entry` names
+// the entry in the messages that are its own, mode.who in the checks it shares with the synchronous calls
+static int icp_enqueue_download(const IcpMode& mode, const char* entry, const float* src, const float* tgt, int n_src, int n_tgt,
+                                const float* T_init_dev, float max_correspondence_distance, int max_iteration, double relative_fitness,
+                                double relative_rmse, int first, int iterations, void* state_host, void* workspace,
+                                size_t workspace_bytes, void* stream)
+{
+    UMEREG_REQUIRE(!first || T_init_dev, "%s: null T_init", entry);
+    hipStream_t st = (hipStream_t)stream;
+    IcpState* state = nullptr;
+    if (int rc = icp_enqueue(mode, src, tgt, n_src, n_tgt, nullptr, T_init_dev, max_correspondence_distance, max_iteration,
+                             relative_fitness, relative_rmse, first != 0, iterations, workspace, workspace_bytes, st, &state))
+        return rc;
+    if (hipMemcpyAsync(state_host, state, sizeof(IcpState), hipMemcpyDeviceToHost, st) != hipSuccess) {
+        set_error("%s: state download failed", entry);
+        return UMEREG_ELAUNCH;
+    }
+    return UMEREG_OK;
+}
+
 UMEREG_API int umereg_icp_enqueue_f32(const float* src, const float* tgt, int n_src, int n_tgt, const float* T_init_dev,
                                       float max_correspondence_distance, int max_iteration, double relative_fitness,
                                       double relative_rmse, int first, int iterations, void* state_host, void* workspace,
                                       size_t workspace_bytes, void* stream)
 {
     UMEREG_REQUIRE(state_host, "icp_enqueue: null state_host");
-    UMEREG_REQUIRE(!first || T_init_dev, "icp_enqueue: null T_init");
-    hipStream_t st = (hipStream_t)stream;
-    IcpState* state = nullptr;
-    if (int rc = icp_enqueue(kIcpPointToPoint, src, tgt, n_src, n_tgt, nullptr, T_init_dev, max_correspondence_distance, max_iteration,
-                             relative_fitness, relative_rmse, first != 0, iterations, workspace, workspace_bytes, st, &state))
-        return rc;
-    if (hipMemcpyAsync(state_host, state, sizeof(IcpState), hipMemcpyDeviceToHost, st) != hipSuccess) {
-        set_error("icp_enqueue: state download failed");
-        return UMEREG_ELAUNCH;
-    }
-    return UMEREG_OK;
+    return icp_enqueue_download(kIcpPointToPoint, "icp_enqueue", src, tgt, n_src, n_tgt, T_init_dev, max_correspondence_distance,
+                                max_iteration, relative_fitness, relative_rmse, first, iterations, state_host, workspace,
+                                workspace_bytes, stream);
 }
 
-// ---- point to plane: the same host paths with the target's normals (icp_plane_api.h) ---------------------------------------
+// ---- point to plane: the same host paths with the target's normals (umereg_icp_plane.h) ------------------------------------
 UMEREG_API int umereg_icp_point_to_plane_f32(const float* src, const float* tgt, const float* tgt_normals, int n_src, int n_tgt,
                                              const double* T_init_host, float max_correspondence_distance, int max_iteration,
                                              double relative_fitness, double relative_rmse, double* T_out_host, double* fitness_host,
@@ -472,18 +484,10 @@ UMEREG_API int umereg_icp_plane_enqueue_f32(const float* src, const float* tgt, 
 {
     UMEREG_REQUIRE(state_host, "icp_plane_enqueue: null state_host");
     UMEREG_REQUIRE(tgt_normals, "icp_plane_enqueue: null normals");
-    UMEREG_REQUIRE(!first || T_init_dev, "icp_plane_enqueue: null T_init");
-    hipStream_t st = (hipStream_t)stream;
-    IcpState* state = nullptr;
     const IcpMode mode = {tgt_normals, "icp_point_to_plane"};
-    if (int rc = icp_enqueue(mode, src, tgt, n_src, n_tgt, nullptr, T_init_dev, max_correspondence_distance, max_iteration,
-                             relative_fitness, relative_rmse, first != 0, iterations, workspace, workspace_bytes, st, &state))
-        return rc;
-    if (hipMemcpyAsync(state_host, state, sizeof(IcpState), hipMemcpyDeviceToHost, st) != hipSuccess) {
-        set_error("icp_plane_enqueue: state download failed");
-        return UMEREG_ELAUNCH;
-    }
-    return UMEREG_OK;
+    return icp_enqueue_download(mode, "icp_plane_enqueue", src, tgt, n_src, n_tgt, T_init_dev, max_correspondence_distance,
+                                max_iteration, relative_fitness, relative_rmse, first, iterations, state_host, workspace,
+                                workspace_bytes, stream);
 }
 
 UMEREG_API int umereg_icp_state_decode(const void* state_host, double* T_out_host, double* fitness_host, double* inlier_rmse_host,

@@ -1,4 +1,4 @@
-// infonce.hip -- the fused InfoNCE point-wise loss, forward and backward (csrc/infonce_api.h has the contract; the tile constants
+// infonce.hip -- the fused InfoNCE point-wise loss, forward and backward (include/umereg_infonce.h has the contract; the tile constants
 // and the workspace layout are csrc/infonce_plan.h).  No S x S tensor is formed and nothing is gathered into HBM: every kernel reads
 // the caller's [B, N, 32] / [B, M, 32] features and [B, N, 3] points through `matches`.
 //
@@ -25,7 +25,7 @@
 //   infonce_scatter_kernel  per-sample gradients -> dsrc / dtgt.  The lowest sample that names a row owns it and adds the samples
 //                           that name it in ascending order; the S row indices of a batch element are scanned from LDS.
 #include "common.h"
-#include "infonce_api.h"
+#include "umereg_infonce.h"
 #include "infonce_plan.h"
 
 namespace umereg {

@@ -8,7 +8,7 @@
 // One lane per point: a point is ~30 dependent gathers of 12 bytes (latency, not bandwidth), 120 000 points are 1 900 wavefronts --
 // enough to hide them; no LDS, no atomics, no cross-lane step, so the output is the same in every run.
 #include "grid.h"
-#include "icp_plane_api.h"
+#include "umereg_icp_plane.h"
 #include "icp_plane_math.h"
 
 namespace umereg {

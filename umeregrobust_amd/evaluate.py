@@ -371,7 +371,7 @@ def main(argv=None):
     parser.add_argument("--no-refine", action="store_true", help="skip the ICP refinement (evaluate.py:301)")
     parser.add_argument("--icp-estimation", choices=list(icp_plane.ESTIMATIONS), default="point_to_point",
                         help="estimation of the ICP refinement: the reference's point to point (default) or point to plane on target "
-                             "normals estimated on the device (csrc/icp_plane_api.h)")
+                             "normals estimated on the device (include/umereg_icp_plane.h)")
     parser.add_argument("--icp-normal-knn", type=int, default=icp_plane.DEFAULT_KNN,
                         help="with --icp-estimation point_to_plane: neighbours per target normal (3 .. 64)")
     parser.add_argument("--icp-normal-radius", type=float, default=None,

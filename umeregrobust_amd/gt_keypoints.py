@@ -1,5 +1,5 @@
 """Device-side selection of the ground-truth-driven keypoints: the engine behind
-`utils.loc_utils.generate_ume_from_keypoints2(..., selection="device")` on the HIP kernels of csrc/gt_keypoints_api.h.
+`utils.loc_utils.generate_ume_from_keypoints2(..., selection="device")` on the HIP kernels of include/umereg_gt_keypoints.h.
 
     cand, lengths = candidates(overlap_idx, non_flat)                      # descending index order, -1 padded; no sort
     kp_index, record = select(src_pts, cand, lengths, nn_r, max_nn, min_nn, num_samples)
@@ -8,26 +8,13 @@
 `select` answers "min(hits, max_nn) >= min_nn" lazily -- a ball's scan ends at its min_nn-th hit and candidates are only tested up
 to the one that completes num_samples dense ones -- where the default path forms the moment matrix of every candidate.  `record`
 (int32 [B, 2]: min(#dense, num_samples) and the candidate count per element) is the one thing the generator reads on the host.
-Every output is the same in every run; nothing here waits for the device.
-
-The entries are declared in csrc/gt_keypoints_api.h, not under include/, and typed here (GT_KEYPOINTS_SIGNATURES), not in
-`_lib.TABLES`."""
-import ctypes
-
+Every output is the same in every run; nothing here waits for the device."""
 import torch
 
 from . import _lib, ops
 
-c_void_p, c_int, c_float, c_size_t = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
-
-# name -> (restype, argtypes); mirrors csrc/gt_keypoints_api.h one to one
-GT_KEYPOINTS_SIGNATURES = {
-    "umereg_gt_keypoints_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "umereg_gt_candidates": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "umereg_gt_select_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
-                                     c_void_p, c_void_p, c_size_t, c_void_p]),
-    "umereg_gt_ball_any_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_float, c_int, c_void_p, c_void_p]),
-}
+GT_KEYPOINTS_SIGNATURES = _lib.TABLES["umereg_gt_keypoints.h"]
+load_native = _lib.load
 
 SELECTIONS = ("torch", "device")
 MAX_B = 1024                # UMEREG_GT_KEYPOINTS_MAX_B
@@ -41,10 +28,6 @@ def check_selection(who, selection):
     """ValueError for anything but "torch" / "device"; touches no tensor and no library."""
     if selection not in SELECTIONS:
         raise ValueError(f"{who}: selection must be 'torch' or 'device', got {selection!r}")
-
-
-def load_native():
-    return _lib.load_typed(GT_KEYPOINTS_SIGNATURES)
 
 
 def workspace_bytes(B, N):
@@ -106,14 +89,13 @@ def select(pts, cand, lengths, radius, max_nn, min_nn, num_samples, fma=False, w
     dev = pts.device
     pts, cand, lengths = pts.contiguous(), cand.contiguous(), lengths.contiguous()
     workspace = _workspace(lib, dev, B, N, workspace)
-    base = _lib.load()
-    packed = ops._workspace(dev, base.umereg_ume_moments_workspace_bytes(B, N), "mom")
+    packed = ops._workspace(dev, lib.umereg_ume_moments_workspace_bytes(B, N), "mom")
     kp_index = torch.empty(B, num_samples, dtype=torch.int64, device=dev)
     record = torch.empty(B, RECORD_WORDS, dtype=torch.int32, device=dev)
     tested = torch.empty(B, dtype=torch.int32, device=dev) if return_tested else None
     with torch.cuda.device(dev):
         st = _lib.stream_ptr(dev)
-        _lib.checked(base.umereg_pack_points_f32, pts.data_ptr(), B, N, float(radius), packed.data_ptr(), packed.numel(), st)
+        _lib.checked(lib.umereg_pack_points_f32, pts.data_ptr(), B, N, float(radius), packed.data_ptr(), packed.numel(), st)
         _lib.checked(lib.umereg_gt_select_f32, packed.data_ptr(), cand.data_ptr(), lengths.data_ptr(), B, N, float(radius), int(max_nn),
                      int(min_nn), num_samples, ops.BALL_FMA if fma else 0, kp_index.data_ptr(), record.data_ptr(), _lib.ptr(tested),
                      workspace.data_ptr(), workspace.numel(), st)

@@ -1,5 +1,5 @@
 """The point-wise InfoNCE loss of the reference (loss.py:19-46) as one differentiable op on the fused HIP kernels of
-csrc/infonce_api.h: what `pw_loss.MyInfoNCELossNoSeg` is made of.
+include/umereg_infonce.h: what `pw_loss.MyInfoNCELossNoSeg` is made of.
 
     loss = infonce_loss(src_feat, src_pts, tgt_feat, matches, tau, neg_euclid_dist)      # scalar; gradient to the two feature tensors
 
@@ -7,31 +7,16 @@ src_feat f32 [B, N, 32], src_pts f32 [B, N, 3], tgt_feat f32 [B, M, 32], matches
 sample (`row_stats`: the row's log-sum-exp and its cosine similarity); the backward recomputes every weight from them.  No S x S
 tensor exists at any time, nothing is gathered into a copy, and both passes are deterministic bit for bit, run on the current stream
 and never wait for the device.  The row sum runs under a running maximum, so logits / tau above 88 -- where the torch form returns
-inf / inf = NaN -- give a finite loss.  A `matches` entry out of range is not read through: the loss is NaN.
-
-The entries are declared in csrc/infonce_api.h, not under include/, and typed here (INFONCE_SIGNATURES), not in `_lib.TABLES`."""
-import ctypes
-
+inf / inf = NaN -- give a finite loss.  A `matches` entry out of range is not read through: the loss is NaN."""
 import torch
 
 from . import _lib
 
-c_void_p, c_int, c_float, c_size_t = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
-
-_COMMON = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float]
-# name -> (restype, argtypes); mirrors csrc/infonce_api.h one to one
-INFONCE_SIGNATURES = {
-    "umereg_infonce_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "umereg_infonce_fwd_f32": (c_int, _COMMON + [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "umereg_infonce_bwd_f32": (c_int, _COMMON + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-}
+INFONCE_SIGNATURES = _lib.TABLES["umereg_infonce.h"]
+load_native = _lib.load
 
 D = 32              # UMEREG_INFONCE_D
 MAX_S = 8192        # UMEREG_INFONCE_MAX_S
-
-
-def load_native():
-    return _lib.load_typed(INFONCE_SIGNATURES)
 
 
 def _inputs(who, src_feat, src_pts, tgt_feat, matches):

@@ -592,33 +592,51 @@ def icp_point_to_point(src_pts, tgt_pts, T_init, max_correspondence_distance=0.2
     SimpleNamespace(transformation float64 [4,4] numpy, fitness, inlier_rmse, iterations).
     A T_init that is a contiguous float32 DEVICE tensor is not read back: the first kernel reads it when it runs, so the chain is
     enqueued behind whatever is still computing it (the hypothesis selection)."""
+    return _icp_sync("icp_point_to_point", src_pts, tgt_pts, (), T_init, max_correspondence_distance, max_iteration, relative_fitness,
+                     relative_rmse)
+
+
+def _icp_entries(lib, plane):
+    """(size query, synchronous entry from a host start, the same from a device start, enqueue-only entry) of an estimation; the
+    point-to-plane entries take the target's normals as one more pointer behind the two clouds"""
+    if plane:
+        return (lib.umereg_icp_plane_workspace_bytes, lib.umereg_icp_point_to_plane_f32, lib.umereg_icp_point_to_plane_dev_f32,
+                lib.umereg_icp_plane_enqueue_f32)
+    return lib.umereg_icp_workspace_bytes, lib.umereg_icp_point_to_point_f32, lib.umereg_icp_point_to_point_dev_f32, lib.umereg_icp_enqueue_f32
+
+
+def _icp_sync(who, src_pts, tgt_pts, normals, T_init, max_correspondence_distance, max_iteration, relative_fitness, relative_rmse):
+    """The synchronous call behind icp_point_to_point (`normals` = ()) and icp_point_to_plane (`normals` = (tgt_normals,)); `who` is
+    the caller's name in every error."""
     import numpy as np
     from types import SimpleNamespace
     lib = _lib.load()
     sp = _dev(src_pts, "src_pts"); tp = _dev(tgt_pts, "tgt_pts")
     if sp.dim() != 2 or tp.dim() != 2 or sp.shape[1] != 3 or tp.shape[1] != 3:
-        raise ValueError(f"icp_point_to_point: expected [n,3] clouds, got {tuple(sp.shape)}, {tuple(tp.shape)}")
+        raise ValueError(f"{who}: expected [n,3] clouds, got {tuple(sp.shape)}, {tuple(tp.shape)}")
+    nrm = [_normals_arg(who, t, tp) for t in normals]
     if not isinstance(T_init, torch.Tensor):
         T_init = np.asarray(T_init)
     on_dev = isinstance(T_init, torch.Tensor) and T_init.is_cuda and T_init.dtype == torch.float32 and T_init.is_contiguous() \
         and T_init.device == sp.device
     if tuple(T_init.shape) != (4, 4):
-        raise ValueError("icp_point_to_point: T_init must be 4x4")
+        raise ValueError(f"{who}: T_init must be 4x4")
     T0 = None if on_dev else np.ascontiguousarray(np.asarray(T_init.detach().cpu() if isinstance(T_init, torch.Tensor) else T_init,
                                                              dtype=np.float64))
     n, m = sp.shape[0], tp.shape[0]
     if n == 0 or m == 0:
-        raise ValueError("icp_point_to_point: empty cloud")
+        raise ValueError(f"{who}: empty cloud")
     dev = sp.device
     T = np.empty((4, 4), dtype=np.float64)
     out = np.zeros(2, dtype=np.float64)
     iters = np.zeros(1, dtype=np.int32)
+    size, from_host, from_dev, _ = _icp_entries(lib, bool(nrm))
     # (a workspace of its own: an IcpJob in flight on this stream keeps its search grid in "icp" / "icpN" across result())
-    ws = _workspace(dev, lib.umereg_icp_workspace_bytes(n, m), "icp_sync")
-    fn = lib.umereg_icp_point_to_point_dev_f32 if on_dev else lib.umereg_icp_point_to_point_f32
-    _lib.call(dev, fn, _ptr(sp), _ptr(tp), n, m, T_init.data_ptr() if on_dev else T0.ctypes.data, float(max_correspondence_distance),
-              int(max_iteration), float(relative_fitness), float(relative_rmse), T.ctypes.data, out.ctypes.data, out.ctypes.data + 8,
-              iters.ctypes.data, _ptr(ws), ws.numel(), _stream_ptr(dev))
+    ws = _workspace(dev, size(n, m), "icp_sync")
+    _lib.call(dev, from_dev if on_dev else from_host, _ptr(sp), _ptr(tp), *map(_ptr, nrm), n, m,
+              T_init.data_ptr() if on_dev else T0.ctypes.data, float(max_correspondence_distance), int(max_iteration),
+              float(relative_fitness), float(relative_rmse), T.ctypes.data, out.ctypes.data, out.ctypes.data + 8, iters.ctypes.data,
+              _ptr(ws), ws.numel(), _stream_ptr(dev))
     return SimpleNamespace(transformation=T, fitness=float(out[0]), inlier_rmse=float(out[1]), iterations=int(iters[0]))
 
 
@@ -643,7 +661,7 @@ def estimate_normals(pts, knn=30, radius=None):
     knn = icp_plane.check_knn("estimate_normals", knn)
     if radius is not None and not float(radius) > 0.0:
         raise ValueError(f"estimate_normals: radius must be positive or None, got {radius!r}")
-    lib = icp_plane.load_native()
+    lib = _lib.load()
     p = _dev(pts, "pts")
     if p.dim() != 2 or p.shape[1] != 3:
         raise ValueError(f"estimate_normals: expected an [n,3] cloud, got {tuple(p.shape)}")
@@ -666,35 +684,8 @@ def icp_point_to_plane(src_pts, tgt_pts, tgt_normals, T_init, max_correspondence
     icp_point_to_point.  One documented deviation from open3d: the 6x6 normal equations are solved through their eigen-decomposition
     with eigenvalues <= 1e-12 lambda_max treated as zero (open3d: LDLT) -- a single wall or a ground plane gives a finite update
     that leaves the unconstrained directions alone; full-rank systems get the same solution."""
-    import numpy as np
-    from types import SimpleNamespace
-    from . import icp_plane
-    sp = _dev(src_pts, "src_pts"); tp = _dev(tgt_pts, "tgt_pts")
-    if sp.dim() != 2 or tp.dim() != 2 or sp.shape[1] != 3 or tp.shape[1] != 3:
-        raise ValueError(f"icp_point_to_plane: expected [n,3] clouds, got {tuple(sp.shape)}, {tuple(tp.shape)}")
-    nrm = _normals_arg("icp_point_to_plane", tgt_normals, tp)
-    lib = icp_plane.load_native()
-    if not isinstance(T_init, torch.Tensor):
-        T_init = np.asarray(T_init)
-    on_dev = isinstance(T_init, torch.Tensor) and T_init.is_cuda and T_init.dtype == torch.float32 and T_init.is_contiguous() \
-        and T_init.device == sp.device
-    if tuple(T_init.shape) != (4, 4):
-        raise ValueError("icp_point_to_plane: T_init must be 4x4")
-    T0 = None if on_dev else np.ascontiguousarray(np.asarray(T_init.detach().cpu() if isinstance(T_init, torch.Tensor) else T_init,
-                                                             dtype=np.float64))
-    n, m = sp.shape[0], tp.shape[0]
-    if n == 0 or m == 0:
-        raise ValueError("icp_point_to_plane: empty cloud")
-    dev = sp.device
-    T = np.empty((4, 4), dtype=np.float64)
-    out = np.zeros(2, dtype=np.float64)
-    iters = np.zeros(1, dtype=np.int32)
-    ws = _workspace(dev, lib.umereg_icp_plane_workspace_bytes(n, m), "icp_sync")
-    fn = lib.umereg_icp_point_to_plane_dev_f32 if on_dev else lib.umereg_icp_point_to_plane_f32
-    _lib.call(dev, fn, _ptr(sp), _ptr(tp), _ptr(nrm), n, m, T_init.data_ptr() if on_dev else T0.ctypes.data,
-              float(max_correspondence_distance), int(max_iteration), float(relative_fitness), float(relative_rmse), T.ctypes.data,
-              out.ctypes.data, out.ctypes.data + 8, iters.ctypes.data, _ptr(ws), ws.numel(), _stream_ptr(dev))
-    return SimpleNamespace(transformation=T, fitness=float(out[0]), inlier_rmse=float(out[1]), iterations=int(iters[0]))
+    return _icp_sync("icp_point_to_plane", src_pts, tgt_pts, (tgt_normals,), T_init, max_correspondence_distance, max_iteration,
+                     relative_fitness, relative_rmse)
 
 
 _icp_pinned = []      # pinned state buffers of finished IcpJobs, for reuse (a pinned allocation costs more than an ICP evaluation)
@@ -717,10 +708,8 @@ class IcpJob:
         self.sp = _dev(src_pts, "src_pts"); self.tp = _dev(tgt_pts, "tgt_pts")
         if self.sp.dim() != 2 or self.tp.dim() != 2 or self.sp.shape[1] != 3 or self.tp.shape[1] != 3:
             raise ValueError(f"IcpJob: expected [n,3] clouds, got {tuple(self.sp.shape)}, {tuple(self.tp.shape)}")
-        self.nrm = None if tgt_normals is None else _normals_arg("IcpJob", tgt_normals, self.tp)
-        if self.nrm is not None:
-            from . import icp_plane
-            lib = icp_plane.load_native()
+        self.nrm = [] if tgt_normals is None else [_normals_arg("IcpJob", tgt_normals, self.tp)]
+        size, _, _, self.entry = _icp_entries(lib, bool(self.nrm))
         if not (isinstance(T_init_dev, torch.Tensor) and T_init_dev.is_cuda and T_init_dev.dtype == torch.float32
                 and T_init_dev.is_contiguous() and tuple(T_init_dev.shape) == (4, 4) and T_init_dev.device == self.sp.device):
             raise ValueError("IcpJob: T_init_dev must be a contiguous float32 [4,4] tensor on the clouds' device")
@@ -738,8 +727,7 @@ class IcpJob:
         self.state = None
         self._res = None
         try:
-            need = lib.umereg_icp_workspace_bytes(n, m) if self.nrm is None else lib.umereg_icp_plane_workspace_bytes(n, m)
-            self.ws = _workspace(dev, need, "icp" if self.slot == 0 else f"icp{self.slot}")
+            self.ws = _workspace(dev, size(n, m), "icp" if self.slot == 0 else f"icp{self.slot}")
             self.state = _icp_pinned.pop() if _icp_pinned else torch.empty(int(lib.umereg_icp_state_bytes()), dtype=torch.uint8, pin_memory=True)
             self.event = torch.cuda.Event()
             self.launched = 0
@@ -776,16 +764,9 @@ class IcpJob:
             pass
 
     def _enqueue(self, first, iterations):
-        lib = _lib.load()
-        d, it, rf, rr = self.par
-        if self.nrm is None:
-            _lib.call(self.dev, lib.umereg_icp_enqueue_f32, _ptr(self.sp), _ptr(self.tp), self.sp.shape[0], self.tp.shape[0], _ptr(self.T0), d,
-                      it, rf, rr, 1 if first else 0, int(iterations), self.state.data_ptr(), _ptr(self.ws), self.ws.numel(),
-                      self.stream.cuda_stream)
-        else:
-            _lib.call(self.dev, lib.umereg_icp_plane_enqueue_f32, _ptr(self.sp), _ptr(self.tp), _ptr(self.nrm), self.sp.shape[0],
-                      self.tp.shape[0], _ptr(self.T0), d, it, rf, rr, 1 if first else 0, int(iterations), self.state.data_ptr(),
-                      _ptr(self.ws), self.ws.numel(), self.stream.cuda_stream)
+        _lib.call(self.dev, self.entry, _ptr(self.sp), _ptr(self.tp), *map(_ptr, self.nrm), self.sp.shape[0], self.tp.shape[0],
+                  _ptr(self.T0), *self.par, 1 if first else 0, int(iterations), self.state.data_ptr(), _ptr(self.ws), self.ws.numel(),
+                  self.stream.cuda_stream)
         self.launched += iterations
         self.event.record(self.stream)
 

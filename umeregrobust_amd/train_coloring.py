@@ -37,7 +37,7 @@ is computed, the order in which the host RNG is consumed and everything that is 
 by side instead of one after another by scipy on the host.  Off by default.
 
 `--fused-pointwise` (`run(..., fused_pointwise=True)`) computes the point-wise term with `pw_loss.MyInfoNCELossNoSeg`: one fused HIP
-forward and backward (csrc/infonce_api.h) instead of the torch statements of `loss.MyInfoNCELossNoSeg`.  Off by default."""
+forward and backward (include/umereg_infonce.h) instead of the torch statements of `loss.MyInfoNCELossNoSeg`.  Off by default."""
 import argparse
 import json
 import os
@@ -446,10 +446,10 @@ def run(args, synthetic=0, synthetic_points=3000, summary_writer=None, out_path=
     fused_norm: batch norm, residual and ReLU of the layer-wise path on the kernels of include/umereg_bn_act.h (models.py; the same
     parameters and checkpoint keys).
     conv_mode: "union", or "pairs" for the pair-compacted engine of the 27-offset convolutions (models.py; the same values bit for bit).
-    fused_pointwise: the point-wise loss is `pw_loss.MyInfoNCELossNoSeg`, the fused HIP forward and backward of csrc/infonce_api.h, in
+    fused_pointwise: the point-wise loss is `pw_loss.MyInfoNCELossNoSeg`, the fused HIP forward and backward of include/umereg_infonce.h, in
     place of the torch statements of `loss.MyInfoNCELossNoSeg` (same constructor and call; values agree to fp32 rounding).
     device_keypoints: the ground-truth-driven keypoints of the UME loss and of the validation inlier ratio are selected on the device
-    (`generate_ume_from_keypoints2(..., selection="device")`, csrc/gt_keypoints_api.h; the same keypoints and values bit for bit)."""
+    (`generate_ume_from_keypoints2(..., selection="device")`, include/umereg_gt_keypoints.h; the same keypoints and values bit for bit)."""
     torch.manual_seed(args.random_seed)
     np.random.seed(args.random_seed)
     device = torch.device(args.device)
