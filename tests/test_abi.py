@@ -274,6 +274,41 @@ def test_corr_kernels_are_launched_where_they_are_defined():
     assert "hipLaunchKernelGGL" not in open(os.path.join(csrc, "corr.hip")).read()
 
 
+def test_corr_bit_contracts_are_stated_once():
+    """Three bit-level contracts of hypothesis selection have ONE statement each, in corr_dev.h: the image of a source point
+    under a hypothesis (hyp_image: the nested-fmaf row form, by pointer rows and by float4 rows), the score of one query from the keys
+    coop_knn leaves in LDS (coop_score: the only caller of cauchy_weight_hw) and the bounded mode's slack rule (bound_eps, slack_units,
+    slack_publish, slack_value: the slack unit and the sticky saturation bit).  A restated copy that drifts by one operand does not crash;
+    a query lands in a lattice cell nobody marked, or a bound under-counts.  Read as text: no corr* source but corr_dev.h spells them."""
+    csrc = os.path.join(REPO, "umeregrobust_amd", "csrc")
+    forms = {"image, pointer rows": r"fmaf\(\s*\w+\[2\]\s*,[^;]*?fmaf\(\s*\w+\[1\]\s*,[^;]*?\w+\[0\]\s*\*",
+             "image, float4 rows": r"fmaf\(\s*(\w+)\.z\s*,[^;]*?fmaf\(\s*\1\.y\s*,[^;]*?\1\.x\s*\*",
+             "cauchy_weight_hw(": r"\bcauchy_weight_hw\s*\(",
+             "kSlackUnit": r"\bkSlackUnit\b",
+             "1ull << 63": r"\b1ull\s*<<\s*63\b"}
+    # Sites left inline, {(file, form): occurrences}, each with its reason:
+    allowed = {
+        # the single-lane bound of corr_score_flat_kernel<3> (one query, lane 0, direct atomics): with slack_units (and with bound_eps) in
+        # place of its two lines the kernel's instruction schedule changed, which the refactor that introduced the helpers did not accept
+        ("corr_leftover.hip", "kSlackUnit"): 1,
+    }
+    files = sorted(f for f in os.listdir(csrc) if f.startswith("corr") and f.endswith((".hip", ".h")))
+    assert {"corr.hip", "corr_dev.h", "corr_host.h", "corr_knn.hip", "corr_consensus.hip", "corr_lattice.hip", "corr_leftover.hip"} <= set(files)
+    dev = open(os.path.join(csrc, "corr_dev.h")).read()
+    for name, pat in forms.items():
+        assert re.search(pat, dev), f"corr_dev.h no longer states: {name}"
+    seen = {}
+    for f in files:
+        if f == "corr_dev.h":
+            continue
+        text = open(os.path.join(csrc, f)).read()
+        for name, pat in forms.items():
+            n = len(re.findall(pat, text))
+            if n:
+                seen[(f, name)] = n
+    assert seen == allowed, f"restated outside corr_dev.h (or a stale exception): {seen}"
+
+
 def test_match_kernels_are_launched_where_they_are_defined():
     """The matcher sources are four translation units over match_dev.h: each of the eight kernels is DEFINED in exactly
     one of them and LAUNCHED only from that unit -- no kernel is declared across units; the units call each other through the

@@ -236,16 +236,12 @@ __global__ __launch_bounds__(1024) void hyp_order_chunk_kernel(const float* __re
     int n2 = 64;
     while (n2 < M) n2 <<= 1;
     const float4 c = centroid[chunk];
-    const float mx = fmaf(Tmed[2], c.z, fmaf(Tmed[1], c.y, Tmed[0] * c.x)) + Tmed[3];
-    const float my = fmaf(Tmed[6], c.z, fmaf(Tmed[5], c.y, Tmed[4] * c.x)) + Tmed[7];
-    const float mz = fmaf(Tmed[10], c.z, fmaf(Tmed[9], c.y, Tmed[8] * c.x)) + Tmed[11];
+    const HypImage m = hyp_image(Tmed, c.x, c.y, c.z);
     for (int h = threadIdx.x; h < n2; h += blockDim.x) {
         unsigned int k = 0xffffffffu;
         if (h < M) {
-            const float* Th = T + (size_t)h * 16;
-            const float ex = fmaf(Th[2], c.z, fmaf(Th[1], c.y, Th[0] * c.x)) + Th[3] - mx;
-            const float ey = fmaf(Th[6], c.z, fmaf(Th[5], c.y, Th[4] * c.x)) + Th[7] - my;
-            const float ez = fmaf(Th[10], c.z, fmaf(Th[9], c.y, Th[8] * c.x)) + Th[11] - mz;
+            const HypImage q = hyp_image(T + (size_t)h * 16, c.x, c.y, c.z);
+            const float ex = q.x - m.x, ey = q.y - m.y, ez = q.z - m.z;
             const float d2 = ex * ex + ey * ey + ez * ez;
             // NaN / inf transforms last (before the padding): 0x7f800 in the upper 19 bits; finite d2 >= 0 orders as its bits
             const unsigned int b = d2 == d2 && d2 < 3.0e38f ? __float_as_uint(d2) >> 13 : 0x3fc00u;
@@ -326,9 +322,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     const Grid& g = c.g;
     const int n_words = (M + 63) >> 6;
     const float px = src_pts[(size_t)n * 3], py = src_pts[(size_t)n * 3 + 1], pz = src_pts[(size_t)n * 3 + 2];
-    const float cx = fmaf(Tmed[2], pz, fmaf(Tmed[1], py, Tmed[0] * px)) + Tmed[3];
-    const float cy = fmaf(Tmed[6], pz, fmaf(Tmed[5], py, Tmed[4] * px)) + Tmed[7];
-    const float cz = fmaf(Tmed[10], pz, fmaf(Tmed[9], py, Tmed[8] * px)) + Tmed[11];
+    const HypImage ci = hyp_image(Tmed, px, py, pz);
+    const float cx = ci.x, cy = ci.y, cz = ci.z;
     auto give_up = [&]() __attribute__((always_inline)) {
         for (int h = lane; h < M; h += kWave) val[(size_t)n * M + h] = 0.f;
         for (int w = lane; w < n_words; w += kWave) served[(size_t)n * n_words + w] = 0ull;
@@ -439,9 +434,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
         const int h = perm[pos_h < M ? pos_h : 0];
         const float4* Th = reinterpret_cast<const float4*>(T + (size_t)h * 16);    // (T is 16-byte aligned: checked by the host)
         const float4 r0 = Th[0], r1 = Th[1], r2 = Th[2];
-        const float qx = fmaf(r0.z, pz, fmaf(r0.y, py, r0.x * px)) + r0.w;               // the arithmetic of corr_score_kernel
-        const float qy = fmaf(r1.z, pz, fmaf(r1.y, py, r1.x * px)) + r1.w;
-        const float qz = fmaf(r2.z, pz, fmaf(r2.y, py, r2.x * px)) + r2.w;
+        const HypImage q = hyp_image(r0, r1, r2, px, py, pz);
+        const float qx = q.x, qy = q.y, qz = q.z;
         const float ex = qx - cx, ey = qy - cy, ez = qz - cz;
         const float delta = sqrtf(ex * ex + ey * ey + ez * ez) * 1.0001f + 1e-6f;
         // a lane can only pass the exactness test if d_K(q) + delta <= D, and d_K(q) >= d_K(q~) - delta
@@ -719,9 +713,8 @@ __device__ __forceinline__ void cons2_point(
     const Grid& g = c.g;
     const int n_words = (M + 63) >> 6;
     const float px = src_pts[(size_t)n * 3], py = src_pts[(size_t)n * 3 + 1], pz = src_pts[(size_t)n * 3 + 2];
-    const float cx = fmaf(Tmed[2], pz, fmaf(Tmed[1], py, Tmed[0] * px)) + Tmed[3];
-    const float cy = fmaf(Tmed[6], pz, fmaf(Tmed[5], py, Tmed[4] * px)) + Tmed[7];
-    const float cz = fmaf(Tmed[10], pz, fmaf(Tmed[9], py, Tmed[8] * px)) + Tmed[11];
+    const HypImage ci = hyp_image(Tmed, px, py, pz);
+    const float cx = ci.x, cy = ci.y, cz = ci.z;
     auto give_up = [&]() __attribute__((always_inline)) {
         for (int h = lane; h < M; h += kWave) val[(size_t)n * M + h] = 0.f;
         for (int w = lane; w < n_words; w += kWave) served[(size_t)n * n_words + w] = 0ull;
@@ -899,9 +892,8 @@ __device__ __forceinline__ void cons2_point(
         const int h = perm[pos_h < M ? pos_h : 0];
         const float4* Th = reinterpret_cast<const float4*>(T + (size_t)h * 16);    // (T is 16-byte aligned: checked by the host)
         const float4 r0 = Th[0], r1 = Th[1], r2 = Th[2];
-        const float qx = fmaf(r0.z, pz, fmaf(r0.y, py, r0.x * px)) + r0.w;               // the arithmetic of corr_score_kernel
-        const float qy = fmaf(r1.z, pz, fmaf(r1.y, py, r1.x * px)) + r1.w;
-        const float qz = fmaf(r2.z, pz, fmaf(r2.y, py, r2.x * px)) + r2.w;
+        const HypImage q = hyp_image(r0, r1, r2, px, py, pz);
+        const float qx = q.x, qy = q.y, qz = q.z;
         const float ex = qx - cx, ey = qy - cy, ez = qz - cz;
         const float delta = __builtin_amdgcn_sqrtf(ex * ex + ey * ey + ez * ez) * 1.0001f + 1e-6f;   // (1 ulp: inside the slack)
         // a lane can only pass the exactness test if d_K(q) + delta <= D, and d_K(q) >= d_K(q~) - delta

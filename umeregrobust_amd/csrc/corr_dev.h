@@ -594,13 +594,84 @@ __device__ __forceinline__ float cauchy_weight_fast(float d2, float inv_sigma2)
     return __builtin_amdgcn_rcpf(fmaf(d2, inv_sigma2, 1.0f));
 }
 
+// The image of a source point under a hypothesis: rows 0..2 of the row-major 4x4 T (or the three rows as float4).  EVERY kernel that
+// maps a query to a lattice cell, records it, scores it or bounds it forms the image HERE, so that all of them see the same bits: a
+// query must find its own cell marked, and a bound must be taken at the point the search would have scored.  The form -- one product,
+// two FMAs, then the translation added -- is fixed: the golden test test_corr_images_fma_form_is_correctly_rounded holds it to exact fmaf.
+struct HypImage { float x, y, z; };
+__device__ __forceinline__ HypImage hyp_image(const float* Th, float x, float y, float z)
+{
+    return {fmaf(Th[2], z, fmaf(Th[1], y, Th[0] * x)) + Th[3],
+            fmaf(Th[6], z, fmaf(Th[5], y, Th[4] * x)) + Th[7],
+            fmaf(Th[10], z, fmaf(Th[9], y, Th[8] * x)) + Th[11]};
+}
+__device__ __forceinline__ HypImage hyp_image(const float4& r0, const float4& r1, const float4& r2, float x, float y, float z)
+{
+    return {fmaf(r0.z, z, fmaf(r0.y, y, r0.x * x)) + r0.w,
+            fmaf(r1.z, z, fmaf(r1.y, y, r1.x * x)) + r1.w,
+            fmaf(r2.z, z, fmaf(r2.y, y, r2.x * x)) + r2.w};
+}
+// The score of ONE query from the K keys ((bits(d2) << 32) | index, cnt of them) that coop_knn left in LDS, by the whole wavefront:
+// 8 neighbours per round (grp = lane >> 3), 8 lanes per 128-byte feature row (sub = lane & 7), the last round's empty slots add 0.
+// Returns the sum over the wavefront, the same in every lane.  Every one-wavefront-per-query kernel scores HERE, so that a query
+// is worth the same bits whichever of them serves it (the routes are compared for equality).
+__device__ __forceinline__ float coop_score(const unsigned long long* keys, int cnt, const float4* __restrict__ vp4, const float4* __restrict__ vq4,
+                                            int qs, float inv_sigma, int grp, int sub)
+{
+    const float4 a = vp4[(size_t)qs * 8 + sub];
+    float part = 0.f;
+    for (int e0 = 0; e0 < cnt; e0 += 8) {
+        const int e = e0 + grp;
+        const unsigned long long k = keys[e < cnt ? e : 0];
+        const float wgt = cauchy_weight_hw(__uint_as_float((unsigned int)(k >> 32)), inv_sigma);   // :593, :588-589
+        const float4 o = vq4[(size_t)(unsigned int)(k & 0xffffffffull) * 8 + sub];
+        float d = a.x * o.x;
+        d = fmaf(a.y, o.y, d); d = fmaf(a.z, o.z, d); d = fmaf(a.w, o.w, d);
+        part += e < cnt ? wgt * d : 0.f;
+    }
+    return wave_sum_f(part);
+}
+// ---- the slack rule of the bounded (arg-max) mode, UMEREG_CORR_BOUND_OUTSIDE (see flat_bound_kernel) ------------------------------
+// A query that is bounded instead of searched adds, to the slack word of its hypothesis, the most its K terms can be worth:
+// K w(d_low) |vp_n| max_j |vq_j| for a lower bound d_low of every neighbour's distance, rounded up (the two guard factors).
+__device__ __forceinline__ float bound_eps(int K, float d_low, float inv_sigma, float vpn_n, float vq_max)
+{
+    const float r = d_low * inv_sigma * 0.9999f;
+    return (float)K * (1.0f / (1.0f + r * r)) * vpn_n * vq_max * 1.0001f;
+}
+constexpr float kSlackUnit = 1.0f / 16777216.0f;     // 2^-24: a slack word counts these (rounded up per query)
+constexpr unsigned long long kSlackSat = 1ull << 63;
+// A bound in slack units.  An infinite, NaN or absurdly large bound -- NaN features -- is `sat`: it adds nothing and sets the sticky
+// top bit of the word instead (atomicOr), and the hypothesis then needs its queries whatever the scores.  Finite terms are < 2^34
+// each, so even 2^20 of them cannot carry into that bit, and any number of saturated queries leaves it set -- an added 2^62 per
+// query wrapped to 0 at the fourth.
+__device__ __forceinline__ unsigned long long slack_units(float eps, bool& sat)
+{
+    sat = !(eps < 1.0e3f);
+    return sat ? 0ull : (unsigned long long)(eps * (1.0f / kSlackUnit)) + 1ull;
+}
+// the wavefront's units (0 in the lanes that bound nothing) to slack[h]: one atomic per wavefront and hypothesis, not per query
+__device__ __forceinline__ void slack_publish(unsigned long long* __restrict__ slack, int h, unsigned long long fx, bool sat, int lane)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) fx += (unsigned long long)__shfl_xor((long long)fx, o, kWave);                 // (integers: any order)
+    const bool any_sat = __any(sat);
+    if (lane == 0) {
+        if (fx != 0ull) atomicAdd(&slack[h], fx);
+        if (any_sat) atomicOr(&slack[h], kSlackSat);
+    }
+}
+// what a hypothesis' slack word can move its score by (a mean over Ns source points): no bound at all once saturated
+__device__ __forceinline__ float slack_value(unsigned long long fx, int Ns)
+{
+    return (fx >> 63) ? 3.0e38f : (float)fx * kSlackUnit / (float)Ns;
+}
+
 // (per-neighbourhood hypothesis orders: corr_consensus.hip)
 constexpr int kChunkOrderMax = 8192;        // hypotheses a chunk order can sort in LDS (beyond: the global order for every chunk)
 
 constexpr int kCoopCap = 256;       // cooperative key list (keys)
 constexpr int kCoopWaves = 8;       // wavefronts per record
-// (the bounded mode, UMEREG_CORR_BOUND_OUTSIDE: see flat_bound_kernel)
-constexpr float kSlackUnit = 1.0f / 16777216.0f;     // 2^-24
 
 // keep the K smallest of list[0 .. cnt) (cnt <= SLOTS * 64 <= kCoopCap): out[rank] = key for rank < K.  Returns min(cnt, K).
 // Rank counting: keys are unique, so ranks are a permutation.  cnt * SLOTS compare-and-adds per lane.

@@ -127,12 +127,9 @@ __global__ __launch_bounds__(256) void lattice_mark_kernel(const char* __restric
     const float sx = src_pts[(size_t)n * 3], sy = src_pts[(size_t)n * 3 + 1], sz = src_pts[(size_t)n * 3 + 2];
     for (int h = h0; h < h1; ++h) {
         const float* Th = T + (size_t)h * 16;     // uniform: scalar loads
-        // (the same arithmetic as corr_score_kernel: a query must find its own cell marked)
-        const float qx = fmaf(Th[2], sz, fmaf(Th[1], sy, Th[0] * sx)) + Th[3];
-        const float qy = fmaf(Th[6], sz, fmaf(Th[5], sy, Th[4] * sx)) + Th[7];
-        const float qz = fmaf(Th[10], sz, fmaf(Th[9], sy, Th[8] * sx)) + Th[11];
+        const HypImage q = hyp_image(Th, sx, sy, sz);
         if (served) { const int ph = inv[(size_t)chunk_of[n] * M + h]; if ((served[(size_t)n * n_words + (ph >> 6)] >> (ph & 63)) & 1ull) continue; }   // done by the consensus pass
-        const int cell = lattice_cell(L, qx, qy, qz);
+        const int cell = lattice_cell(L, q.x, q.y, q.z);
         if (cell >= 0) {
             marks[cell] = 1;
             if (cell_cnt) atomicAdd(&cell_cnt[cell], 1u);       // (the cell pass's counting sort: see corr_cell_kernel)
@@ -181,12 +178,9 @@ __device__ __forceinline__ void for_each_unserved(const char* __restrict__ ws_sr
             const int h = perm_c[b];                                 // uniform
             if (only != nullptr && only[h] == 0u) continue;
             const float* Th = T + (size_t)h * 16;                    // uniform: scalar loads
-            // (the arithmetic of corr_score_kernel: the cell is the one every other kernel computes for this query)
-            const float qx = fmaf(Th[2], sz, fmaf(Th[1], sy, Th[0] * sx)) + Th[3];
-            const float qy = fmaf(Th[6], sz, fmaf(Th[5], sy, Th[4] * sx)) + Th[7];
-            const float qz = fmaf(Th[10], sz, fmaf(Th[9], sy, Th[8] * sx)) + Th[11];
-            if constexpr (kAll) f(mine, n, w * 64 + b, h, qx, qy, qz);
-            else if (mine) f(n, w * 64 + b, h, qx, qy, qz);
+            const HypImage q = hyp_image(Th, sx, sy, sz);
+            if constexpr (kAll) f(mine, n, w * 64 + b, h, q.x, q.y, q.z);
+            else if (mine) f(n, w * 64 + b, h, q.x, q.y, q.z);
         }
         word_end(slot < Ns, n, w);
     }
@@ -271,19 +265,10 @@ __global__ __launch_bounds__(256) void lattice_mark_order_kernel(const char* __r
                 unsigned long long fx = 0ull;
                 bool sat = false;
                 if (far) {
-                    const float r = d_low * inv_sigma * 0.9999f;
-                    const float eps = (float)K * (1.0f / (1.0f + r * r)) * vpn[n] * vq_max * 1.0001f;
-                    sat = !(eps < 1.0e3f);
-                    fx = sat ? 0ull : (unsigned long long)(eps * (1.0f / kSlackUnit)) + 1ull;
+                    fx = slack_units(bound_eps(K, d_low, inv_sigma, vpn[n], vq_max), sat);
                     far_bits |= 1ull << (pos & 63);
                 }
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) fx += (unsigned long long)__shfl_xor((long long)fx, o, kWave);                 // (integers: any order)
-                const bool any_sat = __any(sat);
-                if (lane == 0) {
-                    if (fx != 0ull) atomicAdd(&slack[h], fx);
-                    if (any_sat) atomicOr(&slack[h], 1ull << 63);
-                }
+                slack_publish(slack, h, fx, sat, lane);
             }
             if (cell >= 0 && !far) {
                 marks[cell] = 1;
@@ -774,17 +759,10 @@ __global__ __launch_bounds__(256) void cell_scatter_kernel(const char* __restric
             if (far) {
                 // (the most the weights of a query of this cell can add up to: cells[].z of a far cell, the wsum array for a near-far one)
                 const float eps = (near_far ? wsum_arr[cell] : __uint_as_float(ce.z)) * vpn[n] * vq_max * 1.0001f;
-                sat = !(eps < 1.0e3f);
-                fx = sat ? 0ull : (unsigned long long)(eps * (1.0f / kSlackUnit)) + 1ull;
+                fx = slack_units(eps, sat);
                 far_bits |= 1ull << (pos & 63);
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) fx += (unsigned long long)__shfl_xor((long long)fx, o, kWave);                 // (integers: any order)
-            const bool any_sat = __any(sat);
-            if (lane == 0) {
-                if (fx != 0ull) atomicAdd(&slack[h], fx);
-                if (any_sat) atomicOr(&slack[h], 1ull << 63);
-            }
+            slack_publish(slack, h, fx, sat, lane);
         }
         if (cell >= 0 && !far && cell_usable(ce)) {
             const unsigned int at = cw.cnt[cell] + atomicAdd(&cw.cur[cell], 1u);
@@ -878,23 +856,9 @@ __global__ __launch_bounds__(kCoopWaves * 64) __attribute__((amdgpu_waves_per_eu
                 const float py = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sy), l));
                 const float pz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(sz), l));
                 const int qs = __builtin_amdgcn_readlane(n, l);
-                // (the arithmetic of corr_score_kernel)
-                const float qx = fmaf(Th[2], pz, fmaf(Th[1], py, Th[0] * px)) + Th[3];
-                const float qy = fmaf(Th[6], pz, fmaf(Th[5], py, Th[4] * px)) + Th[7];
-                const float qz = fmaf(Th[10], pz, fmaf(Th[9], py, Th[8] * px)) + Th[11];
-                const int cnt = coop_knn(P4s, box, Nt, K, qx, qy, qz, la, lb, chist[wave], lane);
-                const float4 a = vp4[(size_t)qs * 8 + sub];
-                float part = 0.f;
-                for (int e0 = 0; e0 < cnt; e0 += 8) {
-                    const int e = e0 + grp;
-                    const unsigned long long k = la[e < cnt ? e : 0];
-                    const float wgt = cauchy_weight_hw(__uint_as_float((unsigned int)(k >> 32)), inv_sigma);   // :593, :588-589
-                    const float4 o = vq4[(size_t)(unsigned int)(k & 0xffffffffull) * 8 + sub];
-                    float d = a.x * o.x;
-                    d = fmaf(a.y, o.y, d); d = fmaf(a.z, o.z, d); d = fmaf(a.w, o.w, d);
-                    part += e < cnt ? wgt * d : 0.f;
-                }
-                part = wave_sum_f(part);
+                const HypImage q = hyp_image(Th, px, py, pz);
+                const int cnt = coop_knn(P4s, box, Nt, K, q.x, q.y, q.z, la, lb, chist[wave], lane);
+                const float part = coop_score(la, cnt, vp4, vq4, qs, inv_sigma, grp, sub);
                 if (lane == 0) val[(size_t)qs * M + (size_t)(w * 64 + b)] = part;
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             }
@@ -1060,9 +1024,8 @@ __global__ __launch_bounds__(64) void corr_cell_kernel(const char* __restrict__ 
             const float px = src_pts[(size_t)n * 3], py = src_pts[(size_t)n * 3 + 1], pz = src_pts[(size_t)n * 3 + 2];
             const float4* Th = reinterpret_cast<const float4*>(T + (size_t)eh.y * 16);
             const float4 r0 = Th[0], r1 = Th[1], r2 = Th[2];
-            const float qx = fmaf(r0.z, pz, fmaf(r0.y, py, r0.x * px)) + r0.w;               // the arithmetic of corr_score_kernel
-            const float qy = fmaf(r1.z, pz, fmaf(r1.y, py, r1.x * px)) + r1.w;
-            const float qz = fmaf(r2.z, pz, fmaf(r2.y, py, r2.x * px)) + r2.w;
+            const HypImage q = hyp_image(r0, r1, r2, px, py, pz);
+            const float qx = q.x, qy = q.y, qz = q.z;
             const float ex = qx - ccx, ey = qy - ccy, ez = qz - ccz;
             const float delta = __builtin_amdgcn_sqrtf(ex * ex + ey * ey + ez * ez) * 1.0001f + 1e-6f;
             const bool act = valid && delta <= L.hd * 1.01f + 1e-5f;                        // (in its cell: always; a guard for the bracket)

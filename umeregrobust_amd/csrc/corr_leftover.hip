@@ -141,9 +141,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         }
         const float* Th = T + (size_t)h * 16;
         // source_transformed = p R^T + t  (utils/loc_utils.py:629)
-        const float qx = fmaf(Th[2], sp.z, fmaf(Th[1], sp.y, Th[0] * sp.x)) + Th[3];
-        const float qy = fmaf(Th[6], sp.z, fmaf(Th[5], sp.y, Th[4] * sp.x)) + Th[7];
-        const float qz = fmaf(Th[10], sp.z, fmaf(Th[9], sp.y, Th[8] * sp.x)) + Th[11];
+        const HypImage q = hyp_image(Th, sp.x, sp.y, sp.z);
+        const float qx = q.x, qy = q.y, qz = q.z;
         int cnt;
         // queries the consensus pass has already scored are not this kernel's business
         const int ph = (served && !by_word) ? inv[(size_t)chunk * M + h] : 0;       // position of the hypothesis in the order of this chunk (consensus pass)
@@ -373,9 +372,7 @@ __global__ __launch_bounds__(kCoopWaves * 64) void corr_score_fallback_kernel(co
         const int sidx = __float_as_int(S4s[slot < Ns ? slot : 0].w);
         const float sx = src_pts[(size_t)sidx * 3], sy = src_pts[(size_t)sidx * 3 + 1], sz = src_pts[(size_t)sidx * 3 + 2];
         const float* Th = T + (size_t)h * 16;
-        const float lqx = fmaf(Th[2], sz, fmaf(Th[1], sy, Th[0] * sx)) + Th[3];
-        const float lqy = fmaf(Th[6], sz, fmaf(Th[5], sy, Th[4] * sx)) + Th[7];
-        const float lqz = fmaf(Th[10], sz, fmaf(Th[9], sy, Th[8] * sx)) + Th[11];
+        const HypImage lq = hyp_image(Th, sx, sy, sz);
         if (threadIdx.x < kWave) qval[threadIdx.x] = 0.f;
         __syncthreads();
         int rank_in_mask = 0;
@@ -383,22 +380,10 @@ __global__ __launch_bounds__(kCoopWaves * 64) void corr_score_fallback_kernel(co
             if ((rank_in_mask % kCoopWaves) != wave) continue;           // this wavefront's share of the record's queries
             const int ql = __ffsll((long long)todo) - 1;
             if (chunk * kWave + ql >= Ns) continue;
-            const float qx = __shfl(lqx, ql, kWave), qy = __shfl(lqy, ql, kWave), qz = __shfl(lqz, ql, kWave);
+            const float qx = __shfl(lq.x, ql, kWave), qy = __shfl(lq.y, ql, kWave), qz = __shfl(lq.z, ql, kWave);
             const int qs = __shfl(sidx, ql, kWave);
             const int cnt = coop_knn(P4s, box, Nt, K, qx, qy, qz, la, lb, chist[wave], lane);
-            // (3) score: 8 neighbours per round, 8 lanes per 128-byte feature row
-            const float4 a = vp4[(size_t)qs * 8 + sub];
-            float part = 0.f;
-            for (int e0 = 0; e0 < cnt; e0 += 8) {
-                const int e = e0 + grp;
-                const unsigned long long k = la[e < cnt ? e : 0];
-                const float wgt = cauchy_weight_hw(__uint_as_float((unsigned int)(k >> 32)), inv_sigma);   // :593, :588-589
-                const float4 o = vq4[(size_t)(unsigned int)(k & 0xffffffffull) * 8 + sub];
-                float d = a.x * o.x;
-                d = fmaf(a.y, o.y, d); d = fmaf(a.z, o.z, d); d = fmaf(a.w, o.w, d);
-                part += e < cnt ? wgt * d : 0.f;
-            }
-            part = wave_sum_f(part);
+            const float part = coop_score(la, cnt, vp4, vq4, qs, inv_sigma, grp, sub);      // (3) score
             if (lane == 0) qval[ql] = part;
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         }
@@ -540,10 +525,8 @@ __global__ __launch_bounds__(256) void flat_bound_kernel(const char* __restrict_
         const int qs_l = __float_as_int(S4s[in_cloud ? slot_l : 0].w);
         const float sx = src_pts[(size_t)qs_l * 3], sy = src_pts[(size_t)qs_l * 3 + 1], sz = src_pts[(size_t)qs_l * 3 + 2];
         const float* Th = T + (size_t)h_l * 16;
-        // (the same arithmetic as the record kernel and corr_score_kernel)
-        const float qx_l = fmaf(Th[2], sz, fmaf(Th[1], sy, Th[0] * sx)) + Th[3];
-        const float qy_l = fmaf(Th[6], sz, fmaf(Th[5], sy, Th[4] * sx)) + Th[7];
-        const float qz_l = fmaf(Th[10], sz, fmaf(Th[9], sy, Th[8] * sx)) + Th[11];
+        const HypImage q = hyp_image(Th, sx, sy, sz);
+        const float qx_l = q.x, qy_l = q.y, qz_l = q.z;
         // outside the lattice (NaN images are not: they go through the search as always)
         const bool outside = in_cloud && qx_l == qx_l && qy_l == qy_l && qz_l == qz_l && lattice_cell(Lt, qx_l, qy_l, qz_l) < 0;
         bool exact;
@@ -555,13 +538,7 @@ __global__ __launch_bounds__(256) void flat_bound_kernel(const char* __restrict_
                 const float dx = fmaxf(fmaxf(bmn[0] - qx_l, qx_l - bmx[0]), 0.f), dy = fmaxf(fmaxf(bmn[1] - qy_l, qy_l - bmx[1]), 0.f);
                 const float dz = fmaxf(fmaxf(bmn[2] - qz_l, qz_l - bmx[2]), 0.f);
                 const float dB = fmaxf(sqrtf(dx * dx + dy * dy + dz * dz) * 0.9999f - 1e-5f, 0.f);
-                const float r = dB * inv_sigma * 0.9999f;
-                const float eps = (float)K * (1.0f / (1.0f + r * r)) * vpn[qs_l] * vq_max * 1.0001f;
-                // (an infinite, NaN or absurdly large bound -- NaN features -- sets the sticky top bit: the hypothesis then needs its
-                // queries whatever the scores.  Finite terms are < 2^34 each, so even 2^20 of them cannot carry into that bit, and any
-                // number of saturated queries leaves it set -- an added 2^62 per query wrapped to 0 at the fourth.)
-                sat = !(eps < 1.0e3f);
-                fx = sat ? 0ull : (unsigned long long)(eps * (1.0f / kSlackUnit)) + 1ull;
+                fx = slack_units(bound_eps(K, dB, inv_sigma, vpn[qs_l], vq_max), sat);
             }
             // one atomic per (wavefront, hypothesis), not per query: the entries of a record -- one hypothesis -- are consecutive in the list,
             // and 30 M queries of a nuScenes-size pair on the slack words of 2 000 hypotheses serialised on those words (3 ms)
@@ -571,14 +548,7 @@ __global__ __launch_bounds__(256) void flat_bound_kernel(const char* __restrict_
                 const bool mine = outside && h_l == h0;
                 const unsigned long long m = __ballot(mine);
                 todo &= ~m;
-                unsigned long long part = mine ? fx : 0ull;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) part += (unsigned long long)__shfl_xor((long long)part, o, kWave);     // (integers: any order)
-                const bool any_sat = __any(mine && sat);
-                if (lane == 0) {
-                    if (part != 0ull) atomicAdd(&slack[h0], part);
-                    if (any_sat) atomicOr(&slack[h0], 1ull << 63);
-                }
+                slack_publish(slack, h0, mine ? fx : 0ull, mine && sat, lane);
             }
             if (valid) f.qfar[q_l] = 0;
         } else {
@@ -658,14 +628,11 @@ __global__ __launch_bounds__(kCoopWaves * 64) __attribute__((amdgpu_waves_per_eu
         const int qs_l = __float_as_int(S4s[in_cloud ? slot_l : 0].w);
         const float sx = src_pts[(size_t)qs_l * 3], sy = src_pts[(size_t)qs_l * 3 + 1], sz = src_pts[(size_t)qs_l * 3 + 2];
         const float* Th = T + (size_t)h_l * 16;
-        // (the same arithmetic as the record kernel and corr_score_kernel)
-        const float qx_l = fmaf(Th[2], sz, fmaf(Th[1], sy, Th[0] * sx)) + Th[3];
-        const float qy_l = fmaf(Th[6], sz, fmaf(Th[5], sy, Th[4] * sx)) + Th[7];
-        const float qz_l = fmaf(Th[10], sz, fmaf(Th[9], sy, Th[8] * sx)) + Th[11];
+        const HypImage q_im = hyp_image(Th, sx, sy, sz);
         const bool exact = in_cloud;
         if (valid && !exact) f.qval[q_l] = 0.f;
         static_assert(kFlatVisit == 4, "visit[][4]");
-        if (lane < (int)kFlatVisit) { visit[wave][lane] = make_float4(qx_l, qy_l, qz_l, __int_as_float(qs_l)); visit_h[wave][lane] = h_l; }
+        if (lane < (int)kFlatVisit) { visit[wave][lane] = make_float4(q_im.x, q_im.y, q_im.z, __int_as_float(qs_l)); visit_h[wave][lane] = h_l; }
         unsigned int todo = (unsigned int)__ballot(exact);
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         while (todo != 0u) {
@@ -686,26 +653,17 @@ __global__ __launch_bounds__(kCoopWaves * 64) __attribute__((amdgpu_waves_per_eu
                         const float r = dB * inv_sigma * 0.9999f;
                         const float eps = (float)K * (1.0f / (1.0f + r * r)) * vpn[qs] * __uint_as_float(*vq_max_bits) * 1.0001f;
                         const int h = visit_h[wave][l];
+                        // (bound_eps and slack_units, restated: one lane, one query, nothing to sum over the wavefront -- and through the
+                        // helpers this kernel's schedule came out different, which the refactor that introduced them did not accept)
                         if (eps < 1.0e3f) atomicAdd(&slack[h], (unsigned long long)(eps * (1.0f / kSlackUnit)) + 1ull);
-                        else atomicOr(&slack[h], 1ull << 63);
+                        else atomicOr(&slack[h], kSlackSat);
                         f.qval[q_far] = 0.f;
                         f.qfar[q_far] = 1;
                     }
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                     continue;
                 }
-                const float4 a = vp4[(size_t)qs * 8 + sub];
-                float part = 0.f;
-                for (int e0 = 0; e0 < c0; e0 += 8) {
-                    const int e = e0 + grp;
-                    const unsigned long long k = la[e < c0 ? e : 0];
-                    const float wgt = cauchy_weight_hw(__uint_as_float((unsigned int)(k >> 32)), inv_sigma);   // :593, :588-589
-                    const float4 o = vq4[(size_t)(unsigned int)(k & 0xffffffffull) * 8 + sub];
-                    float d = a.x * o.x;
-                    d = fmaf(a.y, o.y, d); d = fmaf(a.z, o.z, d); d = fmaf(a.w, o.w, d);
-                    part += e < c0 ? wgt * d : 0.f;
-                }
-                part = wave_sum_f(part);
+                const float part = coop_score(la, c0, vp4, vq4, qs, inv_sigma, grp, sub);
                 const unsigned int q_o = (unsigned int)__builtin_amdgcn_readlane((int)q_l, l);
                 if (lane == 0) f.qval[q_o] = part;
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -727,18 +685,7 @@ __global__ __launch_bounds__(kCoopWaves * 64) __attribute__((amdgpu_waves_per_eu
 #else
             const int cnt = coop_knn(P4s, box, Nt, K, qx, qy, qz, la, lb, chist[wave], lane);
 #endif
-            const float4 a = vp4[(size_t)qs * 8 + sub];
-            float part = 0.f;
-            for (int e0 = 0; e0 < cnt; e0 += 8) {
-                const int e = e0 + grp;
-                const unsigned long long k = la[e < cnt ? e : 0];
-                const float wgt = cauchy_weight_hw(__uint_as_float((unsigned int)(k >> 32)), inv_sigma);   // :593, :588-589
-                const float4 o = vq4[(size_t)(unsigned int)(k & 0xffffffffull) * 8 + sub];
-                float d = a.x * o.x;
-                d = fmaf(a.y, o.y, d); d = fmaf(a.z, o.z, d); d = fmaf(a.w, o.w, d);
-                part += e < cnt ? wgt * d : 0.f;
-            }
-            part = wave_sum_f(part);
+            const float part = coop_score(la, cnt, vp4, vq4, qs, inv_sigma, grp, sub);
             const unsigned int q_out = kMode == 3 ? (unsigned int)__builtin_amdgcn_readlane((int)q_l, l) : blk * kFlatVisit + (unsigned int)l;
             if (lane == 0) f.qval[q_out] = part;
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -770,8 +717,7 @@ __global__ __launch_bounds__(1024) void bound_survivors_kernel(const float* __re
     __shared__ unsigned int cnt[2];
     if (threadIdx.x < 2) cnt[threadIdx.x] = 0u;
     auto margin = [&](int h, float s) {
-        const unsigned long long fx = slack[h];
-        const float e = (fx >> 63) ? 3.0e38f : (float)fx * kSlackUnit / (float)Ns;
+        const float e = slack_value(slack[h], Ns);
         return e * 1.0001f + 4e-6f * (fabsf(s) + 1.0f);                 // + what the two roundings of a sum of <= Ns + chunks terms can move it
     };
     float best = -3.0e38f;
@@ -866,10 +812,8 @@ __global__ __launch_bounds__(128) void corr_score_record2_kernel(const char* __r
         const int sidx = __float_as_int(S4s[slot < Ns ? slot : 0].w);
         const float sx = src_pts[(size_t)sidx * 3], sy = src_pts[(size_t)sidx * 3 + 1], sz = src_pts[(size_t)sidx * 3 + 2];
         const float* Th = T + (size_t)h * 16;
-        // (the same arithmetic as the other structures)
-        const float qx = fmaf(Th[2], sz, fmaf(Th[1], sy, Th[0] * sx)) + Th[3];
-        const float qy = fmaf(Th[6], sz, fmaf(Th[5], sy, Th[4] * sx)) + Th[7];
-        const float qz = fmaf(Th[10], sz, fmaf(Th[9], sy, Th[8] * sx)) + Th[11];
+        const HypImage q = hyp_image(Th, sx, sy, sz);
+        const float qx = q.x, qy = q.y, qz = q.z;
         const bool fin = live && fabsf(qx) < 1.0e18f && fabsf(qy) < 1.0e18f && fabsf(qz) < 1.0e18f;     // (NaN / inf images: not boxed)
         if (!__any(fin)) continue;
         // the box of the record's (finite) queries
