@@ -1,11 +1,12 @@
-"""Time the two ICP estimations and the normal estimation on the same inputs in one process; one JSON line per measurement.
+"""Time the three ICP estimations and the normal estimation on the same inputs in one process; one JSON line per measurement.
 
     python tools/icp_time.py [--out profiles/icp_plane/icp_time.jsonl] [--iters 10] [--warmup 3]
 
   * `normals`: ops.estimate_normals(pts, knn=30) at 50 000 and 120 000 points of a synthetic street scene (ground disc + wall
     patches, unsnapped, sigma 0.02 m), the search (umereg_knn_points_f32) and the covariance / eigenvector kernel together.
-  * `icp`: ops.icp_point_to_point and ops.icp_point_to_plane (synchronous calls, normals NOT included: they are the line above)
-    from the same start, with open3d's stop rule and max_iteration = 200 --
+  * `icp`: ops.icp_point_to_point, ops.icp_point_to_plane and ops.icp_plane_to_plane (epsilon 1e-3; synchronous calls, normals NOT
+    included: `normals_ms` is the target's, which point to plane needs, `src_normals_ms` the source's, which plane to plane needs on
+    top) from the same start, with open3d's stop rule and max_iteration = 200 --
       corner     three orthogonal 8 m patches, 2 000 points per cloud, independent samples, sigma 0.01 m, start off by
                  (0.02, -0.03, 0.05) rad and (0.15, -0.10, 0.12) m, correspondence distance 0.5 m (the case of DESIGN 4.18);
       kitti_raw  two independent 120 000-point samples of one street scene, start off by 0.5 deg about every axis and
@@ -122,13 +123,15 @@ def main():
         for name, c in CASES.items():
             src, tgt, gt, T0 = pair(c["cloud"], c["n"], 0, c["offset"], c["sigma"])
             s_, t_ = torch.from_numpy(src).to(dev), torch.from_numpy(tgt).to(dev)
-            normals = ops.estimate_normals(t_, args.knn)
+            normals, src_normals = ops.estimate_normals(t_, args.knn), ops.estimate_normals(s_, args.knn)
             line = dict(what="icp", case=name, n_src=len(src), n_tgt=len(tgt), max_correspondence_distance=c["max_dist"],
                         max_iteration=200, knn=args.knn, iters=args.iters, warmup=args.warmup)
             line["start_rot_deg"], line["start_trans_m"] = errors(T0, gt)
             line["normals_ms"] = median_ms(lambda: ops.estimate_normals(t_, args.knn), args.iters, args.warmup)
+            line["src_normals_ms"] = median_ms(lambda: ops.estimate_normals(s_, args.knn), args.iters, args.warmup)
             for est, fn in (("point_to_point", lambda: ops.icp_point_to_point(s_, t_, T0, c["max_dist"], 200)),
-                            ("point_to_plane", lambda: ops.icp_point_to_plane(s_, t_, normals, T0, c["max_dist"], 200))):
+                            ("point_to_plane", lambda: ops.icp_point_to_plane(s_, t_, normals, T0, c["max_dist"], 200)),
+                            ("plane_to_plane", lambda: ops.icp_plane_to_plane(s_, t_, src_normals, normals, T0, c["max_dist"], 200))):
                 ms = median_ms(fn, args.iters, args.warmup)
                 reg = fn()
                 rot, trans = errors(reg.transformation, gt)

@@ -24,9 +24,16 @@
 // the 21 upper entries of sum J J^T, the 6 of sum J r} (29 instead of 17, the same reduction tree) and the step solves
 // (sum J J^T) x = -(sum J r) through a 6x6 Jacobi eigen-decomposition (icp_plane_math.h: eigenvalues <= 1e-12 lambda_max count as
 // zero; open3d uses Eigen's LDLT, the two differ on rank-deficient systems only), update = [Rz(x2) Ry(x1) Rx(x0) | x3..5].
+//
+// Plane to plane (opt-in, icp_gicp_api.h; Segal's Generalized ICP, open3d's registration_generalized_icp): the same loop, search, stop
+// rule and step kernel once more.  icp_gicp_eval_kernel weights each correspondence by W = (C_q + R C_s R^T)^-1 with C = I - (1 - eps) n n^T
+// from the two normals (icp_gicp_math.h) and sums {n, sum |p'-q|^2, the 21 upper entries of sum J0^T W J0, the 6 of sum J0^T W d},
+// J0 = [-[p']x I3] -- the 29 sums of the point-to-plane layout, which is the special case W = n_q n_q^T.
 #include "grid.h"
 #include "umereg_icp_plane.h"
 #include "icp_plane_math.h"
+#include "icp_gicp_api.h"
+#include "icp_gicp_math.h"
 #include "polar.h"
 
 namespace umereg {
@@ -165,6 +172,104 @@ __global__ __launch_bounds__(kIcpThreads) void icp_eval_kernel(const float* __re
     }
 }
 
+// Plane to plane (opt-in, icp_gicp_api.h): the evaluation with the weights of icp_gicp_math.h.  A kernel of its own with the search of
+// icp_eval_kernel restated line for line: with the search shared as a device function the two existing instantiations came out with
+// commuted operands and another load offset, and they are to stay what they were, instruction for instruction.  The sums
+// have the layout of IcpSums<true>, so icp_step_kernel<true> takes them as they are.
+__global__ __launch_bounds__(kIcpThreads) void icp_gicp_eval_kernel(const float* __restrict__ src, int n_src,
+                                                                    const char* __restrict__ ws, int n_tgt, float max_dist,
+                                                                    const IcpState* __restrict__ state, double* __restrict__ partial,
+                                                                    const float* __restrict__ src_normals,
+                                                                    const float* __restrict__ normals, float epsilon)
+{
+    constexpr int kIcpSums = IcpSums<true>::kCount;
+    __shared__ double red[kIcpThreads / kWave][kIcpSums];
+    if (state->done) return;
+    const GridWs w = grid_ws(n_tgt);
+    const float4* __restrict__ P4s = reinterpret_cast<const float4*>(ws + w.off_p4s);
+    const int* __restrict__ start = reinterpret_cast<const int*>(ws + w.off_start);
+    const Grid g = load_grid(reinterpret_cast<const unsigned int*>(ws + w.off_bbox), -1.0f, n_tgt);
+    const int lane = lane_id(), wave = threadIdx.x >> 6;
+    const int sub = threadIdx.x & (kIcpLanes - 1);
+    double s[kIcpSums];
+#pragma unroll
+    for (int k = 0; k < kIcpSums; ++k) s[k] = 0.0;
+    constexpr int kPerRound = kIcpThreads / kIcpLanes;
+    for (int round = 0; round < kIcpBlock / kPerRound; ++round) {
+        const int i = blockIdx.x * kIcpBlock + round * kPerRound + (int)(threadIdx.x / kIcpLanes);
+        const bool live = i < n_src;
+        const int ii = live ? i : 0;
+        const double px = src[3 * ii + 0], py = src[3 * ii + 1], pz = src[3 * ii + 2];
+        const double* T = state->T;
+        const double qx = T[0] * px + T[1] * py + T[2] * pz + T[3];
+        const double qy = T[4] * px + T[5] * py + T[6] * pz + T[7];
+        const double qz = T[8] * px + T[9] * py + T[10] * pz + T[11];
+        const float fx = (float)qx, fy = (float)qy, fz = (float)qz;
+        // cells that can hold a point within max_dist (slack covers the rounding of the cell map)
+        const float r = max_dist * 1.001f + 1e-6f;
+        const int x0 = cell_axis(fx - r, g.minx, g.invx, g.nx), x1 = cell_axis(fx + r, g.minx, g.invx, g.nx);
+        const int y0 = cell_axis(fy - r, g.miny, g.invy, g.ny), y1 = cell_axis(fy + r, g.miny, g.invy, g.ny);
+        const int z0 = cell_axis(fz - r, g.minz, g.invz, g.nz), z1 = cell_axis(fz + r, g.minz, g.invz, g.nz);
+        unsigned long long best = ~0ull;                 // (d2 bits << 32) | original index: d2 >= 0, so the bits order like the values
+        float bx = 0.f, by = 0.f, bz = 0.f;
+        if (live)
+            for (int z = z0; z <= z1; ++z)
+                for (int y = y0; y <= y1; ++y) {
+                    const int cbase = (z * g.ny + y) * g.nx;
+                    const int beg = start[cbase + x0], end = start[cbase + x1 + 1];   // cells of one x-row are contiguous
+                    for (int k = beg + sub; k < end; k += kIcpLanes) {
+                        const float4 t = P4s[k];
+                        const float dx = fx - t.x, dy = fy - t.y, dz = fz - t.z;
+                        const float d2 = dx * dx + dy * dy + dz * dz;   // left to right, no contraction
+                        const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned int)__float_as_int(t.w);
+                        if (key < best) { best = key; bx = t.x; by = t.y; bz = t.z; }
+                    }
+                }
+        // the group's minimum, then the coordinates from the lane that holds it
+        unsigned long long m = best;
+#pragma unroll
+        for (int d = 1; d < kIcpLanes; d <<= 1) {
+            const unsigned long long o = __shfl_xor(m, d, kWave);
+            m = o < m ? o : m;
+        }
+        const unsigned long long holders = __ballot(best == m);
+        const int owner = (lane & ~(kIcpLanes - 1)) + (__ffs((int)((holders >> (lane & ~(kIcpLanes - 1))) & ((1u << kIcpLanes) - 1u))) - 1);
+        bx = __shfl(bx, owner, kWave); by = __shfl(by, owner, kWave); bz = __shfl(bz, owner, kWave);
+        const float bd2 = __uint_as_float((unsigned int)(m >> 32));
+        if (live && sub == 0 && m != ~0ull && bd2 < max_dist * max_dist) {
+            const double tx = bx, ty = by, tz = bz;
+            const double ex = qx - tx, ey = qy - ty, ez = qz - tz;
+            // both normals: the source's by the source index, rotated by the current R; the target's by the original index the key
+            // carries (a real point: its distance passed the cut).  W is fixed during the update.
+            const unsigned int oi = (unsigned int)(m & 0xffffffffull);
+            if (oi < (unsigned int)n_tgt) {
+                const double sx = src_normals[3 * (size_t)ii + 0], sy = src_normals[3 * (size_t)ii + 1], sz = src_normals[3 * (size_t)ii + 2];
+                const double a[3] = {T[0] * sx + T[1] * sy + T[2] * sz, T[4] * sx + T[5] * sy + T[6] * sz, T[8] * sx + T[9] * sy + T[10] * sz};
+                const double b[3] = {normals[3 * (size_t)oi + 0], normals[3 * (size_t)oi + 1], normals[3 * (size_t)oi + 2]};
+                const double p[3] = {qx, qy, qz}, d[3] = {ex, ey, ez};
+                double W[6];
+                gicp_weight(a, b, (double)epsilon, W);
+                s[0] += 1.0;
+                s[1] += ex * ex + ey * ey + ez * ez;
+                gicp_accumulate(p, d, W, s + 2);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < kIcpSums; ++k) {
+        double v = s[k];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) v += shfl_xor_f64(v, m);
+        if (lane == 0) red[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < kIcpSums) {
+        double v = 0.0;
+        for (int q = 0; q < kIcpThreads / kWave; ++q) v += red[q][threadIdx.x];
+        partial[(size_t)blockIdx.x * kIcpSums + threadIdx.x] = v;
+    }
+}
+
 template <bool kPlane>
 __global__ __launch_bounds__(kIcpWG) void icp_step_kernel(const double* __restrict__ partial, int n_blocks, int n_src,
                                                            int max_iter, double rel_fitness, double rel_rmse,
@@ -283,10 +388,13 @@ static size_t icp_extra_bytes(int n_src, int sums)
     return align_up(sizeof(IcpState), 256) + align_up(n_blocks * sums * sizeof(double), 256);
 }
 
-// which estimation a host call runs: point to point (normals == nullptr) or point to plane, and the name its errors carry
+// which estimation a host call runs: point to point (normals == nullptr), point to plane (the target's normals) or plane to plane
+// (src_normals too, and epsilon), and the name its errors carry
 struct IcpMode {
     const float* normals;
     const char* who;
+    const float* src_normals;
+    float epsilon;
 };
 constexpr IcpMode kIcpPointToPoint = {nullptr, "icp_point_to_point"};
 
@@ -367,7 +475,12 @@ static int icp_enqueue(const IcpMode& mode, const float* src, const float* tgt, 
     }
     const int n_blocks = (n_src + kIcpBlock - 1) / kIcpBlock;
     for (int b = 0; b < iterations; ++b) {
-        if (mode.normals) {
+        if (mode.src_normals) {
+            hipLaunchKernelGGL(icp_gicp_eval_kernel, dim3(n_blocks), dim3(kIcpThreads), 0, st, src, n_src, ws, n_tgt,
+                               max_correspondence_distance, state, partial, mode.src_normals, mode.normals, mode.epsilon);
+            hipLaunchKernelGGL(icp_step_kernel<true>, dim3(1), dim3(kIcpWG), 0, st, partial, n_blocks, n_src, max_iteration,
+                               relative_fitness, relative_rmse, state);
+        } else if (mode.normals) {
             hipLaunchKernelGGL(icp_eval_kernel<true>, dim3(n_blocks), dim3(kIcpThreads), 0, st, src, n_src, ws, n_tgt,
                                max_correspondence_distance, state, partial, mode.normals);
             hipLaunchKernelGGL(icp_step_kernel<true>, dim3(1), dim3(kIcpWG), 0, st, partial, n_blocks, n_src, max_iteration,
@@ -486,6 +599,61 @@ UMEREG_API int umereg_icp_plane_enqueue_f32(const float* src, const float* tgt, 
     UMEREG_REQUIRE(tgt_normals, "icp_plane_enqueue: null normals");
     const IcpMode mode = {tgt_normals, "icp_point_to_plane"};
     return icp_enqueue_download(mode, "icp_plane_enqueue", src, tgt, n_src, n_tgt, T_init_dev, max_correspondence_distance,
+                                max_iteration, relative_fitness, relative_rmse, first, iterations, state_host, workspace,
+                                workspace_bytes, stream);
+}
+
+// ---- plane to plane: the same host paths with both sets of normals and epsilon (icp_gicp_api.h) ------------------------------
+UMEREG_API size_t umereg_icp_plane_to_plane_workspace_bytes(int n_src, int n_tgt)
+{
+    return umereg_icp_plane_workspace_bytes(n_src, n_tgt);      // the 29 sums of IcpSums<true>
+}
+
+// the arguments the three entries add to the point-to-plane ones; NaN fails the range test
+static int icp_gicp_check(const char* entry, const float* src_normals, const float* tgt_normals, float epsilon)
+{
+    UMEREG_REQUIRE(src_normals && tgt_normals, "%s: null normals", entry);
+    UMEREG_REQUIRE(epsilon >= UMEREG_GICP_MIN_EPSILON && epsilon <= UMEREG_GICP_MAX_EPSILON, "%s: epsilon %g outside [1e-4, 1]", entry,
+                   (double)epsilon);
+    return UMEREG_OK;
+}
+
+UMEREG_API int umereg_icp_plane_to_plane_f32(const float* src, const float* tgt, const float* src_normals, const float* tgt_normals,
+                                             int n_src, int n_tgt, const double* T_init_host, float max_correspondence_distance,
+                                             int max_iteration, double relative_fitness, double relative_rmse, float epsilon,
+                                             double* T_out_host, double* fitness_host, double* inlier_rmse_host, int* iterations_host,
+                                             void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (int rc = icp_gicp_check("icp_plane_to_plane", src_normals, tgt_normals, epsilon)) return rc;
+    UMEREG_REQUIRE(T_init_host, "icp_plane_to_plane: null T_init");
+    const IcpMode mode = {tgt_normals, "icp_plane_to_plane", src_normals, epsilon};
+    return icp_run(mode, src, tgt, n_src, n_tgt, T_init_host, nullptr, max_correspondence_distance, max_iteration, relative_fitness,
+                   relative_rmse, T_out_host, fitness_host, inlier_rmse_host, iterations_host, workspace, workspace_bytes, stream);
+}
+
+UMEREG_API int umereg_icp_plane_to_plane_dev_f32(const float* src, const float* tgt, const float* src_normals, const float* tgt_normals,
+                                                 int n_src, int n_tgt, const float* T_init_dev, float max_correspondence_distance,
+                                                 int max_iteration, double relative_fitness, double relative_rmse, float epsilon,
+                                                 double* T_out_host, double* fitness_host, double* inlier_rmse_host,
+                                                 int* iterations_host, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (int rc = icp_gicp_check("icp_plane_to_plane_dev", src_normals, tgt_normals, epsilon)) return rc;
+    UMEREG_REQUIRE(T_init_dev, "icp_plane_to_plane_dev: null T_init");
+    const IcpMode mode = {tgt_normals, "icp_plane_to_plane", src_normals, epsilon};
+    return icp_run(mode, src, tgt, n_src, n_tgt, nullptr, T_init_dev, max_correspondence_distance, max_iteration, relative_fitness,
+                   relative_rmse, T_out_host, fitness_host, inlier_rmse_host, iterations_host, workspace, workspace_bytes, stream);
+}
+
+UMEREG_API int umereg_icp_plane_to_plane_enqueue_f32(const float* src, const float* tgt, const float* src_normals,
+                                                     const float* tgt_normals, int n_src, int n_tgt, const float* T_init_dev,
+                                                     float max_correspondence_distance, int max_iteration, double relative_fitness,
+                                                     double relative_rmse, float epsilon, int first, int iterations, void* state_host,
+                                                     void* workspace, size_t workspace_bytes, void* stream)
+{
+    UMEREG_REQUIRE(state_host, "icp_plane_to_plane_enqueue: null state_host");
+    if (int rc = icp_gicp_check("icp_plane_to_plane_enqueue", src_normals, tgt_normals, epsilon)) return rc;
+    const IcpMode mode = {tgt_normals, "icp_plane_to_plane", src_normals, epsilon};
+    return icp_enqueue_download(mode, "icp_plane_to_plane_enqueue", src, tgt, n_src, n_tgt, T_init_dev, max_correspondence_distance,
                                 max_iteration, relative_fitness, relative_rmse, first, iterations, state_host, workspace,
                                 workspace_bytes, stream);
 }

@@ -8,7 +8,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import icp_plane, ops, streams as _streams
+from . import icp_gicp, icp_plane, ops, streams as _streams
 from .host_rng import choice_uniform_noreplace
 from .pipeline import (PairBatch, PairResult, RegistrationPipeline, _draw_keypoints, _draw_keypoints_host, _index_tensor,  # noqa: F401
                        _phase_a, _phase_b, _PinnedRing, _ring, _to_host, phase_a_route, register_pair)
@@ -125,7 +125,8 @@ def refine_registration(R_hat, t_hat, args, pairs, tform_dev=None, estimation=No
     max correspondence distance 0.2 m, max_iteration=200, then RRE / RTE against the ground truth.
     estimation (default: args.icp_estimation, else "point_to_point", the reference's): "point_to_plane" refines with
     ops.icp_point_to_plane on the target's normals (ops.estimate_normals with args.icp_normal_knn = 30 neighbours and
-    args.icp_normal_radius = None), computed once per target cloud.
+    args.icp_normal_radius = None), computed once per target cloud; "plane_to_plane" with ops.icp_plane_to_plane on the normals of
+    both clouds (the source's in its own frame: the kernel rotates them) and args.icp_gicp_epsilon = 1e-3.
     The reference re-opens its dataset here; this takes the raw clouds instead:
     pairs = iterable of (src_pts_raw [n,3], tgt_pts_raw [m,3], gt_tform [4,4]).
     tform_dev: optional [P,4,4] float32 DEVICE tensor holding the same (R_hat, t_hat) as 4 x 4 transforms: the ICP then starts from
@@ -135,6 +136,7 @@ def refine_registration(R_hat, t_hat, args, pairs, tform_dev=None, estimation=No
     max_corr = float(getattr(args, "icp_max_correspondence_distance", 0.2))
     max_it = int(getattr(args, "icp_max_iteration", 200))
     estimation, normal_knn, normal_radius = icp_plane.estimation_of(args, estimation)
+    gicp_epsilon = icp_gicp.epsilon_of(args) if estimation == icp_gicp.ESTIMATION else None
     for itr, (src_pts_raw, tgt_pts_raw, gt_tform) in enumerate(pairs):
         if tform_dev is not None:
             tform_hat = tform_dev[itr].contiguous()
@@ -146,6 +148,10 @@ def refine_registration(R_hat, t_hat, args, pairs, tform_dev=None, estimation=No
         if estimation == "point_to_plane":
             normals = ops.estimate_normals(tgt_pts_raw, normal_knn, normal_radius)
             reg = ops.icp_point_to_plane(src_pts_raw, tgt_pts_raw, normals, tform_hat, max_corr, max_it)
+        elif estimation == icp_gicp.ESTIMATION:
+            src_normals = ops.estimate_normals(src_pts_raw, normal_knn, normal_radius)
+            normals = ops.estimate_normals(tgt_pts_raw, normal_knn, normal_radius)
+            reg = ops.icp_plane_to_plane(src_pts_raw, tgt_pts_raw, src_normals, normals, tform_hat, max_corr, max_it, epsilon=gicp_epsilon)
         else:
             reg = ops.icp_point_to_point(src_pts_raw, tgt_pts_raw, tform_hat, max_corr, max_it)
         new_tform = torch.from_numpy(reg.transformation).float()
@@ -195,6 +201,7 @@ def evaluate_pairs(pairs, args, rng=np.random, refine=True, verbose=False, overl
     max_corr = float(getattr(args, "icp_max_correspondence_distance", 0.2))
     max_it = int(getattr(args, "icp_max_iteration", 200))
     estimation, normal_knn, normal_radius = icp_plane.estimation_of(args)
+    gicp_epsilon = icp_gicp.epsilon_of(args) if estimation == icp_gicp.ESTIMATION else icp_gicp.DEFAULT_EPSILON
 
     def read_back(p):
         R_hat, t_hat, st, _keep, T_dev, job, clouds = p     # _keep: the pair's input tensors stay alive until its last kernel is done
@@ -243,9 +250,11 @@ def evaluate_pairs(pairs, args, rng=np.random, refine=True, verbose=False, overl
             job = None
             if refine and st is not None and src_raw.is_cuda and src_raw.dtype == torch.float32 and tgt_raw.dtype == torch.float32:
                 # (point to plane: the target's normals, once per target cloud, on the pair's stream behind the selection like the
-                # chain itself -- opting in adds no host read)
-                normals = ops.estimate_normals(tgt_raw, normal_knn, normal_radius) if estimation == "point_to_plane" else None
-                job = ops.IcpJob(src_raw, tgt_raw, T_dev[0].contiguous(), max_corr, max_it, tgt_normals=normals)          # :63-96
+                # chain itself -- opting in adds no host read; plane to plane: the source's too, in the source's own frame)
+                src_normals = ops.estimate_normals(src_raw, normal_knn, normal_radius) if estimation == icp_gicp.ESTIMATION else None
+                normals = ops.estimate_normals(tgt_raw, normal_knn, normal_radius) if estimation != "point_to_point" else None
+                job = ops.IcpJob(src_raw, tgt_raw, T_dev[0].contiguous(), max_corr, max_it, tgt_normals=normals,
+                                 src_normals=src_normals, epsilon=gicp_epsilon)                                           # :63-96
         raw.append(pair["gt_tform"])
         if pending is not None:
             read_back(pending)        # the previous pair's result: its scores ran beside everything above
@@ -370,16 +379,20 @@ def main(argv=None):
     parser.add_argument("--synthetic", type=int, default=8, help="number of synthetic pairs when no --pairs are given")
     parser.add_argument("--no-refine", action="store_true", help="skip the ICP refinement (evaluate.py:301)")
     parser.add_argument("--icp-estimation", choices=list(icp_plane.ESTIMATIONS), default="point_to_point",
-                        help="estimation of the ICP refinement: the reference's point to point (default) or point to plane on target "
-                             "normals estimated on the device (include/umereg_icp_plane.h)")
+                        help="estimation of the ICP refinement: the reference's point to point (default), point to plane on target "
+                             "normals estimated on the device (include/umereg_icp_plane.h), or plane to plane (generalized ICP) on the "
+                             "normals of both clouds (csrc/icp_gicp_api.h)")
     parser.add_argument("--icp-normal-knn", type=int, default=icp_plane.DEFAULT_KNN,
-                        help="with --icp-estimation point_to_plane: neighbours per target normal (3 .. 64)")
+                        help="with --icp-estimation point_to_plane / plane_to_plane: neighbours per normal (3 .. 64)")
     parser.add_argument("--icp-normal-radius", type=float, default=None,
-                        help="with --icp-estimation point_to_plane: hybrid search, neighbours farther than this are dropped")
+                        help="with --icp-estimation point_to_plane / plane_to_plane: hybrid search, neighbours farther than this are dropped")
+    parser.add_argument("--icp-gicp-epsilon", type=float, default=icp_gicp.DEFAULT_EPSILON,
+                        help="with --icp-estimation plane_to_plane: the regularised covariance's small eigenvalue, in [1e-4, 1]")
     cli = parser.parse_args(argv)
     config_path = benchmark_config_path(cli.benchmark)
     args = update_namespace_from_yaml(argparse.Namespace(benchmark=cli.benchmark), config_path)
     args.icp_estimation, args.icp_normal_knn, args.icp_normal_radius = cli.icp_estimation, cli.icp_normal_knn, cli.icp_normal_radius
+    args.icp_gicp_epsilon = cli.icp_gicp_epsilon
     rank, local_rank, world = init_distributed()
     device = torch.device("cuda", local_rank)
     torch.cuda.set_device(device)

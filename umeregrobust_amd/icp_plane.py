@@ -5,23 +5,24 @@
     job = ops.IcpJob(src, tgt, T_init_dev, 0.2, 200, tgt_normals=normals) # the same chain without the wait
 
 `evaluate.refine_registration` and `evaluate.evaluate_pairs` read `args.icp_estimation` ("point_to_point", the default and the
-reference's estimator, or "point_to_plane"), `args.icp_normal_knn` (30) and `args.icp_normal_radius` (None)."""
+reference's estimator, "point_to_plane", or "plane_to_plane": icp_gicp.py), `args.icp_normal_knn` (30) and `args.icp_normal_radius`
+(None)."""
 from . import _lib
 
 ICP_PLANE_SIGNATURES = _lib.TABLES["umereg_icp_plane.h"]
 load_native = _lib.load
 
-ESTIMATIONS = ("point_to_point", "point_to_plane")
+ESTIMATIONS = ("point_to_point", "point_to_plane", "plane_to_plane")     # the last one: icp_gicp.py (Segal's name for that form)
 MIN_KNN, MAX_KNN = 3, 64        # UMEREG_NORMALS_MIN_KNN / UMEREG_NORMALS_MAX_KNN
 DEFAULT_KNN = 30
 
 
 def check_estimation(who, estimation):
-    """None -> "point_to_point"; ValueError for anything but the two names.  Touches no tensor and no library."""
+    """None -> "point_to_point"; ValueError for anything but the three names.  Touches no tensor and no library."""
     if estimation is None:
         return ESTIMATIONS[0]
     if estimation not in ESTIMATIONS:
-        raise ValueError(f"{who}: icp_estimation must be 'point_to_point' or 'point_to_plane', got {estimation!r}")
+        raise ValueError(f"{who}: icp_estimation must be one of {', '.join(map(repr, ESTIMATIONS))}, got {estimation!r}")
     return estimation
 
 

@@ -596,25 +596,35 @@ def icp_point_to_point(src_pts, tgt_pts, T_init, max_correspondence_distance=0.2
                      relative_rmse)
 
 
-def _icp_entries(lib, plane):
-    """(size query, synchronous entry from a host start, the same from a device start, enqueue-only entry) of an estimation; the
-    point-to-plane entries take the target's normals as one more pointer behind the two clouds"""
-    if plane:
+def _icp_entries(lib, n_normals):
+    """(size query, synchronous entry from a host start, the same from a device start, enqueue-only entry) of an estimation, by the
+    number of normal sets it takes: the point-to-plane entries take the target's normals as one more pointer behind the two clouds,
+    the plane-to-plane entries (typed by icp_gicp's own table) the source's in front of them, and epsilon behind relative_rmse"""
+    if n_normals == 2:
+        from . import icp_gicp
+        lib = icp_gicp.load_native()
+        return (lib.umereg_icp_plane_to_plane_workspace_bytes, lib.umereg_icp_plane_to_plane_f32, lib.umereg_icp_plane_to_plane_dev_f32,
+                lib.umereg_icp_plane_to_plane_enqueue_f32)
+    if n_normals:
         return (lib.umereg_icp_plane_workspace_bytes, lib.umereg_icp_point_to_plane_f32, lib.umereg_icp_point_to_plane_dev_f32,
                 lib.umereg_icp_plane_enqueue_f32)
     return lib.umereg_icp_workspace_bytes, lib.umereg_icp_point_to_point_f32, lib.umereg_icp_point_to_point_dev_f32, lib.umereg_icp_enqueue_f32
 
 
-def _icp_sync(who, src_pts, tgt_pts, normals, T_init, max_correspondence_distance, max_iteration, relative_fitness, relative_rmse):
-    """The synchronous call behind icp_point_to_point (`normals` = ()) and icp_point_to_plane (`normals` = (tgt_normals,)); `who` is
-    the caller's name in every error."""
+def _icp_sync(who, src_pts, tgt_pts, normals, T_init, max_correspondence_distance, max_iteration, relative_fitness, relative_rmse,
+              epsilon=()):
+    """The synchronous call behind icp_point_to_point (`normals` = ()), icp_point_to_plane (`normals` = (tgt_normals,)) and
+    icp_plane_to_plane (`normals` = (src_normals, tgt_normals), `epsilon` = (checked float,)); `who` is the caller's name in every
+    error."""
     import numpy as np
     from types import SimpleNamespace
     lib = _lib.load()
     sp = _dev(src_pts, "src_pts"); tp = _dev(tgt_pts, "tgt_pts")
     if sp.dim() != 2 or tp.dim() != 2 or sp.shape[1] != 3 or tp.shape[1] != 3:
         raise ValueError(f"{who}: expected [n,3] clouds, got {tuple(sp.shape)}, {tuple(tp.shape)}")
-    nrm = [_normals_arg(who, t, tp) for t in normals]
+    # (one set: the target's; two: the source's in front of it)
+    clouds = ((sp, "src_normals"), (tp, "tgt_normals"))[2 - len(normals):]
+    nrm = [_normals_arg(who, t, c, name) for t, (c, name) in zip(normals, clouds)]
     if not isinstance(T_init, torch.Tensor):
         T_init = np.asarray(T_init)
     on_dev = isinstance(T_init, torch.Tensor) and T_init.is_cuda and T_init.dtype == torch.float32 and T_init.is_contiguous() \
@@ -630,24 +640,24 @@ def _icp_sync(who, src_pts, tgt_pts, normals, T_init, max_correspondence_distanc
     T = np.empty((4, 4), dtype=np.float64)
     out = np.zeros(2, dtype=np.float64)
     iters = np.zeros(1, dtype=np.int32)
-    size, from_host, from_dev, _ = _icp_entries(lib, bool(nrm))
+    size, from_host, from_dev, _ = _icp_entries(lib, len(nrm))
     # (a workspace of its own: an IcpJob in flight on this stream keeps its search grid in "icp" / "icpN" across result())
     ws = _workspace(dev, size(n, m), "icp_sync")
     _lib.call(dev, from_dev if on_dev else from_host, _ptr(sp), _ptr(tp), *map(_ptr, nrm), n, m,
               T_init.data_ptr() if on_dev else T0.ctypes.data, float(max_correspondence_distance), int(max_iteration),
-              float(relative_fitness), float(relative_rmse), T.ctypes.data, out.ctypes.data, out.ctypes.data + 8, iters.ctypes.data,
-              _ptr(ws), ws.numel(), _stream_ptr(dev))
+              float(relative_fitness), float(relative_rmse), *epsilon, T.ctypes.data, out.ctypes.data, out.ctypes.data + 8,
+              iters.ctypes.data, _ptr(ws), ws.numel(), _stream_ptr(dev))
     return SimpleNamespace(transformation=T, fitness=float(out[0]), inlier_rmse=float(out[1]), iterations=int(iters[0]))
 
 
-def _normals_arg(who, tgt_normals, tp):
-    """tgt_normals as the point-to-plane kernels read it: contiguous f32 [m,3] on the target's device (ValueError otherwise)."""
-    if not isinstance(tgt_normals, torch.Tensor) or tgt_normals.dtype != torch.float32 or tgt_normals.device != tp.device \
-            or tuple(tgt_normals.shape) != tuple(tp.shape):
-        got = (f"{tgt_normals.dtype} {tuple(tgt_normals.shape)} on {tgt_normals.device}" if isinstance(tgt_normals, torch.Tensor)
-               else type(tgt_normals).__name__)
-        raise ValueError(f"{who}: tgt_normals must be a float32 {tuple(tp.shape)} tensor on {tp.device}, got {got}")
-    return tgt_normals.contiguous()
+def _normals_arg(who, normals, cloud, name="tgt_normals"):
+    """a cloud's normals as the ICP kernels read them: contiguous f32 [m,3] on the cloud's device (ValueError otherwise, under `name`)."""
+    if not isinstance(normals, torch.Tensor) or normals.dtype != torch.float32 or normals.device != cloud.device \
+            or tuple(normals.shape) != tuple(cloud.shape):
+        got = (f"{normals.dtype} {tuple(normals.shape)} on {normals.device}" if isinstance(normals, torch.Tensor)
+               else type(normals).__name__)
+        raise ValueError(f"{who}: {name} must be a float32 {tuple(cloud.shape)} tensor on {cloud.device}, got {got}")
+    return normals.contiguous()
 
 
 def estimate_normals(pts, knn=30, radius=None):
@@ -688,6 +698,21 @@ def icp_point_to_plane(src_pts, tgt_pts, tgt_normals, T_init, max_correspondence
                      relative_fitness, relative_rmse)
 
 
+def icp_plane_to_plane(src_pts, tgt_pts, src_normals, tgt_normals, T_init, max_correspondence_distance=0.2, max_iteration=30,
+                       relative_fitness=1e-6, relative_rmse=1e-6, epsilon=1e-3):
+    """Plane-to-plane (generalized) ICP, Segal et al.'s GICP as open3d's registration_generalized_icp runs it: the loop, the stop rule,
+    fitness and inlier_rmse of icp_point_to_point; each correspondence is weighted by W = (C_q + R C_s R^T)^-1, where both clouds are
+    modelled as locally planar, C = I - (1 - epsilon) n n^T, and the update minimises sum d^T W d linearised in open3d's six parameters
+    (the 6x6 solve is icp_point_to_plane's).  src_normals [n,3] in the source's OWN frame and tgt_normals [m,3], f32 unit vectors on
+    the device (estimate_normals of each cloud; not checked; a zero normal means an isotropic covariance for that point);
+    epsilon in [1e-4, 1] (default open3d's, as recalled), handed over as f32; epsilon = 1 is Gauss-Newton point to point.  Everything
+    else, and the result, as icp_point_to_point.  The result does not depend on the sign of either set of normals."""
+    from . import icp_gicp
+    eps = icp_gicp.check_epsilon("icp_plane_to_plane", epsilon)
+    return _icp_sync("icp_plane_to_plane", src_pts, tgt_pts, (src_normals, tgt_normals), T_init, max_correspondence_distance,
+                     max_iteration, relative_fitness, relative_rmse, (eps,))
+
+
 _icp_pinned = []      # pinned state buffers of finished IcpJobs, for reuse (a pinned allocation costs more than an ICP evaluation)
 _icp_inflight = {}    # (device index, stream) -> workspace tags of the jobs in flight there
 
@@ -700,23 +725,32 @@ class IcpJob:
     flight (evaluate.evaluate_pairs) starts a pair's ICP right behind its hypothesis selection and collects it one pair later: the
     refinement costs the host no round trip (reference evaluate.py:301 refines after the loop -- nothing needs it earlier).
     tgt_normals (f32 [m,3] on the device, e.g. estimate_normals(tgt_pts) enqueued on the same stream): the point-to-plane chain of
-    icp_point_to_plane instead, with the same workspace-slot and pinned-state discipline."""
+    icp_point_to_plane instead, with the same workspace-slot and pinned-state discipline.  src_normals too (f32 [n,3], the source's own
+    frame; ValueError without tgt_normals): the plane-to-plane chain of icp_plane_to_plane with `epsilon`, which is read in that case only."""
 
     def __init__(self, src_pts, tgt_pts, T_init_dev, max_correspondence_distance=0.2, max_iteration=30, relative_fitness=1e-6,
-                 relative_rmse=1e-6, tgt_normals=None):
+                 relative_rmse=1e-6, tgt_normals=None, src_normals=None, epsilon=1e-3):
+        if src_normals is not None and tgt_normals is None:
+            raise ValueError("IcpJob: src_normals given without tgt_normals (plane to plane takes both; point to plane the target's)")
+        eps = ()
+        if src_normals is not None:
+            from . import icp_gicp
+            eps = (icp_gicp.check_epsilon("IcpJob", epsilon),)
         lib = _lib.load()
         self.sp = _dev(src_pts, "src_pts"); self.tp = _dev(tgt_pts, "tgt_pts")
         if self.sp.dim() != 2 or self.tp.dim() != 2 or self.sp.shape[1] != 3 or self.tp.shape[1] != 3:
             raise ValueError(f"IcpJob: expected [n,3] clouds, got {tuple(self.sp.shape)}, {tuple(self.tp.shape)}")
         self.nrm = [] if tgt_normals is None else [_normals_arg("IcpJob", tgt_normals, self.tp)]
-        size, _, _, self.entry = _icp_entries(lib, bool(self.nrm))
+        if src_normals is not None:
+            self.nrm.insert(0, _normals_arg("IcpJob", src_normals, self.sp, "src_normals"))
+        size, _, _, self.entry = _icp_entries(lib, len(self.nrm))
         if not (isinstance(T_init_dev, torch.Tensor) and T_init_dev.is_cuda and T_init_dev.dtype == torch.float32
                 and T_init_dev.is_contiguous() and tuple(T_init_dev.shape) == (4, 4) and T_init_dev.device == self.sp.device):
             raise ValueError("IcpJob: T_init_dev must be a contiguous float32 [4,4] tensor on the clouds' device")
         if self.sp.shape[0] == 0 or self.tp.shape[0] == 0:
             raise ValueError("IcpJob: empty cloud")
         self.T0 = T_init_dev
-        self.par = (float(max_correspondence_distance), int(max_iteration), float(relative_fitness), float(relative_rmse))
+        self.par = (float(max_correspondence_distance), int(max_iteration), float(relative_fitness), float(relative_rmse)) + eps
         dev = self.dev = self.sp.device
         self.stream = torch.cuda.current_stream(dev)
         self.key = (dev.index, _stream_ptr(dev))
