@@ -699,12 +699,17 @@ def umeyama_no_scaling(p, q):
     return R, mq - R @ mp
 
 
-def icp_point_to_point(src, tgt, T_init, max_dist=0.2, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6, steps=None):
+def icp_point_to_point(src, tgt, T_init, max_dist=0.2, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6, steps=None,
+                       trace=None):
     """-> (T float64 [4,4], fitness, inlier_rmse, iterations).
-    steps: optional list; receives (max |R_upd - I|, max |t_upd|) of every update applied, in order."""
+    steps: optional list; receives (max |R_upd - I|, max |t_upd|) of every update applied, in order.
+    trace: optional list; receives one record per evaluation, (T evaluated, fitness, rmse, |d fitness|, |d rmse|, stopped), the
+    differences against the evaluation before (None for the first)."""
     T = np.asarray(T_init, np.float64).copy()
     tgt64 = np.asarray(tgt, np.float32).astype(np.float64)
     idx, fit, rmse, q = icp_evaluate(src, tgt, T, max_dist)
+    if trace is not None:
+        trace.append((T.copy(), fit, rmse, None, None, False))
     it = 0
     for _ in range(max_iteration):
         ok = idx >= 0
@@ -718,7 +723,10 @@ def icp_point_to_point(src, tgt, T_init, max_dist=0.2, max_iteration=30, relativ
         it += 1
         pf, pr = fit, rmse
         idx, fit, rmse, q = icp_evaluate(src, tgt, T, max_dist)
-        if abs(pf - fit) < relative_fitness and abs(pr - rmse) < relative_rmse:
+        stop = abs(pf - fit) < relative_fitness and abs(pr - rmse) < relative_rmse
+        if trace is not None:
+            trace.append((T.copy(), fit, rmse, abs(pf - fit), abs(pr - rmse), stop))
+        if stop:
             break
     return T, fit, rmse, it
 

@@ -55,16 +55,19 @@ def retained_cond(A):
 
 
 def icp_plane_to_plane(src, tgt, src_normals, tgt_normals, T_init, max_dist=0.2, max_iteration=30, relative_fitness=1e-6,
-                       relative_rmse=1e-6, epsilon=DEFAULT_EPSILON, conds=None, margins=None):
+                       relative_rmse=1e-6, epsilon=DEFAULT_EPSILON, conds=None, margins=None, trace=None):
     """open3d's RegistrationICP loop with the plane-to-plane system -> (T float64 [4,4], fitness, inlier_rmse, iterations).
     conds: optional list; receives the retained condition number of every system solved.  margins: optional list; receives, per stop
-    test, how far the decision is from flipping."""
+    test, how far the decision is from flipping.  trace: optional list; receives one record per evaluation, (T evaluated, fitness,
+    rmse, |d fitness|, |d rmse|, stopped), the differences against the evaluation before (None for the first)."""
     eps = float(np.float32(epsilon))
     T = np.asarray(T_init, np.float64).copy()
     tgt64 = np.asarray(tgt, np.float32).astype(np.float64)
     ns64 = np.asarray(src_normals, np.float32).astype(np.float64)
     nt64 = np.asarray(tgt_normals, np.float32).astype(np.float64)
     idx, fit, rmse, p = orc.icp_evaluate(src, tgt, T, max_dist)
+    if trace is not None:
+        trace.append((T.copy(), fit, rmse, None, None, False))
     it = 0
     for _ in range(max_iteration):
         ok = idx >= 0
@@ -80,6 +83,8 @@ def icp_plane_to_plane(src, tgt, src_normals, tgt_normals, T_init, max_dist=0.2,
         stop = df < relative_fitness and dr < relative_rmse
         if margins is not None:      # what either difference would have to move by for the decision to flip
             margins.append(min(relative_fitness - df, relative_rmse - dr) if stop else max(df - relative_fitness, dr - relative_rmse))
+        if trace is not None:
+            trace.append((T.copy(), fit, rmse, df, dr, stop))
         if stop:
             break
     return T, fit, rmse, it

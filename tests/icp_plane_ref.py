@@ -174,13 +174,16 @@ def plane_solve(A, b):
 
 
 def icp_point_to_plane(src, tgt, normals, T_init, max_dist=0.2, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6,
-                       conds=None):
+                       conds=None, trace=None):
     """open3d's RegistrationICP with TransformationEstimationPointToPlane -> (T float64 [4,4], fitness, inlier_rmse, iterations).
-    conds: optional list; receives cond(J^T J) of every system solved."""
+    conds: optional list; receives cond(J^T J) of every system solved.  trace: optional list; receives one record per evaluation,
+    (T evaluated, fitness, rmse, |d fitness|, |d rmse|, stopped), the differences against the evaluation before (None for the first)."""
     T = np.asarray(T_init, np.float64).copy()
     tgt64 = np.asarray(tgt, np.float32).astype(np.float64)
     nrm64 = np.asarray(normals, np.float32).astype(np.float64)
     idx, fit, rmse, q = orc.icp_evaluate(src, tgt, T, max_dist)
+    if trace is not None:
+        trace.append((T.copy(), fit, rmse, None, None, False))
     it = 0
     for _ in range(max_iteration):
         ok = idx >= 0
@@ -194,7 +197,10 @@ def icp_point_to_plane(src, tgt, normals, T_init, max_dist=0.2, max_iteration=30
         it += 1
         pf, pr = fit, rmse
         idx, fit, rmse, q = orc.icp_evaluate(src, tgt, T, max_dist)
-        if abs(pf - fit) < relative_fitness and abs(pr - rmse) < relative_rmse:
+        stop = abs(pf - fit) < relative_fitness and abs(pr - rmse) < relative_rmse
+        if trace is not None:
+            trace.append((T.copy(), fit, rmse, abs(pf - fit), abs(pr - rmse), stop))
+        if stop:
             break
     return T, fit, rmse, it
 

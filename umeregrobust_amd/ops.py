@@ -591,7 +591,10 @@ def icp_point_to_point(src_pts, tgt_pts, T_init, max_correspondence_distance=0.2
     src_pts [n,3], tgt_pts [m,3] (device f32), T_init [4,4] (any float tensor / array) ->
     SimpleNamespace(transformation float64 [4,4] numpy, fitness, inlier_rmse, iterations).
     A T_init that is a contiguous float32 DEVICE tensor is not read back: the first kernel reads it when it runs, so the chain is
-    enqueued behind whatever is still computing it (the hypothesis selection)."""
+    enqueued behind whatever is still computing it (the hypothesis selection).
+    The loop stops after the update whose evaluation has |d fitness| < relative_fitness AND |d inlier_rmse| < relative_rmse against
+    the evaluation before.  Both comparisons are strict, as open3d's are: a threshold of 0 disables that half of the rule, and with
+    it the rule, so the run goes to max_iteration."""
     return _icp_sync("icp_point_to_point", src_pts, tgt_pts, (), T_init, max_correspondence_distance, max_iteration, relative_fitness,
                      relative_rmse)
 
@@ -693,7 +696,8 @@ def icp_point_to_plane(src_pts, tgt_pts, tgt_normals, T_init, max_correspondence
     parameters.  tgt_normals [m,3] f32 on the device (estimate_normals(tgt_pts)); everything else, and the result, as
     icp_point_to_point.  One documented deviation from open3d: the 6x6 normal equations are solved through their eigen-decomposition
     with eigenvalues <= 1e-12 lambda_max treated as zero (open3d: LDLT) -- a single wall or a ground plane gives a finite update
-    that leaves the unconstrained directions alone; full-rank systems get the same solution."""
+    that leaves the unconstrained directions alone; full-rank systems get the same solution.  The stop rule's two comparisons are
+    strict (icp_point_to_point): a relative_fitness or relative_rmse of 0 disables that half, and the run goes to max_iteration."""
     return _icp_sync("icp_point_to_plane", src_pts, tgt_pts, (tgt_normals,), T_init, max_correspondence_distance, max_iteration,
                      relative_fitness, relative_rmse)
 
@@ -706,7 +710,9 @@ def icp_plane_to_plane(src_pts, tgt_pts, src_normals, tgt_normals, T_init, max_c
     (the 6x6 solve is icp_point_to_plane's).  src_normals [n,3] in the source's OWN frame and tgt_normals [m,3], f32 unit vectors on
     the device (estimate_normals of each cloud; not checked; a zero normal means an isotropic covariance for that point);
     epsilon in [1e-4, 1] (default open3d's, as recalled), handed over as f32; epsilon = 1 is Gauss-Newton point to point.  Everything
-    else, and the result, as icp_point_to_point.  The result does not depend on the sign of either set of normals."""
+    else, and the result, as icp_point_to_point.  The result does not depend on the sign of either set of normals.  The stop rule's
+    two comparisons are strict (icp_point_to_point): a relative_fitness or relative_rmse of 0 disables that half, and the run goes to
+    max_iteration."""
     from . import icp_gicp
     eps = icp_gicp.check_epsilon("icp_plane_to_plane", epsilon)
     return _icp_sync("icp_plane_to_plane", src_pts, tgt_pts, (src_normals, tgt_normals), T_init, max_correspondence_distance,
