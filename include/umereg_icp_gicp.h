@@ -1,19 +1,18 @@
-/* icp_gicp_api.h -- C entries of the opt-in plane-to-plane (generalized) ICP refinement (csrc/icp.hip, csrc/icp_gicp_math.h): Segal et
+/* umereg_icp_gicp.h -- C entries of the opt-in plane-to-plane (generalized) ICP refinement (csrc/icp.hip, csrc/icp_gicp_math.h): Segal et
  * al.'s Generalized ICP in its plane-to-plane form, the counterpart of open3d's
  *     registration_generalized_icp(src, tgt, d, T_init, TransformationEstimationForGeneralizedICP(epsilon),
  *                                  ICPConvergenceCriteria(max_iteration=...))
  * (epsilon = 1e-3 by default there, as recalled).  open3d is not installable here: parity with it stays unpinned, as for the other two
  * loops.
  *
- * The header lives beside the kernels, not under include/ (the public ABI census is pinned); the entries are typed by a module-owned
- * table (umeregrobust_amd/icp_gicp.py: ICP_GICP_SIGNATURES).
+ * The entries are typed by _lib.TABLES["umereg_icp_gicp.h"], which umeregrobust_amd/icp_gicp.py aliases as ICP_GICP_SIGNATURES.
  *
  * Same conventions as umereg_icp_plane.h: outputs and workspace belong to the caller, every compute entry takes a HIP stream (NULL =
  * the default stream), returns UMEREG_OK or a negative UMEREG_E* code, reports argument errors before it probes for a device and
  * allocates nothing.  The size query is host arithmetic and returns 0 for arguments the entries refuse.  Every output is a function
  * of the inputs alone: no atomics, fixed reduction trees, no word of the workspace read that the call did not write. */
-#ifndef UMEREG_ICP_GICP_API_H
-#define UMEREG_ICP_GICP_API_H
+#ifndef UMEREG_ICP_GICP_H
+#define UMEREG_ICP_GICP_H
 
 #include <stddef.h>
 #include <stdint.h>

@@ -30,6 +30,7 @@ HEADERS = {
     "umereg_infonce.h": ("infonce.INFONCE_SIGNATURES", 3),
     "umereg_gt_keypoints.h": ("gt_keypoints.GT_KEYPOINTS_SIGNATURES", 4),
     "umereg_icp_plane.h": ("icp_plane.ICP_PLANE_SIGNATURES", 6),
+    "umereg_icp_gicp.h": ("icp_gicp.ICP_GICP_SIGNATURES", 4),
 }
 
 

@@ -1,4 +1,4 @@
-"""fp64 restatement of the plane-to-plane (generalized) ICP refinement (umeregrobust_amd/csrc/icp_gicp_api.h), for
+"""fp64 restatement of the plane-to-plane (generalized) ICP refinement (include/umereg_icp_gicp.h), for
 tests/test_icp_gicp_cpu.py and tests/test_icp_gicp_gpu.py: the open3d loop of icp_plane_ref.icp_point_to_plane with the system
 
     a = R n_s, b = n_q, M = 2 I - (1 - eps) (a a^T + b b^T), W = inv(M), d = p - q, J0 = [-[p]x I3]

@@ -19,14 +19,14 @@ def _alias(attr):
 
 
 def test_library_builds_and_one_table_per_header():
-    """the library builds and loads; include/ holds the sixteen headers, _lib.TABLES one table for each, no symbol in two of them"""
+    """the library builds and loads; include/ holds the seventeen headers, _lib.TABLES one table for each, no symbol in two of them"""
     import umeregrobust_amd
     from umeregrobust_amd import _lib
     assert os.path.exists(umeregrobust_amd.build_native())
-    assert sorted(os.listdir(abi_headers.INCLUDE)) == sorted(abi_headers.HEADERS) == sorted(_lib.TABLES) and len(_lib.TABLES) == 16
+    assert sorted(os.listdir(abi_headers.INCLUDE)) == sorted(abi_headers.HEADERS) == sorted(_lib.TABLES) and len(_lib.TABLES) == 17
     assert _lib.TABLES["umereg.h"] is _lib.SIGNATURES
     names = [name for table in _lib.TABLES.values() for name in table]
-    assert len(names) == len(set(names)) == 126, sorted(n for n in set(names) if names.count(n) > 1)
+    assert len(names) == len(set(names)) == 130, sorted(n for n in set(names) if names.count(n) > 1)
     assert _lib.load().umereg_abi_version() == _lib.ABI_VERSION == 2
 
 
@@ -115,7 +115,7 @@ def test_no_status_entry_is_called_directly():
     make the tensors' device current): nowhere under umeregrobust_amd/ is one called as `lib.umereg_...(`."""
     from umeregrobust_amd import _lib
     status = {name for table in _lib.TABLES.values() for name, (res, _) in table.items() if res is ctypes.c_int} - NOT_A_STATUS
-    assert len(status) == 89 and NOT_A_STATUS <= {n for t in _lib.TABLES.values() for n in t}
+    assert len(status) == 92 and NOT_A_STATUS <= {n for t in _lib.TABLES.values() for n in t}
     pkg, seen = os.path.join(REPO, "umeregrobust_amd"), 0
     for root, _, files in os.walk(pkg):
         for f in files:

@@ -5,7 +5,6 @@ Python entry points without a GPU.
 Bounds (derived, not measured): M = 2 I - (1 - eps) (a a^T + b b^T) has eigenvalues in [2 eps, 2], so cond(M) <= 1 / eps and an
 inverse computed in fp64 errs by a small multiple of cond(M) 2^-53 relative to max |W|: the bar is ten such units, 10 * 2^-53 / eps.
 The 27 sums are a few hundred fp64 terms each, every term a short product of W (already within 1e-13 of numpy's): 1e-12 relative."""
-import ctypes
 import inspect
 from types import SimpleNamespace
 
@@ -152,25 +151,19 @@ def test_restatement_without_correspondences_is_the_identity():
 # ---- the entries and the Python surface without a GPU ------------------------------------------------------------------------------
 
 def test_the_table_is_the_module_s_and_mirrors_the_header():
+    """the header is one of include/ and its table one of _lib.TABLES (names, parameter counts and return types against the header:
+    test_abi.py::test_table_mirrors_its_header_and_every_symbol_is_exported); here what is the module's own"""
     import abi_headers
     from umeregrobust_amd import _build, _lib, icp_gicp
     import os
-    path = os.path.join(_build.CSRC, "icp_gicp_api.h")
-    assert path in _build.headers() and os.path.join(_build.CSRC, "icp_gicp_math.h") in _build.headers()      # part of the build hash
-    assert not any(set(icp_gicp.ICP_GICP_SIGNATURES) & set(t) for t in _lib.TABLES.values())
-    assert not os.path.exists(os.path.join(abi_headers.INCLUDE, "icp_gicp_api.h"))
-    # the header's declarations, read as tests/abi_headers.py reads the public ones: names, parameter counts, return types
     import re
-    raw = open(path).read()
-    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", raw, flags=re.S))
-    decl = {m.group(2): (m.group(1), abi_headers._count(" ".join(m.group(3).split())))
-            for m in re.finditer(r"^(size_t|int)\s+(umereg_\w+)\s*\(([^)]*)\)\s*;", text, flags=re.M)}
-    assert sorted(decl) == sorted(icp_gicp.ICP_GICP_SIGNATURES) and len(decl) == 4
-    for name, (ret, n_params) in decl.items():
-        res, args = icp_gicp.ICP_GICP_SIGNATURES[name]
-        assert res is {"size_t": ctypes.c_size_t, "int": ctypes.c_int}[ret] and len(args) == n_params, name
+    path = os.path.join(abi_headers.INCLUDE, "umereg_icp_gicp.h")
+    assert path in _build.headers() and os.path.join(_build.CSRC, "icp_gicp_math.h") in _build.headers()      # part of the build hash
+    assert icp_gicp.ICP_GICP_SIGNATURES is _lib.TABLES["umereg_icp_gicp.h"] and abi_headers.HEADERS["umereg_icp_gicp.h"][1] == 4
+    assert icp_gicp.load_native is _lib.load
     lib = icp_gicp.load_native()
     assert lib is _lib.load() and lib.umereg_icp_plane_to_plane_f32.argtypes == icp_gicp.ICP_GICP_SIGNATURES["umereg_icp_plane_to_plane_f32"][1]
+    raw = open(path).read()
     assert (icp_gicp.MIN_EPSILON, icp_gicp.MAX_EPSILON) == tuple(float(re.search(rf"#define UMEREG_GICP_{k}_EPSILON ([0-9.e-]+)f", raw).group(1))
                                                                  for k in ("MIN", "MAX"))
 

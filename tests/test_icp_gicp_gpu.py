@@ -1,4 +1,4 @@
-"""GPU: the opt-in plane-to-plane (generalized) ICP (umeregrobust_amd/csrc/icp_gicp_api.h) against its fp64 restatement
+"""GPU: the opt-in plane-to-plane (generalized) ICP (include/umereg_icp_gicp.h) against its fp64 restatement
 (tests/icp_gicp_ref.py).
 
 The gate is the point-to-plane test's own -- equal iteration count, |d fitness| < 1e-12, |d rmse| < 1e-9, max |dT| < 1e-9.  What

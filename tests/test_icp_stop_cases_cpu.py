@@ -159,25 +159,19 @@ def test_margins_ignore_a_comparison_against_zero():
 
 # ------------------------------------------------------------------------------------------------ the threshold slots
 def _tables():
-    from umeregrobust_amd import _build, _lib, icp_gicp
-    gicp_header = os.path.join(_build.CSRC, "icp_gicp_api.h")
-    return (("umereg.h", _lib.TABLES["umereg.h"], None, ("umereg_icp_point_to_point_f32", "umereg_icp_point_to_point_dev_f32",
-                                                         "umereg_icp_enqueue_f32")),
-            ("umereg_icp_plane.h", _lib.TABLES["umereg_icp_plane.h"], None,
+    from umeregrobust_amd import _lib
+    return (("umereg.h", _lib.TABLES["umereg.h"], ("umereg_icp_point_to_point_f32", "umereg_icp_point_to_point_dev_f32",
+                                                   "umereg_icp_enqueue_f32")),
+            ("umereg_icp_plane.h", _lib.TABLES["umereg_icp_plane.h"],
              ("umereg_icp_point_to_plane_f32", "umereg_icp_point_to_plane_dev_f32", "umereg_icp_plane_enqueue_f32")),
-            ("icp_gicp_api.h", icp_gicp.ICP_GICP_SIGNATURES, gicp_header,
+            ("umereg_icp_gicp.h", _lib.TABLES["umereg_icp_gicp.h"],
              ("umereg_icp_plane_to_plane_f32", "umereg_icp_plane_to_plane_dev_f32", "umereg_icp_plane_to_plane_enqueue_f32")))
 
 
-def _header_params(header, path, name):
+def _header_params(header, name):
     """the declaration's parameters as (type, name) pairs"""
-    if path is None:
-        plist = abi_headers.params(header, name)
-    else:
-        text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S))
-        plist = " ".join(re.search(r"\b" + re.escape(name) + r"\s*\(([^)]*)\)", text).group(1).split())
     out = []
-    for p in plist.split(","):
+    for p in abi_headers.params(header, name).split(","):
         words = p.replace("*", "* ").split()
         out.append((" ".join(words[:-1]).replace(" *", "*"), words[-1]))
     return out
@@ -193,12 +187,12 @@ def _threshold_slots(argtypes):
 
 def test_threshold_slots_are_doubles_in_the_tables_and_the_headers():
     seen = 0
-    for header, table, path, names in _tables():
+    for header, table, names in _tables():
         for name in names:
             argtypes = table[name][1]
             f, r = _threshold_slots(argtypes)
             assert argtypes[f] is c_double and argtypes[r] is c_double, name
-            params = _header_params(header, path, name)
+            params = _header_params(header, name)
             assert len(params) == len(argtypes), name
             assert params[f - 1] == ("int", "max_iteration"), name
             assert params[f] == ("double", "relative_fitness") and params[r] == ("double", "relative_rmse"), name
@@ -208,17 +202,19 @@ def test_threshold_slots_are_doubles_in_the_tables_and_the_headers():
 
 
 def test_the_definitions_hand_the_thresholds_on_in_order():
-    """csrc/icp.hip: every one of the nine entries, icp_run and icp_enqueue_download pass (relative_fitness, relative_rmse) on in that
-    order, and the three launches of icp_step_kernel take them in the order of its parameters (rel_fitness, rel_rmse)"""
+    """csrc/icp.hip: every one of the nine entries puts (relative_fitness, relative_rmse) into the call's record in that order, which
+    is the order of the record's fields, and the one launch of icp_step_kernel takes them from the record in the order of its
+    parameters (rel_fitness, rel_rmse)"""
     from umeregrobust_amd import _build
     text = open(os.path.join(_build.CSRC, "icp.hip")).read()
     text = re.sub(r"//[^\n]*", "", text)
-    pairs = re.findall(r"\b(relative_\w+)\s*,\s*(?:double\s+)?(relative_\w+)", text)
-    assert len(pairs) >= 9 + 9 + 4 + 4               # the entries' parameters and what they pass on, the helpers and their declarations
+    pairs = re.findall(r"\b(relative_\w+)\s*,\s*(?:double\s+|m\.)?(relative_\w+)", text)
+    assert len(pairs) == 9 + 9 + 1 + 1               # the entries' parameters, what they put into the record, its fields, the step launch
     assert set(pairs) == {("relative_fitness", "relative_rmse")}
     assert len(re.findall(r"\brelative_fitness\b", text)) == len(re.findall(r"\brelative_rmse\b", text)) == len(pairs)
     assert re.search(r"int max_iter, double rel_fitness, double rel_rmse,", text)
-    assert len(re.findall(r"max_iteration,\s*relative_fitness, relative_rmse, state\);", text)) == 3
+    assert len(re.findall(r"m\.max_iteration,\s*m\.relative_fitness, m\.relative_rmse, state\);", text)) == 1
+    assert len(re.findall(r"\bicp_step_kernel<", text)) == 1
 
 
 def test_sync_wrappers_pass_fitness_before_rmse(monkeypatch):
@@ -234,10 +230,10 @@ def test_sync_wrappers_pass_fitness_before_rmse(monkeypatch):
     monkeypatch.setattr(_lib, "call", lambda dev, fn, *args: calls.append((fn, args)))
     s, t = torch.zeros(5, 3), torch.zeros(7, 3)
     rf, rr = 0.1 + 2.0 ** -40, 0.3 + 2.0 ** -41                 # neither survives a trip through float
-    tables = {h: (tab, names) for h, tab, _, names in _tables()}
+    tables = {h: (tab, names) for h, tab, names in _tables()}
     for header, run in (("umereg.h", lambda **kw: ops.icp_point_to_point(s, t, np.eye(4), 0.2, 17, **kw)),
                         ("umereg_icp_plane.h", lambda **kw: ops.icp_point_to_plane(s, t, t.clone(), np.eye(4), 0.2, 17, **kw)),
-                        ("icp_gicp_api.h", lambda **kw: ops.icp_plane_to_plane(s, t, s.clone(), t.clone(), np.eye(4), 0.2, 17, **kw))):
+                        ("umereg_icp_gicp.h", lambda **kw: ops.icp_plane_to_plane(s, t, s.clone(), t.clone(), np.eye(4), 0.2, 17, **kw))):
         table, names = tables[header]
         f, r = _threshold_slots(table[names[0]][1])
         for kw, want in ((dict(relative_fitness=rf, relative_rmse=rr), (rf, rr)), (dict(relative_rmse=rr), (1e-6, rr)),
@@ -252,7 +248,7 @@ def test_sync_wrappers_pass_fitness_before_rmse(monkeypatch):
     ops.icp_point_to_point(s, t, np.eye(4), 0.2, 17, rf, rr)
     ops.icp_point_to_plane(s, t, t.clone(), np.eye(4), 0.2, 17, rf, rr)
     ops.icp_plane_to_plane(s, t, s.clone(), t.clone(), np.eye(4), 0.2, 17, rf, rr)
-    for (fn, args), header in zip(calls, ("umereg.h", "umereg_icp_plane.h", "icp_gicp_api.h")):
+    for (fn, args), header in zip(calls, ("umereg.h", "umereg_icp_plane.h", "umereg_icp_gicp.h")):
         f, r = _threshold_slots(tables[header][0][tables[header][1][0]][1])
         assert (args[f], args[r]) == (rf, rr)
 

@@ -224,7 +224,7 @@ def test_trajectory(gpu, estimator):
 def test_totals_second_stride(gpu, estimator, n_src):
     """256, 257 and 258 rows of partial sums: thread t of icp_step_kernel sums rows t, t + 256, so threads 0 and 1 go round a second
     time for the last two counts, whose rows 256 and 257 hold one matched point each (17 sums for point to point, 29 for the two
-    plane estimators, the latter fed by icp_eval_kernel<true> and by icp_gicp_eval_kernel)"""
+    plane estimators, the latter fed by icp_eval_kernel's point-to-plane and plane-to-plane instantiations)"""
     s, t, nrm, T0d = _device_inputs("stride", gpu)
     s = s[:n_src].contiguous()
     nrm = _normals(estimator, nrm, n_src)

@@ -252,6 +252,18 @@ _ICP_PLANE = {
                                              c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
+_ICP_GICP = {
+    "umereg_icp_plane_to_plane_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "umereg_icp_plane_to_plane_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_double,
+                                              c_double, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "umereg_icp_plane_to_plane_dev_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int,
+                                                  c_double, c_double, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_size_t, c_void_p]),
+    "umereg_icp_plane_to_plane_enqueue_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int,
+                                                      c_double, c_double, c_float, c_int, c_int, c_void_p, c_void_p, c_size_t,
+                                                      c_void_p]),
+}
+
 # header under include/ -> {name: (restype, argtypes)}: each table mirrors its header one to one, and one .so exports them all
 TABLES = {
     "umereg.h": SIGNATURES,
@@ -270,6 +282,7 @@ TABLES = {
     "umereg_infonce.h": _INFONCE,
     "umereg_gt_keypoints.h": _GT_KEYPOINTS,
     "umereg_icp_plane.h": _ICP_PLANE,
+    "umereg_icp_gicp.h": _ICP_GICP,
 }
 
 ABI_VERSION = 2

@@ -1,4 +1,4 @@
-// icp_gicp_math.h -- the per-correspondence fp64 routines of the plane-to-plane (generalized) ICP (icp.hip, icp_gicp_api.h): the weight
+// icp_gicp_math.h -- the per-correspondence fp64 routines of the plane-to-plane (generalized) ICP (icp.hip, umereg_icp_gicp.h): the weight
 // W = (C_q + R C_s R^T)^-1 of a correspondence from the two normals, and its terms of the 6x6 normal equations.  Not part of the C ABI.
 //
 // GICP's regularised covariance of a locally planar point (eigenvalues (eps, 1, 1) in the frame of its normal n) is a function of the

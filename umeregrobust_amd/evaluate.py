@@ -381,7 +381,7 @@ def main(argv=None):
     parser.add_argument("--icp-estimation", choices=list(icp_plane.ESTIMATIONS), default="point_to_point",
                         help="estimation of the ICP refinement: the reference's point to point (default), point to plane on target "
                              "normals estimated on the device (include/umereg_icp_plane.h), or plane to plane (generalized ICP) on the "
-                             "normals of both clouds (csrc/icp_gicp_api.h)")
+                             "normals of both clouds (include/umereg_icp_gicp.h)")
     parser.add_argument("--icp-normal-knn", type=int, default=icp_plane.DEFAULT_KNN,
                         help="with --icp-estimation point_to_plane / plane_to_plane: neighbours per normal (3 .. 64)")
     parser.add_argument("--icp-normal-radius", type=float, default=None,

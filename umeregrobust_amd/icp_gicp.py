@@ -1,4 +1,4 @@
-"""The opt-in plane-to-plane (generalized) ICP refinement: the binding table of csrc/icp_gicp_api.h and the rules for epsilon.
+"""The opt-in plane-to-plane (generalized) ICP refinement: the binding table of include/umereg_icp_gicp.h and the rules for epsilon.
 
     ns, nt = ops.estimate_normals(src), ops.estimate_normals(tgt)            # the source's normals in the SOURCE's own frame
     reg = ops.icp_plane_to_plane(src, tgt, ns, nt, T_init, 0.2, 200)         # registration_generalized_icp(..., epsilon=1e-3)
@@ -8,34 +8,17 @@
 name for this form of Generalized ICP) and read `args.icp_gicp_epsilon` (1e-3) through `epsilon_of`; normals come from
 `args.icp_normal_knn` / `args.icp_normal_radius` as for point to plane, once for each cloud.
 
-The entries are declared in csrc/icp_gicp_api.h, not under include/, and typed here (ICP_GICP_SIGNATURES), not in `_lib.TABLES`."""
-import ctypes
+The entries are declared in include/umereg_icp_gicp.h and typed by `_lib.TABLES`; ICP_GICP_SIGNATURES is that table."""
 import numbers
 
 from . import _lib
 
-c_void_p, c_int, c_float, c_double, c_size_t = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_size_t
-
-# name -> (restype, argtypes); mirrors csrc/icp_gicp_api.h one to one
-ICP_GICP_SIGNATURES = {
-    "umereg_icp_plane_to_plane_workspace_bytes": (c_size_t, [c_int, c_int]),
-    "umereg_icp_plane_to_plane_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int, c_double,
-                                              c_double, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "umereg_icp_plane_to_plane_dev_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int,
-                                                  c_double, c_double, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                                  c_size_t, c_void_p]),
-    "umereg_icp_plane_to_plane_enqueue_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_float, c_int,
-                                                      c_double, c_double, c_float, c_int, c_int, c_void_p, c_void_p, c_size_t,
-                                                      c_void_p]),
-}
+ICP_GICP_SIGNATURES = _lib.TABLES["umereg_icp_gicp.h"]
+load_native = _lib.load
 
 ESTIMATION = "plane_to_plane"
 MIN_EPSILON, MAX_EPSILON = 1e-4, 1.0        # UMEREG_GICP_MIN_EPSILON / UMEREG_GICP_MAX_EPSILON
 DEFAULT_EPSILON = 1e-3                      # open3d's default, as recalled
-
-
-def load_native():
-    return _lib.load_typed(ICP_GICP_SIGNATURES)
 
 
 def check_epsilon(who, epsilon):

@@ -602,10 +602,8 @@ def icp_point_to_point(src_pts, tgt_pts, T_init, max_correspondence_distance=0.2
 def _icp_entries(lib, n_normals):
     """(size query, synchronous entry from a host start, the same from a device start, enqueue-only entry) of an estimation, by the
     number of normal sets it takes: the point-to-plane entries take the target's normals as one more pointer behind the two clouds,
-    the plane-to-plane entries (typed by icp_gicp's own table) the source's in front of them, and epsilon behind relative_rmse"""
+    the plane-to-plane entries the source's in front of them, and epsilon behind relative_rmse"""
     if n_normals == 2:
-        from . import icp_gicp
-        lib = icp_gicp.load_native()
         return (lib.umereg_icp_plane_to_plane_workspace_bytes, lib.umereg_icp_plane_to_plane_f32, lib.umereg_icp_plane_to_plane_dev_f32,
                 lib.umereg_icp_plane_to_plane_enqueue_f32)
     if n_normals:
