@@ -1056,3 +1056,5 @@ class PairMatchGraph(_PairGraph):
 
 # scipy.optimize.linear_sum_assignment on the device (include/umereg_assign.h; assign.py)
 from .assign import linear_sum_assignment  # noqa: E402,F401
+# the built-in sampling equalizer (csrc/equalize_api.h; equalizer.py)
+from .equalizer import equalize_cloud  # noqa: E402,F401

@@ -13,7 +13,8 @@ learning map, the ego box, the unlabelled mask, compaction in scan order) and on
 the transformed source (`rotate_rows`), the same calls the augmentation of a cached item makes.  There is no CPU fallback.
 
 The surface reconstruction of `lidar_point_cloud_completion` (NKSR, :511-533) is not part of this library; its label-transfer
-half is (`copy_labels_nearest`), and `complete_cloud` joins a caller-supplied `completion_fn(pts) -> new_pts` to it.
+half is (`copy_labels_nearest`), and `complete_cloud` joins a caller-supplied `completion_fn(pts) -> new_pts` to it
+(`equalizer.sampling_equalizer` is a ready-made one: the library's own density equalizer, not NKSR's output).
 
 The entry points of include/umereg_scan_prep.h are typed by `_lib.TABLES`; `scan_prep_raw` takes caller-owned outputs and
 workspace and never waits for the device."""
@@ -206,7 +207,8 @@ def completion_missing():
     return NotImplementedError(
         "use_pc_completion=True asks for the reference's NKSR surface reconstruction (lidar_point_cloud_completion), which is not part of "
         "this library: pass completion_fn(pts) -> new_pts (command line: --completion module:function), or switch it off "
-        "(use_pc_completion=False, command line: --nksr False)")
+        "(use_pc_completion=False, command line: --nksr False).  The library's own equalizer is a ready-made one: "
+        "umeregrobust_amd.equalizer.sampling_equalizer (command line: --completion umeregrobust_amd.equalizer:sampling_equalizer)")
 
 
 def complete_cloud(pts, seg, completion_fn, thr=LABEL_COPY_DIST_THR):
