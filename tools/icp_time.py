@@ -13,6 +13,17 @@
                  (0.10, -0.08, 0.05) m, correspondence distance 0.2 m (refine_registration's).
     Per estimation: iterations, fitness, inlier_rmse, rotation / translation error against the ground truth, and `ms`.
 
+With `--multi-scale` (default --out profiles/icp_multiscale/icp_time.jsonl) the tool measures coarse-to-fine ICP instead:
+  * `voxel`: ops.voxel_down_sample at 120 000 points of the street scene for voxel 0.8 / 0.4 / 0.2 m beside ops.voxel_first_index on the
+    same cloud (the thinning kernel the centroid pass is built on: its only fair yardstick); both include their one host read.
+  * `icp_multi_scale`: per case (the corner at 3 000 points, kitti_raw) and per start (the tool's usual one; one 0.5 m off:
+    (0.05, -0.04, 0.06) rad and (0.5, -0.4, 0.45) m), per estimation, the single-scale call (`single`; for the two normal-based
+    estimations `ms` includes the normals, as the multi-scale call re-estimates them per level) against ops.icp_multi_scale with
+    levels voxel 0.8 m / 0.4 m / the clouds as given, distances max(2 voxel, the case's) and the case's, 200 iterations per level
+    (`multi`: iterations per level, points per level, time, final error).
+  * `evaluate_pairs`: evaluate.evaluate_pairs over 8 synthetic KITTI-shaped pairs, wall clock per pair, single scale (overlapped
+    IcpJob) against --icp-voxel-sizes 0.8,0.4,0 (the synchronous branch: one host wait per level per pair).
+
 Every time is the median over `--iters` calls, each bracketed by its own pair of device events on the launch stream (the ICP calls end
 in their own wait for the device), after `--warmup` calls of the same shape."""
 import argparse
@@ -99,13 +110,77 @@ CASES = {
 }
 
 
+FAR_START = (0.05, -0.04, 0.06, 0.5, -0.4, 0.45)
+VOXEL_SIZES = (0.8, 0.4, 0.0)
+
+
+def multi_scale(args, dev, emit):
+    """the measurements of --multi-scale (see the module docstring)"""
+    import time
+    from types import SimpleNamespace
+    pts = torch.from_numpy(street_scene(120000, np.random.RandomState(1)).astype(np.float32)).to(dev)
+    line = dict(what="voxel", cloud="street_scene", n=120000, iters=args.iters, warmup=args.warmup)
+    for v in (0.8, 0.4, 0.2):
+        line[f"voxel_{v}"] = dict(m=int(ops.voxel_down_sample(pts, v).shape[0]),
+                                  down_sample_ms=median_ms(lambda: ops.voxel_down_sample(pts, v), args.iters, args.warmup),
+                                  first_index_ms=median_ms(lambda: ops.voxel_first_index(pts, v), args.iters, args.warmup))
+    emit(line)
+    for name, c in CASES.items():
+        n = 3000 if name == "corner" else c["n"]
+        dists = [max(2.0 * v, c["max_dist"]) if v else c["max_dist"] for v in VOXEL_SIZES]
+        for start, offset in (("usual", c["offset"]), ("far", FAR_START)):
+            src, tgt, gt, T0 = pair(c["cloud"], n, 0, offset, c["sigma"])
+            s_, t_ = torch.from_numpy(src).to(dev), torch.from_numpy(tgt).to(dev)
+            line = dict(what="icp_multi_scale", case=name, start=start, n_src=len(src), n_tgt=len(tgt), voxel_sizes=VOXEL_SIZES,
+                        max_correspondence_distances=dists, max_iteration=200, knn=args.knn, iters=args.iters, warmup=args.warmup)
+            line["start_rot_deg"], line["start_trans_m"] = errors(T0, gt)
+            single = dict(
+                point_to_point=lambda: ops.icp_point_to_point(s_, t_, T0, c["max_dist"], 200),
+                point_to_plane=lambda: ops.icp_point_to_plane(s_, t_, ops.estimate_normals(t_, args.knn), T0, c["max_dist"], 200),
+                plane_to_plane=lambda: ops.icp_plane_to_plane(s_, t_, ops.estimate_normals(s_, args.knn), ops.estimate_normals(t_, args.knn),
+                                                              T0, c["max_dist"], 200))
+            for est, fn in single.items():
+                multi = lambda: ops.icp_multi_scale(s_, t_, T0, VOXEL_SIZES, dists, [200] * 3, estimation=est, normal_knn=args.knn)  # noqa: E731
+                out = {}
+                for kind, call in (("single", fn), ("multi", multi)):
+                    ms = median_ms(call, args.iters, args.warmup)
+                    reg = call()
+                    rot, trans = errors(reg.transformation, gt)
+                    out[kind] = dict(iterations=reg.iterations, fitness=reg.fitness, inlier_rmse=reg.inlier_rmse, rot_err_deg=rot,
+                                     trans_err_m=trans, ms=ms)
+                    if kind == "multi":
+                        out[kind]["iterations_per_level"] = [lv.iterations for lv in reg.levels]
+                        out[kind]["points_per_level"] = [(lv.n_src, lv.n_tgt) for lv in reg.levels]
+                line[est] = out
+            emit(line)
+    from umeregrobust_amd.evaluate import evaluate_pairs, synthetic_pairs
+    from umeregrobust_amd.utils.general_utils import benchmark_config_path, update_namespace_from_yaml
+    cfg = update_namespace_from_yaml(SimpleNamespace(benchmark="kitti_test"), benchmark_config_path("kitti_test"))
+    cfg.batch_size = 1
+    pairs = list(synthetic_pairs("kitti_test", range(8), dev))
+    line = dict(what="evaluate_pairs", pairs=len(pairs), benchmark="kitti_test", voxel_sizes=VOXEL_SIZES)
+    for kind, extra in (("single", {}), ("multi", dict(icp_voxel_sizes=list(VOXEL_SIZES)))):
+        a = SimpleNamespace(**vars(cfg), **extra)
+        res = evaluate_pairs(pairs, a, rng=np.random.RandomState(0))       # warm-up: workspaces, streams
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(3):
+            res = evaluate_pairs(pairs, a, rng=np.random.RandomState(0))
+        torch.cuda.synchronize()
+        line[kind] = dict(ms_per_pair=1e3 * (time.perf_counter() - t0) / (3 * len(pairs)), mrte=res["mrte"], mrre=res["mrre"])
+    emit(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "icp_plane", "icp_time.jsonl"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--multi-scale", action="store_true", help="measure voxel_down_sample and icp_multi_scale instead")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--knn", type=int, default=30)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(REPO, "profiles", "icp_multiscale" if args.multi_scale else "icp_plane", "icp_time.jsonl")
     if not torch.cuda.is_available():
         raise SystemExit("icp_time: no HIP device visible; a time is a measurement on the GPU")
     dev = torch.device("cuda:0")
@@ -115,6 +190,9 @@ def main():
             text = json.dumps(line)
             print(text, flush=True)
             f.write(text + "\n")
+
+        if args.multi_scale:
+            return multi_scale(args, dev, emit)
 
         for n in (50000, 120000):
             pts = torch.from_numpy(street_scene(n, np.random.RandomState(1)).astype(np.float32)).to(dev)

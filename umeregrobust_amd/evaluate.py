@@ -8,7 +8,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import icp_gicp, icp_plane, ops, streams as _streams
+from . import icp_gicp, icp_multiscale, icp_plane, ops, streams as _streams
 from .host_rng import choice_uniform_noreplace
 from .pipeline import (PairBatch, PairResult, RegistrationPipeline, _draw_keypoints, _draw_keypoints_host, _index_tensor,  # noqa: F401
                        _phase_a, _phase_b, _PinnedRing, _ring, _to_host, phase_a_route, register_pair)
@@ -127,6 +127,8 @@ def refine_registration(R_hat, t_hat, args, pairs, tform_dev=None, estimation=No
     ops.icp_point_to_plane on the target's normals (ops.estimate_normals with args.icp_normal_knn = 30 neighbours and
     args.icp_normal_radius = None), computed once per target cloud; "plane_to_plane" with ops.icp_plane_to_plane on the normals of
     both clouds (the source's in its own frame: the kernel rotates them) and args.icp_gicp_epsilon = 1e-3.
+    args.icp_voxel_sizes (with args.icp_level_distances / args.icp_level_iterations, icp_multiscale.levels_of): coarse to fine with
+    that estimation, ops.icp_multi_scale, one host wait per level; unset: the single-scale calls below, as ever.
     The reference re-opens its dataset here; this takes the raw clouds instead:
     pairs = iterable of (src_pts_raw [n,3], tgt_pts_raw [m,3], gt_tform [4,4]).
     tform_dev: optional [P,4,4] float32 DEVICE tensor holding the same (R_hat, t_hat) as 4 x 4 transforms: the ICP then starts from
@@ -137,6 +139,7 @@ def refine_registration(R_hat, t_hat, args, pairs, tform_dev=None, estimation=No
     max_it = int(getattr(args, "icp_max_iteration", 200))
     estimation, normal_knn, normal_radius = icp_plane.estimation_of(args, estimation)
     gicp_epsilon = icp_gicp.epsilon_of(args) if estimation == icp_gicp.ESTIMATION else None
+    levels = icp_multiscale.levels_of(args)
     for itr, (src_pts_raw, tgt_pts_raw, gt_tform) in enumerate(pairs):
         if tform_dev is not None:
             tform_hat = tform_dev[itr].contiguous()
@@ -145,7 +148,10 @@ def refine_registration(R_hat, t_hat, args, pairs, tform_dev=None, estimation=No
             tform_hat[:3, :3] = np.asarray(R_hat[itr].detach().cpu() if isinstance(R_hat[itr], torch.Tensor) else R_hat[itr])
             tform_hat[:3, 3] = np.asarray(t_hat[itr].detach().cpu() if isinstance(t_hat[itr], torch.Tensor) else t_hat[itr])
             tform_hat[3, 3] = 1
-        if estimation == "point_to_plane":
+        if levels is not None:
+            reg = ops.icp_multi_scale(src_pts_raw, tgt_pts_raw, tform_hat, *zip(*levels), estimation=estimation, normal_knn=normal_knn,
+                                      normal_radius=normal_radius, epsilon=icp_gicp.DEFAULT_EPSILON if gicp_epsilon is None else gicp_epsilon)
+        elif estimation == "point_to_plane":
             normals = ops.estimate_normals(tgt_pts_raw, normal_knn, normal_radius)
             reg = ops.icp_point_to_plane(src_pts_raw, tgt_pts_raw, normals, tform_hat, max_corr, max_it)
         elif estimation == icp_gicp.ESTIMATION:
@@ -202,6 +208,9 @@ def evaluate_pairs(pairs, args, rng=np.random, refine=True, verbose=False, overl
     max_it = int(getattr(args, "icp_max_iteration", 200))
     estimation, normal_knn, normal_radius = icp_plane.estimation_of(args)
     gicp_epsilon = icp_gicp.epsilon_of(args) if estimation == icp_gicp.ESTIMATION else icp_gicp.DEFAULT_EPSILON
+    # coarse to fine (args.icp_voxel_sizes): no IcpJob -- such pairs take the synchronous branch of read_back (`job is None`), one host
+    # wait per level per pair; an overlapped pyramid job is deliberately not built
+    multi_scale = icp_multiscale.levels_of(args) is not None
 
     def read_back(p):
         R_hat, t_hat, st, _keep, T_dev, job, clouds = p     # _keep: the pair's input tensors stay alive until its last kernel is done
@@ -248,7 +257,8 @@ def evaluate_pairs(pairs, args, rng=np.random, refine=True, verbose=False, overl
                 collect.append(dict(rtume_tform=out.rtume_tform[0].clone(), cond=out.cond, match=cl(out.match), match_d=cl(out.match_d),
                                     prob=cl(out.prob), ume_src=cl(out.ume_src), ume_tgt=cl(out.ume_tgt), T_sel=T_dev[0].clone()))
             job = None
-            if refine and st is not None and src_raw.is_cuda and src_raw.dtype == torch.float32 and tgt_raw.dtype == torch.float32:
+            if refine and not multi_scale and st is not None and src_raw.is_cuda and src_raw.dtype == torch.float32 \
+                    and tgt_raw.dtype == torch.float32:
                 # (point to plane: the target's normals, once per target cloud, on the pair's stream behind the selection like the
                 # chain itself -- opting in adds no host read; plane to plane: the source's too, in the source's own frame)
                 src_normals = ops.estimate_normals(src_raw, normal_knn, normal_radius) if estimation == icp_gicp.ESTIMATION else None
@@ -388,11 +398,21 @@ def main(argv=None):
                         help="with --icp-estimation point_to_plane / plane_to_plane: hybrid search, neighbours farther than this are dropped")
     parser.add_argument("--icp-gicp-epsilon", type=float, default=icp_gicp.DEFAULT_EPSILON,
                         help="with --icp-estimation plane_to_plane: the regularised covariance's small eigenvalue, in [1e-4, 1]")
+    parser.add_argument("--icp-voxel-sizes", type=icp_multiscale.parse_list, default=None,
+                        help="coarse-to-fine ICP: voxel sizes per level, strictly decreasing, the last may be 0 = the clouds as given "
+                             "(e.g. 0.8,0.4,0); unset: single scale")
+    parser.add_argument("--icp-level-distances", type=icp_multiscale.parse_list, default=None,
+                        help="with --icp-voxel-sizes: max correspondence distance per level (default: max(2 voxel, the single-scale "
+                             "distance); a choice, not tuned on real scans)")
+    parser.add_argument("--icp-level-iterations", type=lambda s: icp_multiscale.parse_list(s, int), default=None,
+                        help="with --icp-voxel-sizes: iteration limit per level (default: the single-scale limit on every level)")
     cli = parser.parse_args(argv)
     config_path = benchmark_config_path(cli.benchmark)
     args = update_namespace_from_yaml(argparse.Namespace(benchmark=cli.benchmark), config_path)
     args.icp_estimation, args.icp_normal_knn, args.icp_normal_radius = cli.icp_estimation, cli.icp_normal_knn, cli.icp_normal_radius
     args.icp_gicp_epsilon = cli.icp_gicp_epsilon
+    args.icp_voxel_sizes, args.icp_level_distances, args.icp_level_iterations = cli.icp_voxel_sizes, cli.icp_level_distances, cli.icp_level_iterations
+    icp_multiscale.levels_of(args)                 # (a bad list is an error now, not at the first pair)
     rank, local_rank, world = init_distributed()
     device = torch.device("cuda", local_rank)
     torch.cuda.set_device(device)

@@ -1058,3 +1058,5 @@ class PairMatchGraph(_PairGraph):
 from .assign import linear_sum_assignment  # noqa: E402,F401
 # the built-in sampling equalizer (csrc/equalize_api.h; equalizer.py)
 from .equalizer import equalize_cloud  # noqa: E402,F401
+# voxel-centroid downsampling and coarse-to-fine ICP (csrc/voxel_centroid_api.h; icp_multiscale.py)
+from .icp_multiscale import icp_multi_scale, voxel_down_sample, voxel_pyramid  # noqa: E402,F401
